@@ -12,7 +12,11 @@ pairs_per_s = query x index-row cosines per second of the search part alone (HIP
 extra.configs2_sharded (every N): BASELINE configs[2] as a strong-scaling leg - 10M rows x 512-d split over the N ranks, 1,000
 replicated queries, local exact top-10, one all-gather of (score, id) + merge: search_ms, allgather_merge_ms, pairs_per_s.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step).  --full adds everything
+else after the timed steps: a second, profiled pass of the K steps (per-kernel HIP events: kernel_ms_per_step, the rooflines,
+search_ms_per_step, pairs_per_s), the search alone, the recall check against the oracle, the CPU baseline and the side
+configurations.  --dump-outputs DIR writes what the last timed step computed (rank 0's view) as DIR/<name>.npy.
 N > 1: one rank per GPU.  Started from a plain shell the script launches `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...` itself as a child process and relays rank 0's JSON line;
 started under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
@@ -297,6 +301,24 @@ def configs2_sharded(dev, rank, world, total_rows=10_000_000, nq=1000, k=10, rep
     return res
 
 
+DUMP_ARRAY_BYTES = 16 << 20   # per array: three arrays + their row lists stay well inside 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array (a device tensor) as path/<name>.npy in float32 (float64 for integer ids, exact below 2^53).
+    An array above DUMP_ARRAY_BYTES keeps a fixed, seeded sample of its rows, whose indices go to path/<name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if np.issubdtype(a.dtype, np.integer) else np.float32)
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            keep = max(1, DUMP_ARRAY_BYTES // (a.nbytes // len(a)))
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -360,8 +382,11 @@ def main():
     ap.add_argument("--index-rows", type=int, default=1_000_000)
     ap.add_argument("--queries", type=int, default=10)
     ap.add_argument("--k", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side configurations (configs[2] shard, configs[3], configs[4] tower)")
+    ap.add_argument("--full", action="store_true", help="after the headline: the profiled pass, search alone, oracle recall check, "
+                    "CPU baseline and side configurations (off: only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (scores, ids, embeddings) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side configurations (configs[2] shard, configs[3], configs[4] tower)")
     ap.add_argument("--lanes", type=int, default=1, help="split each step's frames over this many HIP streams / towers")
     # the defaults are BASELINE.json configs[1] (the metric's configuration); the two flags below select the
     # configs[4]-shaped variant (ViT-L/14, fp8 GEMMs, 768-d rows) as an additional measurement, never the headline
@@ -429,7 +454,6 @@ def main():
     patches = torch.empty((B * G2, kpad), dtype=torch.bfloat16, device=dev)
     emb = torch.empty((B, d_emb), dtype=torch.float32, device=dev)
     ring = {"pos": 0}
-    ev_s0, ev_s1 = [], []
 
     def embed(lane, i, pos):
         b = B // L
@@ -440,7 +464,7 @@ def main():
         towers[lane].encode_patches(pt, b, normalize=True, out=em)
         index.write_device(pos + lane * b, em)          # rows are already L2-normalised by the tower epilogue
 
-    def step(i, timed):
+    def step(i, search_events=None):
         pos = ring["pos"]
         if L == 1:
             embed(0, i, pos)
@@ -453,14 +477,13 @@ def main():
             for lane in range(L):
                 main.wait_stream(lanes[lane])
         ring["pos"] = (pos + B) % (N - B + 1) if N > B else 0
-        if timed:
+        if search_events is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
         D, I = sharded.search(queries, k, normalize=True)
-        if timed:
+        if search_events is not None:
             e1.record()
-            ev_s0.append(e0)
-            ev_s1.append(e1)
+            search_events.append((e0, e1))
         return D, I
 
     def barrier():
@@ -468,86 +491,25 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # the timed steps carry no instrumentation: per-kernel events and the search brackets belong to the --full pass below
     for i in range(args.warmup):
-        step(i, False)
+        step(i)
     barrier()
-    _ffi.profile_reset(local_rank)
-    _ffi.profile_enable(True, local_rank)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        D, I = step(i, True)
+        D, I = step(i)
     barrier()
     elapsed = time.perf_counter() - t0
-    _ffi.profile_enable(False, local_rank)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    prof = _ffi.profile_read(local_rank)
-    search_ms = sum(a.elapsed_time(b) for a, b in zip(ev_s0, ev_s1)) / max(1, len(ev_s0))
-    # the search alone, 50 times back to back with no per-kernel events, then 10 times with every launch of its tail
-    # bracketed (profile level 2): the breakdown costs a few microseconds per event pair, so it stays out of the timed region
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(50):
-        sharded.search(queries, k, normalize=True)
-    e1.record()
-    torch.cuda.synchronize()
-    search_alone_ms = e0.elapsed_time(e1) / 50
-    _ffi.profile_reset(local_rank)
-    _ffi.profile_enable(2, local_rank)
-    for _ in range(10):
-        sharded.search(queries, k, normalize=True)
-    torch.cuda.synchronize()
-    _ffi.profile_enable(False, local_rank)
-    search_kernels_us = {n: v["ms"] / v["launches"] * 1e3 for n, v in sorted(_ffi.profile_read(local_rank).items())}
-    if world > 1:
-        dist.barrier()
-    c2 = None
-    if headline and not args.no_extra:
-        c2 = configs2_sharded(dev, rank, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"scores": D, "ids": I, "embeddings": emb})
 
+    out = None
     if rank == 0:
         frames_total = B * args.steps * world
-        # HBM bytes per launch from the committed PMC passes of this same command (tools/pmc_aggregate.py); null when the
-        # profile was taken at another batch size
-        pmc = {}
-        try:
-            with open(os.path.join(ROOT, "profiles", PMC_FILE)) as f:
-                pmc = json.load(f)
-        except OSError:
-            pass
-        pmc_ok = headline and B == pmc.get("_frames_per_step", -1) and N == 1_000_000
-
-        def traffic(*kernels):
-            if not pmc_ok or not kernels or not all(k in pmc for k in kernels):
-                return None
-            tot = sum(pmc[k]["hbm_bytes"] * pmc[k]["launches"] for k in kernels)
-            return tot / sum(pmc[k]["launches"] for k in kernels)
-        gemm = {n: v for n, v in prof.items() if n.startswith("gemm_")}
-        gemm_flop = sum(v["work"] for v in gemm.values())
-        gemm_ms = sum(v["ms"] for v in gemm.values())
-        gemm_launches = sum(v["launches"] for v in gemm.values())
-        gemm_tf = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms else 0.0
-        # the peak the GEMM launches are priced against: dense bf16, or - in an e4m3 mode - the harmonic mix of the bf16 and fp8
-        # (2 x) peaks weighted by the share of the FLOPs that actually run on the fp8 MFMA (the sites and blocks of the preset)
-        mfma_peak = MFMA_BF16_PEAK_TF
-        if args.compute != "bf16":
-            T_, D_, M_, L_ = cfg.tokens, cfg.width, cfg.mlp, cfg.layers
-            site = {1: 2.0 * T_ * D_ * 3 * D_, 2: 2.0 * T_ * D_ * D_, 4: 2.0 * T_ * D_ * M_, 8: 2.0 * T_ * D_ * M_}
-            total = 2.0 * G2 * kpad * D_ + L_ * sum(site.values()) + 2.0 * D_ * d_emb
-            f8 = sum(v for b, v in site.items() if tower.fp8_sites & b) * (L_ - tower.fp8_first_layer)
-            mfma_peak = total / ((total - f8) / MFMA_BF16_PEAK_TF + f8 / (2 * MFMA_BF16_PEAK_TF))
-
-        def hbm(name):
-            v = prof.get(name)
-            if not v or not v["ms"]:
-                return None
-            a = v["work"] / (v["ms"] * 1e-3) / 1e9
-            return {"bound": "hbm", "achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": a / HBM_PEAK_GBS,
-                    "traffic": traffic(PMC_NAME[name]), "kernel": name, "avg_launch_ms": v["ms"] / v["launches"], "launches": int(v["launches"]),
-                    "bytes_per_launch": v["work"] / v["launches"]}
-
         out = {
             "metric": "frames/s embedded (+ query-vs-index cosine pairs/s; top-10 recall vs CPU ref)",
             "value": frames_total / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -559,55 +521,132 @@ def main():
                                     f"{N}-row x {d_emb}-d fp32 index cosine top-{k} (per GPU)"),
                        "frames_per_step_per_gpu": B, "frames_total": frames_total, "index_rows_per_gpu": N, "queries": Q, "k": k,
                        "parallelism": f"{world} x (frames + index rows sharded per GPU); one all-gather of (score,id) + merge"},
-            "pairs_per_s": N * world * Q / (search_ms * 1e-3), "search_ms_per_step": search_ms,
-            "search_alone": {"ms": search_alone_ms, "pairs_per_s": N * world * Q / (search_alone_ms * 1e-3),
-                             "note": "50 searches back to back outside the timed region, no per-kernel events",
-                             "per_launch_us_with_events": search_kernels_us},
-            "roofline": {"bound": "mfma", "achieved": gemm_tf, "peak": mfma_peak, "unit": "TFLOP/s", "frac": gemm_tf / mfma_peak,
-                         "traffic": traffic(*[k for k in pmc if k.startswith(("gemm_big_kernel<bf16", "gemm_pers_kernel", "gemm_kernel<bf16", "qkv_attn_kernel<bf16", "qkv_attn_pers_kernel<bf16"))]),
-                         "kernel": ("gemm_big_kernel<bf16> / gemm_pers_kernel (fc1) / qkv_attn_pers_kernel<bf16> (QKV projection fused with attention) / gemm_kernel<bf16>" if args.compute == "bf16" else "gemm_big8_kernel (e4m3 sites) + the bf16 GEMMs of the other sites, patch embedding and projection")
-                                   + " (all tower GEMM launches of the timed region)",
-                         "avg_launch_ms": gemm_ms / max(1, gemm_launches), "launches": int(gemm_launches),
-                         "flop_per_launch": gemm_flop / max(1, gemm_launches),
-                         "by_call_site": {n: {"TFLOP/s": v["work"] / (v["ms"] * 1e-3) / 1e12, "ms": v["ms"] / v["launches"]}
-                                          for n, v in sorted(gemm.items())}},
-            # the index pass that actually streams the rows: the bf16 candidate scan when the index keeps one (the exact float32
-            # scan then only runs for queries whose verification failed), else the float32 scan
-            "roofline_search": hbm("scan16_groupmax" if "scan16_groupmax" in prof else "scan_groupmax"),
-            "roofline_preprocess": hbm("preprocess_emit"),
-            "kernel_ms_per_step": {n: v["ms"] / args.steps for n, v in sorted(prof.items())},
         }
-        # recall / id check of the last search against the oracle (rank 0's shard; N == 1: the whole index)
-        from oracle import search_ref as S
-        Xh = index.reconstruct_n(0, N)
-        qn = S.normalize_rows_core(queries.cpu().numpy()).astype(np.float32)
-        Dl, Il = index.search_device(queries, k, normalize=True)
-        Dr, Ir = S.flat_ip_search(Xh, qn, k, dtype=np.float64)
-        Il, Dl = Il.cpu().numpy(), Dl.cpu().numpy()
-        out["recall_at_10"] = float(np.mean([len(set(Il[q]) & set(Ir[q])) / k for q in range(Q)]))
-        out["ids_exact"] = bool(np.array_equal(Il, Ir))
-        out["max_abs_score_err"] = float(np.abs(Dl - Dr).max())
-        # SURVEY.md section 8 hard part 2: recall with and without the re-rank.  "Without" = the top-k of the bf16 candidate
-        # ranking alone (<bf16(row), q> in f32, emulated here with torch on the same rows; the library never reports these scores)
-        Xd = torch.from_numpy(Xh).to(dev)
-        approx = torch.from_numpy(qn).to(dev) @ Xd.to(torch.bfloat16).to(torch.float32).T
-        Ia = torch.topk(approx, k, dim=1).indices.cpu().numpy()
-        out["recall_at_10_candidates_only"] = float(np.mean([len(set(Ia[q]) & set(Ir[q])) / k for q in range(Q)]))
-        out["ids_exact_candidates_only"] = bool(np.array_equal(Ia, Ir))
-        del Xd, approx
-        for key in ("roofline", "roofline_search", "roofline_preprocess"):
-            if out.get(key):
-                out[key]["traffic_source"] = (f"profiles/{PMC_FILE} (rocprofv3 --pmc passes of this same command, tools/pmc_aggregate.py; "
-                                              "not re-measured in this run)") if pmc_ok else None
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, weights, Xh[:100_000], qn, k)
-        if world == 1 and headline and not args.no_extra:
-            # free the headline's buffers first: the streaming index alone is 15 GB
-            del frame_tiles, patches, emb, index, sharded, towers, tower, Xh
-            torch.cuda.empty_cache()
-            out["extra"] = side_configs(dev, weights)
-        if c2 is not None:
-            out.setdefault("extra", {})["configs2_sharded"] = c2
+    if args.full:
+        # the same steps again with every launch of the kernels that carry the step bracketed by HIP events (profile level 1) and
+        # the search part bracketed on its own: per-kernel times, rooflines and pairs/s come from this pass, not the timed one
+        ev_search = []
+        _ffi.profile_reset(local_rank)
+        _ffi.profile_enable(True, local_rank)
+        for i in range(args.steps):
+            step(i, ev_search)
+        barrier()
+        _ffi.profile_enable(False, local_rank)
+        prof = _ffi.profile_read(local_rank)
+        search_ms = sum(a.elapsed_time(b) for a, b in ev_search) / max(1, len(ev_search))
+        # the search alone, 50 times back to back with no per-kernel events, then 10 times with every launch of its tail
+        # bracketed (profile level 2): the breakdown costs a few microseconds per event pair
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(50):
+            sharded.search(queries, k, normalize=True)
+        e1.record()
+        torch.cuda.synchronize()
+        search_alone_ms = e0.elapsed_time(e1) / 50
+        _ffi.profile_reset(local_rank)
+        _ffi.profile_enable(2, local_rank)
+        for _ in range(10):
+            sharded.search(queries, k, normalize=True)
+        torch.cuda.synchronize()
+        _ffi.profile_enable(False, local_rank)
+        search_kernels_us = {n: v["ms"] / v["launches"] * 1e3 for n, v in sorted(_ffi.profile_read(local_rank).items())}
+        if world > 1:
+            dist.barrier()
+        c2 = None
+        if headline and not args.no_extra:
+            c2 = configs2_sharded(dev, rank, world)
+
+        if rank == 0:
+            # HBM bytes per launch from the committed PMC passes of this same command (tools/pmc_aggregate.py); null when the
+            # profile was taken at another batch size
+            pmc = {}
+            try:
+                with open(os.path.join(ROOT, "profiles", PMC_FILE)) as f:
+                    pmc = json.load(f)
+            except OSError:
+                pass
+            pmc_ok = headline and B == pmc.get("_frames_per_step", -1) and N == 1_000_000
+
+            def traffic(*kernels):
+                if not pmc_ok or not kernels or not all(k in pmc for k in kernels):
+                    return None
+                tot = sum(pmc[k]["hbm_bytes"] * pmc[k]["launches"] for k in kernels)
+                return tot / sum(pmc[k]["launches"] for k in kernels)
+            gemm = {n: v for n, v in prof.items() if n.startswith("gemm_")}
+            gemm_flop = sum(v["work"] for v in gemm.values())
+            gemm_ms = sum(v["ms"] for v in gemm.values())
+            gemm_launches = sum(v["launches"] for v in gemm.values())
+            gemm_tf = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms else 0.0
+            # the peak the GEMM launches are priced against: dense bf16, or - in an e4m3 mode - the harmonic mix of the bf16 and fp8
+            # (2 x) peaks weighted by the share of the FLOPs that actually run on the fp8 MFMA (the sites and blocks of the preset)
+            mfma_peak = MFMA_BF16_PEAK_TF
+            if args.compute != "bf16":
+                T_, D_, M_, L_ = cfg.tokens, cfg.width, cfg.mlp, cfg.layers
+                site = {1: 2.0 * T_ * D_ * 3 * D_, 2: 2.0 * T_ * D_ * D_, 4: 2.0 * T_ * D_ * M_, 8: 2.0 * T_ * D_ * M_}
+                total = 2.0 * G2 * kpad * D_ + L_ * sum(site.values()) + 2.0 * D_ * d_emb
+                f8 = sum(v for b, v in site.items() if tower.fp8_sites & b) * (L_ - tower.fp8_first_layer)
+                mfma_peak = total / ((total - f8) / MFMA_BF16_PEAK_TF + f8 / (2 * MFMA_BF16_PEAK_TF))
+
+            def hbm(name):
+                v = prof.get(name)
+                if not v or not v["ms"]:
+                    return None
+                a = v["work"] / (v["ms"] * 1e-3) / 1e9
+                return {"bound": "hbm", "achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": a / HBM_PEAK_GBS,
+                        "traffic": traffic(PMC_NAME[name]), "kernel": name, "avg_launch_ms": v["ms"] / v["launches"], "launches": int(v["launches"]),
+                        "bytes_per_launch": v["work"] / v["launches"]}
+
+            out.update({
+                "pairs_per_s": N * world * Q / (search_ms * 1e-3), "search_ms_per_step": search_ms,
+                "search_alone": {"ms": search_alone_ms, "pairs_per_s": N * world * Q / (search_alone_ms * 1e-3),
+                                 "note": "50 searches back to back outside the timed region, no per-kernel events",
+                                 "per_launch_us_with_events": search_kernels_us},
+                "roofline": {"bound": "mfma", "achieved": gemm_tf, "peak": mfma_peak, "unit": "TFLOP/s", "frac": gemm_tf / mfma_peak,
+                             "traffic": traffic(*[k for k in pmc if k.startswith(("gemm_big_kernel<bf16", "gemm_pers_kernel", "gemm_kernel<bf16", "qkv_attn_kernel<bf16", "qkv_attn_pers_kernel<bf16"))]),
+                             "kernel": ("gemm_big_kernel<bf16> / gemm_pers_kernel (fc1) / qkv_attn_pers_kernel<bf16> (QKV projection fused with attention) / gemm_kernel<bf16>" if args.compute == "bf16" else "gemm_big8_kernel (e4m3 sites) + the bf16 GEMMs of the other sites, patch embedding and projection")
+                                       + " (all tower GEMM launches of the profiled pass)",
+                             "avg_launch_ms": gemm_ms / max(1, gemm_launches), "launches": int(gemm_launches),
+                             "flop_per_launch": gemm_flop / max(1, gemm_launches),
+                             "by_call_site": {n: {"TFLOP/s": v["work"] / (v["ms"] * 1e-3) / 1e12, "ms": v["ms"] / v["launches"]}
+                                              for n, v in sorted(gemm.items())}},
+                # the index pass that actually streams the rows: the bf16 candidate scan when the index keeps one (the exact float32
+                # scan then only runs for queries whose verification failed), else the float32 scan
+                "roofline_search": hbm("scan16_groupmax" if "scan16_groupmax" in prof else "scan_groupmax"),
+                "roofline_preprocess": hbm("preprocess_emit"),
+                "kernel_ms_per_step": {n: v["ms"] / args.steps for n, v in sorted(prof.items())},
+            })
+            # recall / id check of the last search against the oracle (rank 0's shard; N == 1: the whole index)
+            from oracle import search_ref as S
+            Xh = index.reconstruct_n(0, N)
+            qn = S.normalize_rows_core(queries.cpu().numpy()).astype(np.float32)
+            Dl, Il = index.search_device(queries, k, normalize=True)
+            Dr, Ir = S.flat_ip_search(Xh, qn, k, dtype=np.float64)
+            Il, Dl = Il.cpu().numpy(), Dl.cpu().numpy()
+            out["recall_at_10"] = float(np.mean([len(set(Il[q]) & set(Ir[q])) / k for q in range(Q)]))
+            out["ids_exact"] = bool(np.array_equal(Il, Ir))
+            out["max_abs_score_err"] = float(np.abs(Dl - Dr).max())
+            # SURVEY.md section 8 hard part 2: recall with and without the re-rank.  "Without" = the top-k of the bf16 candidate
+            # ranking alone (<bf16(row), q> in f32, emulated here with torch on the same rows; the library never reports these scores)
+            Xd = torch.from_numpy(Xh).to(dev)
+            approx = torch.from_numpy(qn).to(dev) @ Xd.to(torch.bfloat16).to(torch.float32).T
+            Ia = torch.topk(approx, k, dim=1).indices.cpu().numpy()
+            out["recall_at_10_candidates_only"] = float(np.mean([len(set(Ia[q]) & set(Ir[q])) / k for q in range(Q)]))
+            out["ids_exact_candidates_only"] = bool(np.array_equal(Ia, Ir))
+            del Xd, approx
+            for key in ("roofline", "roofline_search", "roofline_preprocess"):
+                if out.get(key):
+                    out[key]["traffic_source"] = (f"profiles/{PMC_FILE} (rocprofv3 --pmc passes of this same command, tools/pmc_aggregate.py; "
+                                                  "not re-measured in this run)") if pmc_ok else None
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg, weights, Xh[:100_000], qn, k)
+            if world == 1 and headline and not args.no_extra:
+                # free the headline's buffers first: the streaming index alone is 15 GB
+                del frame_tiles, patches, emb, index, sharded, towers, tower, Xh
+                torch.cuda.empty_cache()
+                out["extra"] = side_configs(dev, weights)
+            if c2 is not None:
+                out.setdefault("extra", {})["configs2_sharded"] = c2
+    if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -2,8 +2,8 @@
 """Aggregate two rocprofv3 counter passes (FETCH_SIZE, WRITE_SIZE) into per-kernel HBM traffic.
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/fetch -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/write -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/fetch -- python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/write -- python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline
     python tools/pmc_aggregate.py OUT profiles/rNN_pmc_traffic.json
 
 Corrections follow MI355X_MICROARCH.md (HBM section): both counters are in KiB; on gfx950 FETCH_SIZE reports exactly

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MFMA pipe utilisation per kernel from one rocprofv3 PMC pass:
 
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 4 --warmup 1 --no-extra --no-cpu-baseline
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 4 --warmup 1 --full --no-extra --no-cpu-baseline
     python tools/pmc_mfma.py DIR out.json
 
 SQ_VALU_MFMA_BUSY_CYCLES sums the cycles every SIMD's matrix pipe was busy (16 per v_mfma_f32_16x16x32_bf16: checked against the
