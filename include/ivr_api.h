@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IVR_API_VERSION 4
+#define IVR_API_VERSION 5
 #define IVR_MAX_K 2048          /* reference: k=50 default, SearchOptions.limit <= 1000 (system.py:91) */
 
 typedef enum ivr_status {
@@ -168,6 +168,24 @@ int ivr_linear(ivr_ctx *ctx, int f32_mode, int epilogue, const void *x /*DEV*/, 
 int ivr_linear_fp8(ivr_ctx *ctx, int epilogue, const void *x /*DEV*/, const void *w /*DEV*/, const float *colscale /*DEV*/,
                    const float *bias /*DEV*/, int M, int N, int K, int act, void *out /*DEV*/, int out_fp8,
                    float *resid /*DEV*/, ivr_stream stream);
+
+/* Attention of the towers, exposed for parity tests and kernel benchmarks: att[n*T, D] = softmax(Q K^T [+ causal mask]) V per
+ * (image, head), the scaled_dot_product_attention inside the HF attention modules (modeling_clip.py:259-277).  qkv: DEV
+ * [n*T, 3D], row = q | k | v, head h at columns h*64 .. h*64+63 of each part; no 1/sqrt(64) scale is applied (the towers fold it
+ * into the Q weights).  f32_mode = 1: qkv / att float32, T <= 301 (K and V of a head in LDS), n <= 65535; else qkv bf16 and att
+ * bf16 (out_fp8 = 0) or saturated OCP e4m3 (out_fp8 = 1, only where a kernel writes it: T <= 640).  D = 64 * heads, 1 <= heads <= 32,
+ * 1 <= T <= 1024, pointers 16-byte aligned; n = 0 is a no-op (qkv / att may be NULL). */
+int ivr_attention(ivr_ctx *ctx, int f32_mode, const void *qkv /*DEV*/, int n, int T, int D, int heads, int causal, int out_fp8,
+                  void *att /*DEV*/, ivr_stream stream);
+/* Fused variant: qkv = xn W^T + bias rounded to bf16, then ivr_attention (not causal); xn DEV bf16 [n*T, D], w DEV bf16 [3D, D],
+ * bias DEV float32 [3D].  T <= 64, D = 64 * heads >= 192, n * T * D * 2 < 2^31, pointers 16-byte aligned; n = 0 is a no-op. */
+int ivr_qkv_attention(ivr_ctx *ctx, const void *xn /*DEV*/, const void *w /*DEV*/, const float *bias /*DEV*/, int n, int T, int D,
+                      int heads, int out_fp8, void *att /*DEV*/, ivr_stream stream);
+/* LayerNorm of the towers (nn.LayerNorm, modeling_clip.py:332-336): out row r = LN(x row r*row_mul + (offs ? offs[r] : 0)) with
+ * g, b DEV float32 [D]; x DEV float32; offs DEV int32 [rows] or NULL; out_kind 0 bf16, 1 float32, 2 saturated e4m3;
+ * reverse = 1 walks the rows backwards (same result).  D % 4 == 0, D <= 2048, pointers 16-byte aligned; rows = 0 is a no-op. */
+int ivr_layernorm(ivr_ctx *ctx, int out_kind, const float *x /*DEV*/, int row_mul, const int *offs /*DEV*/, const float *g /*DEV*/,
+                  const float *b /*DEV*/, float eps, int rows, int D, int reverse, void *out /*DEV*/, ivr_stream stream);
 
 /* The weight quantiser of IVR_COMPUTE_FP8, exposed so that it can be checked without a GPU: HOST float32 -> HOST OCP e4m3 bytes
  * (bias 7, no infinity, max 448), round to nearest even, saturating; NaN -> 0x7f | sign. */

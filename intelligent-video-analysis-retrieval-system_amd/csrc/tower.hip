@@ -15,8 +15,8 @@ int ivr_tower_create(ivr_ctx *ctx, const ivr_tower_desc *d, ivr_tower **out) {
     IVR_REQUIRE(d->kind == IVR_KIND_VISION || d->kind == IVR_KIND_TEXT, "ivr_tower_create: kind=%d", d->kind);
     IVR_REQUIRE(d->width >= 64 && d->width % 64 == 0 && d->width <= 2048, "ivr_tower_create: width=%d must be a multiple of 64 in [64,2048]",
                 d->width);
-    IVR_REQUIRE(d->heads >= 1 && d->width == d->heads * 64, "ivr_tower_create: head_dim must be 64 (width=%d heads=%d)", d->width,
-                d->heads);
+    IVR_REQUIRE(d->heads >= 1 && d->heads <= 32 && d->width == d->heads * 64, "ivr_tower_create: head_dim must be 64 (width=%d heads=%d)",
+                d->width, d->heads);
     IVR_REQUIRE(d->mlp >= 64 && d->mlp % 64 == 0, "ivr_tower_create: mlp=%d must be a multiple of 64", d->mlp);
     IVR_REQUIRE(d->layers >= 1 && d->layers <= 64, "ivr_tower_create: layers=%d", d->layers);
     IVR_REQUIRE(d->tokens >= 1 && d->tokens <= 1024, "ivr_tower_create: tokens=%d", d->tokens);
@@ -618,6 +618,55 @@ int ivr_linear_fp8(ivr_ctx *ctx, int epilogue, const void *x, const void *w, con
     g.act = act;
     g.tag = "linear_fp8";
     return ivr_launch_gemm_fp8(epilogue, g, (hipStream_t)stream);
+}
+
+static bool al16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+int ivr_attention(ivr_ctx *ctx, int f32_mode, const void *qkv, int n, int T, int D, int heads, int causal, int out_fp8, void *att,
+                  ivr_stream stream) {
+    IVR_REQUIRE(ctx && (n == 0 || (qkv && att)), "ivr_attention: NULL argument");
+    IVR_REQUIRE((f32_mode == 0 || f32_mode == 1) && (causal == 0 || causal == 1) && (out_fp8 == 0 || out_fp8 == 1),
+                "ivr_attention: f32_mode=%d causal=%d out_fp8=%d", f32_mode, causal, out_fp8);
+    // heads bounded before the product (64 * heads must not wrap)
+    IVR_REQUIRE(heads >= 1 && heads <= 32 && D == 64 * heads, "ivr_attention: head_dim must be 64 (D=%d heads=%d, D <= 2048)", D, heads);
+    IVR_REQUIRE(T >= 1 && T <= 1024, "ivr_attention: T=%d outside [1,1024]", T);
+    // every launch's grid (at most one workgroup per image, head and 16-query tile) stays below 2^31
+    IVR_REQUIRE(n >= 0 && (int64_t)n * T <= 0x7fffffff && (int64_t)n * heads * ((T + 15) / 16) <= 0x7fffffff &&
+                    (!f32_mode || n <= 65535), "ivr_attention: n=%d", n);
+    // float32 kernel: K and V of a head in LDS, 2 * T * 68 floats <= 160 KiB
+    IVR_REQUIRE(!f32_mode || (T <= 301 && !out_fp8), "ivr_attention: float32 mode needs T <= 301 (T=%d) and float32 output", T);
+    IVR_REQUIRE(!out_fp8 || T <= 640, "ivr_attention: e4m3 output only from the kernels of T <= 640 (T=%d)", T);
+    IVR_REQUIRE(al16(qkv) && al16(att), "ivr_attention: qkv and att must be 16-byte aligned");
+    if (n == 0) return IVR_OK;
+    IVR_HIP(hipSetDevice(ctx->device));
+    return ivr_launch_attention(f32_mode != 0, qkv, att, n, T, D, heads, causal, (hipStream_t)stream, out_fp8 != 0);
+}
+
+int ivr_qkv_attention(ivr_ctx *ctx, const void *xn, const void *w, const float *bias, int n, int T, int D, int heads, int out_fp8,
+                      void *att, ivr_stream stream) {
+    IVR_REQUIRE(ctx && w && bias && (n == 0 || (xn && att)), "ivr_qkv_attention: NULL argument");
+    IVR_REQUIRE(out_fp8 == 0 || out_fp8 == 1, "ivr_qkv_attention: out_fp8=%d", out_fp8);
+    IVR_REQUIRE(n >= 0 && T >= 1 && (int64_t)n * T <= 0x7fffffff, "ivr_qkv_attention: n=%d T=%d", n, T);
+    IVR_REQUIRE(ivr_fused_qkv_attention_shape_ok(n * T, T, D, heads, 0),
+                "ivr_qkv_attention: unsupported shape n=%d T=%d D=%d heads=%d (T <= 64, D = 64 * heads >= 192)", n, T, D, heads);
+    IVR_REQUIRE(al16(xn) && al16(w) && al16(bias) && al16(att), "ivr_qkv_attention: operands must be 16-byte aligned");
+    if (n == 0) return IVR_OK;
+    IVR_HIP(hipSetDevice(ctx->device));
+    return ivr_launch_qkv_attention(xn, w, bias, att, n, T, D, heads, out_fp8 != 0, (hipStream_t)stream);
+}
+
+int ivr_layernorm(ivr_ctx *ctx, int out_kind, const float *x, int row_mul, const int *offs, const float *g, const float *b, float eps,
+                  int rows, int D, int reverse, void *out, ivr_stream stream) {
+    IVR_REQUIRE(ctx && g && b && (rows == 0 || (x && out)), "ivr_layernorm: NULL argument");
+    IVR_REQUIRE(out_kind == OUT_BF16 || out_kind == OUT_F32 || out_kind == OUT_FP8, "ivr_layernorm: out_kind=%d", out_kind);
+    IVR_REQUIRE(D >= 4 && D % 4 == 0 && D <= 2048, "ivr_layernorm: D=%d must be a multiple of 4 in [4,2048]", D);
+    IVR_REQUIRE(rows >= 0 && row_mul >= 0 && (reverse == 0 || reverse == 1), "ivr_layernorm: rows=%d row_mul=%d reverse=%d", rows,
+                row_mul, reverse);
+    IVR_REQUIRE(eps >= 0.f && std::isfinite(eps), "ivr_layernorm: eps=%g", (double)eps);
+    IVR_REQUIRE(al16(x) && al16(g) && al16(b) && al16(out), "ivr_layernorm: x, g, b and out must be 16-byte aligned");
+    if (rows == 0) return IVR_OK;
+    IVR_HIP(hipSetDevice(ctx->device));
+    return ivr_launch_layernorm(out_kind, x, row_mul, offs, g, b, eps, out, rows, D, (hipStream_t)stream, reverse);
 }
 
 int ivr_quantize_e4m3_host(const float *src, uint8_t *dst, int64_t n) {

@@ -37,6 +37,9 @@ int ivr_launch_layernorm(int out_kind, const float *x, int row_mul, const int *o
 int ivr_launch_attention(bool f32, const void *qkv, void *att, int n, int T, int D, int heads, int causal, hipStream_t s,
                          bool out_fp8 = false);
 // fused QKV projection + attention (bf16, T <= 64, not causal): xn [n*T, D] bf16, w [3D, D] bf16, bias [3D] -> att [n*T, D]
+// shape_ok: the kernel's hard limits, always enforced by the launcher; ok: shape_ok and the size policy (IVR_FUSED_QKV overrides
+// the policy, never the limits)
+bool ivr_fused_qkv_attention_shape_ok(int M, int T, int D, int heads, int causal);
 bool ivr_fused_qkv_attention_ok(int M, int T, int D, int heads, int causal);
 int ivr_launch_qkv_attention(const void *xn, const void *w, const float *bias, void *att, int n, int T, int D, int heads, bool out_fp8,
                              hipStream_t s, int reverse = 0);

@@ -164,8 +164,9 @@ __global__ void eos_pos_kernel(const int64_t *__restrict__ ids, int q, int T, in
 }
 
 // ---------------------------------------------------------------------------------------------
-// LayerNorm: one wave per row, row held in registers, two-pass statistics in float32
-// source row of output row r: r * row_mul + (offs ? offs[r] : 0)
+// LayerNorm: one wave per row, row held in registers, two-pass statistics in float32 on the row shifted by its first element
+// (d = x - x[0]: exact for a constant row, so that row yields exactly b; exact too for rows whose spread is small next to their
+// mean, so a mean of 1e3 costs no accuracy).  source row of output row r: r * row_mul + (offs ? offs[r] : 0)
 // ---------------------------------------------------------------------------------------------
 template <typename TOut>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict__ x, int row_mul, const int *__restrict__ offs,
@@ -179,17 +180,26 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
     const float4 *src = reinterpret_cast<const float4 *>(x + srow * D);
     const int nv = D >> 2;
     float4 v[8];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int idx = lane + 64 * i;
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (idx < nv) v[i] = src[idx];
+    }
+    const float x0 = __shfl(v[0].x, 0, 64);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int idx = lane + 64 * i;
         if (idx < nv) {
-            v[i] = src[idx];
+            v[i].x -= x0;
+            v[i].y -= x0;
+            v[i].z -= x0;
+            v[i].w -= x0;
             s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
         }
     }
-    const float mean = ivr_wave_sum(s) / (float)D;
+    const float mean = ivr_wave_sum(s) / (float)D;            // of d = x - x0
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -2926,11 +2936,16 @@ int ivr_launch_gemm_fp8(int epi, const GemmArgs &g, hipStream_t s) {
     return launch_gemm8_t<EPI_STORE, -1, false>(g, s);
 }
 
+bool ivr_fused_qkv_attention_shape_ok(int M, int T, int D, int heads, int causal) {
+    // whole images per 256-row tile, at least three K stages, one 64-wide head per column block, 32-bit buffer offsets
+    if (T < 1 || T > 64 || causal || D % 64 != 0 || D < 192 || D > 2048 || heads != D / 64 || M < 0 || M % T != 0) return false;
+    return (int64_t)M * D * 2 < 0x7fffffff && (int64_t)3 * D * D * 2 < 0x7fffffff;
+}
+
 bool ivr_fused_qkv_attention_ok(int M, int T, int D, int heads, int causal) {
-    // whole images per 256-row tile, at least three K stages, one 64-wide head per column block; large problems only by default
-    // (IVR_FUSED_QKV=1 forces it wherever it is valid, 0 switches it off)
-    if (T < 1 || T > 64 || causal || D % 64 != 0 || D < 192 || heads * 64 != D || M % T != 0) return false;
-    if ((int64_t)M * D * 2 >= 0x7fffffff || (int64_t)3 * D * D * 2 >= 0x7fffffff) return false;
+    // the shape limits above, then the size policy: large problems only by default (IVR_FUSED_QKV=1 forces it wherever the
+    // shape is valid, 0 switches it off)
+    if (!ivr_fused_qkv_attention_shape_ok(M, T, D, heads, causal)) return false;
     const int mode = env_int("IVR_FUSED_QKV", -1);
     if (mode == 0) return false;
     if (mode == 1) return true;
@@ -2942,7 +2957,9 @@ int ivr_launch_qkv_attention(const void *xn, const void *w, const float *bias, v
                              hipStream_t s, int reverse) {
     if (n <= 0) return IVR_OK;
     const int M = n * T;
-    IVR_REQUIRE(ivr_fused_qkv_attention_ok(M, T, D, heads, 0) || env_int("IVR_FUSED_QKV", -1) == 1, "fused qkv+attention: unsupported shape");
+    // the size policy is the caller's (ivr_fused_qkv_attention_ok); the shape limits hold whatever the environment says
+    IVR_REQUIRE(ivr_fused_qkv_attention_shape_ok(M, T, D, heads, 0), "fused qkv+attention: unsupported shape (n=%d T=%d D=%d heads=%d)",
+                n, T, D, heads);
     const auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
     IVR_REQUIRE(al16(xn) && al16(w) && al16(bias) && al16(att), "fused qkv+attention: operands must be 16-byte aligned");
     QkvAttnArgs g;

@@ -26,7 +26,7 @@ class TowerDesc(C.Structure):
                                                                       ("fp8_first_layer", C.c_int)]
 
 
-API_VERSION = 4
+API_VERSION = 5
 FP8_SITE = {"qkv": 1, "o": 2, "fc1": 4, "fc2": 8}
 
 
@@ -54,6 +54,9 @@ _SIGS = {
     "ivr_tower_workspace_bytes": (_i64, [_p]),
     "ivr_linear": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "ivr_quantize_e4m3_host": (_i, [_p, _p, _i64]),
+    "ivr_attention": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "ivr_qkv_attention": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "ivr_layernorm": (_i, [_p, _i, _p, _i, _p, _p, _p, _f, _i, _i, _i, _p, _p]),
     "ivr_linear_fp8": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p]),
     "ivr_l2_normalize": (_i, [_p, _p, _i64, _i, _p, _p]),
     "ivr_index_create": (_i, [_p, _i, _i64, C.POINTER(_p)]),
