@@ -31,8 +31,8 @@ struct ivr_tower {
     void *qkv = nullptr;     // [rows, 3D]
     void *att = nullptr;     // [rows, D]
     void *hid = nullptr;     // [rows, mlp]
-    void *xn_cls = nullptr;  // [max_batch, D]   bf16 LN rows of token 0 (fp8 mode, fp8_mlp_cls_bf16)
-    void *hid_cls = nullptr; // [max_batch, mlp] bf16 MLP hidden rows of token 0
+    void *xn_cls = nullptr;  // [max_batch, D]   LN rows of token 0 (vision: fp8 side path, pruned last block), compute dtype
+    void *hid_cls = nullptr; // [max_batch, mlp] MLP hidden rows of token 0 (+ an e4m3 copy behind them for bf16 fc1 -> e4m3 fc2)
     int sites = 0;           // fp8 mode: effective IVR_FP8_SITE_* mask (blocks >= d.fp8_first_layer)
     bool mlp_cls = false;    // fp8 mode: token-0 rows take fc1 / fc2 in bf16
     void *pool = nullptr;    // [max_batch, D] pooled + LN rows (compute dtype)

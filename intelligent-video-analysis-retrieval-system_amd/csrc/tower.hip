@@ -214,8 +214,17 @@ int env_zigzag() {
     return v;
 }
 
-// one transformer stack over `rows` = n*T residual rows already in t->resid
-int run_layers(ivr_tower *t, int n, int T, hipStream_t s) {
+// IVR_PRUNE_LAST=0 runs the last block of a vision tower on every row (A/B runs, tests); read on every encode call
+bool env_prune_last() {
+    const char *e = getenv("IVR_PRUNE_LAST");
+    return e ? (atoi(e) != 0) : true;
+}
+
+// one transformer stack over `rows` = n*T residual rows already in t->resid.  prune_last: only row i*T of image i (token 0) of the
+// final residual stream is read afterwards, so the last block runs everything after LN1 + QKV on those n rows alone: attention
+// for query 0, attn-out, LN2, fc1 and fc2 are row by row (K and V of the attention still need every token, hence LN1 + QKV on
+// all rows).  The other rows of the final residual stream are left as the block found them.
+int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
     const ivr_tower_desc &d = t->d;
     const bool f32 = d.compute == IVR_COMPUTE_F32;
 
@@ -234,17 +243,22 @@ int run_layers(ivr_tower *t, int n, int T, hipStream_t s) {
         const int sites = i >= d.fp8_first_layer ? t->sites : 0;      // blocks in front of fp8_first_layer run in bf16
         const bool q8 = sites & IVR_FP8_SITE_QKV, o8 = sites & IVR_FP8_SITE_ATTN_OUT, f18 = sites & IVR_FP8_SITE_FC1, f28 = sites & IVR_FP8_SITE_FC2;
         const bool mlp_cls = t->mlp_cls && (f18 || f28);
+        const bool last = prune_last && i == d.layers - 1;
         if (t->debug_out && t->debug_layer == i)
             IVR_HIP(hipMemcpyAsync(t->debug_out, t->resid, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, s));
         rc = ivr_launch_layernorm(kind(q8), t->resid, 1, nullptr, wptr<float>(t, p + "ln1_g"), wptr<float>(t, p + "ln1_b"), d.ln_eps,
                                   t->xn, rows, D, s, zz);
         if (rc) return rc;
         GemmArgs g;
+        int att_ld = D;                  // row stride of the attention rows attn-out reads (pruned + unfused: every T-th row of att)
         if (!f32 && !q8 && ivr_fused_qkv_attention_ok(rows, T, D, d.heads, d.causal)) {
-            // short sequences, bf16: projection and attention in one kernel, the QKV activations stay in LDS
-            rc = ivr_launch_qkv_attention(t->xn, wptr<void>(t, p + "qkv_w"), wptr<float>(t, p + "qkv_b"), t->att, n, T, D, d.heads, o8, s);
+            // short sequences, bf16: projection and attention in one kernel, the QKV activations stay in LDS (pruned: query 0 of each
+            // image only, written to the compact rows att[0, n))
+            rc = ivr_launch_qkv_attention(t->xn, wptr<void>(t, p + "qkv_w"), wptr<float>(t, p + "qkv_b"), t->att, n, T, D, d.heads, o8, s, 0,
+                                          last);
             if (rc) return rc;
         } else {
+            if (last) att_ld = T * D;
             g.A = t->xn;
             g.lda = D;
             g.ldw = D;
@@ -262,18 +276,62 @@ int run_layers(ivr_tower *t, int n, int T, hipStream_t s) {
         }
         g = GemmArgs();
         g.A = t->att;
-        g.lda = D;
+        g.lda = att_ld;
         g.ldw = D;
-        g.M = rows;
+        g.M = last ? n : rows;
         g.N = D;
         g.K = D;
         g.bias = wptr<float>(t, p + "o_b");
         g.resid = t->resid;
-        g.ldr = D;
-        g.tag = "gemm_attn_out";
+        g.ldr = last ? T * D : D;        // pruned: row i*T of the residual stream
+        g.tag = last ? "gemm_attn_out_cls" : "gemm_attn_out";
         g.reverse_m = zz;
         rc = layer_gemm(t, o8, EPI_RESID, g, p + "o_w", s);
         if (rc) return rc;
+        if (last) {
+            // LN2 -> fc1 -> fc2 on the n token-0 rows.  The sites keep their dtypes, except that with the fp8 side path (mlp_cls)
+            // these rows run in bf16, as they always did: the block launches no e4m3 MLP GEMM at all then.
+            const bool c18 = f18 && !mlp_cls, c28 = f28 && !mlp_cls;
+            rc = ivr_launch_layernorm(kind(c18), t->resid, T, nullptr, wptr<float>(t, p + "ln2_g"), wptr<float>(t, p + "ln2_b"), d.ln_eps,
+                                      t->xn_cls, n, D, s);
+            if (rc) return rc;
+            g = GemmArgs();
+            g.A = t->xn_cls;
+            g.lda = D;
+            g.ldw = D;
+            g.M = n;
+            g.N = d.mlp;
+            g.K = D;
+            g.bias = wptr<float>(t, p + "fc1_b");
+            g.out = t->hid_cls;
+            g.ldo = d.mlp;
+            g.act = d.act;
+            g.out8 = c18 && c28;
+            g.tag = "gemm_fc1_cls";
+            rc = layer_gemm(t, c18, EPI_STORE, g, p + "fc1_w", s);
+            if (rc) return rc;
+            const void *hc_a = t->hid_cls;
+            if (!c18 && c28) {           // bf16 fc1 feeding an e4m3 fc2: converted copy behind the bf16 rows, as for t->hid
+                unsigned char *h8 = reinterpret_cast<unsigned char *>(t->hid_cls) + (size_t)t->max_batch * d.mlp * 2;
+                rc = ivr_launch_bf16_to_e4m3(t->hid_cls, h8, (int64_t)n * d.mlp, s);
+                if (rc) return rc;
+                hc_a = h8;
+            }
+            g = GemmArgs();
+            g.A = hc_a;
+            g.lda = d.mlp;
+            g.ldw = d.mlp;
+            g.M = n;
+            g.N = D;
+            g.K = d.mlp;
+            g.bias = wptr<float>(t, p + "fc2_b");
+            g.resid = t->resid;
+            g.ldr = T * D;
+            g.tag = "gemm_fc2_cls";
+            rc = layer_gemm(t, c28, EPI_RESID, g, p + "fc2_w", s);
+            if (rc) return rc;
+            continue;
+        }
         rc = ivr_launch_layernorm(kind(f18), t->resid, 1, nullptr, wptr<float>(t, p + "ln2_g"), wptr<float>(t, p + "ln2_b"), d.ln_eps,
                                   t->xn, rows, D, s);
         if (rc) return rc;
@@ -474,11 +532,14 @@ int ivr_tower_finalize(ivr_tower *t, int max_batch) {
     const size_t es = d.compute == IVR_COMPUTE_F32 ? 4 : 2;                       // qkv, pooled rows
     const size_t ea = es;        // GEMM A operands (LN out, attention out, MLP hidden): sized for bf16, e4m3 sites use half of it
     const size_t rows = (size_t)max_batch * d.tokens;
+    // token-0 rows (vision towers): the fp8 side path and the pruned last block; e4m3 copy of the MLP hidden for a bf16 fc1 + e4m3 fc2
+    const bool vis = d.kind == IVR_KIND_VISION;
+    const size_t h8 = ((t->sites & IVR_FP8_SITE_FC2) && !(t->sites & IVR_FP8_SITE_FC1)) ? 1 : 0;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_resid = al(rows * D * 4), b_xn = al(rows * D * ea), b_qkv = al(rows * 3 * D * es), b_att = al(rows * D * ea),
-                 b_hid = al(rows * d.mlp * (ea + (((t->sites & IVR_FP8_SITE_FC2) && !(t->sites & IVR_FP8_SITE_FC1)) ? 1 : 0))), b_pool = al((size_t)max_batch * D * es),
+                 b_hid = al(rows * d.mlp * (ea + h8)), b_pool = al((size_t)max_batch * D * es),
                  b_pf = al((size_t)max_batch * std::max(D, d.out_dim) * 4), b_eos = al((size_t)max_batch * 4),
-                 b_xc = t->mlp_cls ? al((size_t)max_batch * D * 2) : 0, b_hc = t->mlp_cls ? al((size_t)max_batch * d.mlp * 2) : 0;
+                 b_xc = vis ? al((size_t)max_batch * D * ea) : 0, b_hc = vis ? al((size_t)max_batch * d.mlp * (ea + h8)) : 0;
     t->ws_bytes = b_resid + b_xn + b_qkv + b_att + b_hid + b_pool + b_pf + b_eos + b_xc + b_hc;
     IVR_HIP(hipMalloc(&t->ws, t->ws_bytes));
     IVR_HIP(hipMemset(t->ws, 0, t->ws_bytes));
@@ -543,7 +604,9 @@ int ivr_tower_encode_image(ivr_tower *t, const void *patches, int n, int normali
                                   n * T, D, s);
         if (rc) return rc;
     }
-    rc = run_layers(t, n, T, s);
+    // run_pool reads row i*T of the final residual stream and nothing else, unless a debug capture wants all of it
+    const bool prune = env_prune_last() && !(t->debug_out && t->debug_layer == d.layers);
+    rc = run_layers(t, n, T, prune, s);
     if (rc) return rc;
     return run_pool(t, n, T, nullptr, normalize, out, s);
 }
@@ -563,7 +626,7 @@ int ivr_tower_encode_text(ivr_tower *t, const int64_t *ids, int q, int T, int no
     int rc = ivr_launch_text_embed(t->resid, ids, wptr<float>(t, "tok"), wptr<float>(t, "pos"), q, T, d.width, d.vocab, d.eos_id,
                                    t->eos_pos, s);
     if (rc) return rc;
-    rc = run_layers(t, q, T, s);
+    rc = run_layers(t, q, T, false, s);      // the pooled row sits at a device-side EOS offset: no pruning
     if (rc) return rc;
     return run_pool(t, q, T, t->eos_pos, normalize, out, s);
 }

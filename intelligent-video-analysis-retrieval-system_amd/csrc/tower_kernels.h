@@ -41,8 +41,9 @@ int ivr_launch_attention(bool f32, const void *qkv, void *att, int n, int T, int
 // the policy, never the limits)
 bool ivr_fused_qkv_attention_shape_ok(int M, int T, int D, int heads, int causal);
 bool ivr_fused_qkv_attention_ok(int M, int T, int D, int heads, int causal);
+// pooled: only query 0 of each image (the pooled row of the vision towers) is attended; its row goes to att[i, D] (compact [n, D])
 int ivr_launch_qkv_attention(const void *xn, const void *w, const float *bias, void *att, int n, int T, int D, int heads, bool out_fp8,
-                             hipStream_t s, int reverse = 0);
+                             hipStream_t s, int reverse = 0, int pooled = 0);
 int ivr_launch_vision_cls(float *resid, const float *cls, const float *pos, int n, int T, int D, hipStream_t s);
 int ivr_launch_text_embed(float *resid, const int64_t *ids, const float *tok, const float *pos, int q, int T, int D, int vocab,
                           int eos, int *eos_pos, hipStream_t s);

@@ -1676,8 +1676,9 @@ struct QkvAttnArgs {
     const void *X = nullptr;      // LayerNorm output [rows, D] bf16
     const void *W = nullptr;      // fused QKV weight [3D, D] bf16 (rows: q | k | v, attention scale folded into q)
     const float *bias = nullptr;  // [3D]
-    void *att = nullptr;          // [rows, D] bf16 (or e4m3 bytes when out8)
+    void *att = nullptr;          // [rows, D] bf16 (or e4m3 bytes when out8); pooled: [rows / T, D]
     int M = 0, D = 0, T = 0, heads = 0, G = 0, group_m = 4, reverse = 0;
+    int pooled = 0;               // attention for query 0 of each image only (the unit that holds it), written to row image
 };
 
 constexpr int QA_WBYTES = 192 * ROWB;                         // one W stage: q_h, k_h, v_h rows = 24 KiB
@@ -1875,7 +1876,8 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(QkvAttnArgs g) {
 #endif
 
     // ---- attention: units (image, 16-query tile) dealt round-robin to the waves
-    const int Tn = g.T, nqt = (Tn + 15) >> 4, units = g.G * nqt;
+    // (pooled: only the unit that holds query 0 of each image, G units per tile instead of G * nqt)
+    const int Tn = g.T, nqt = g.pooled ? 1 : (Tn + 15) >> 4, units = g.G * nqt;
     const int gl = lane >> 4, c = lane & 15;
     constexpr float L2E = 1.4426950408889634f;
     for (int u = wave; u < units; u += 8) {
@@ -1975,7 +1977,8 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(QkvAttnArgs g) {
         }
         const float inv = __builtin_amdgcn_rcpf(sum);
         const int64_t grow = (int64_t)m0 + R0 + q;
-        TOut *op = reinterpret_cast<TOut *>(g.att) + grow * g.D + h * 64 + gl * 4;
+        const int64_t orow = g.pooled ? (int64_t)(m0 / Tn) + img : grow;      // pooled: compact row of the image
+        TOut *op = reinterpret_cast<TOut *>(g.att) + orow * g.D + h * 64 + gl * 4;
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
             f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -1984,7 +1987,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(QkvAttnArgs g) {
                 const uint4 vf = make_uint4(vt[nt][2 * ks].x, vt[nt][2 * ks].y, vt[nt][2 * ks + 1].x, vt[nt][2 * ks + 1].y);
                 o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf), __builtin_bit_cast(bf16x8_t, pf[ks]), o, 0, 0, 0);
             }
-            if (q < Tn && grow < g.M) {
+            if ((g.pooled ? q == 0 : q < Tn) && grow < g.M) {
                 const float v[4] = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
                 El<TOut>::store4(op + nt * 16, v);
             }
@@ -2213,7 +2216,8 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
     }
 
     // ---- attention: units (image, 16-query tile) dealt round-robin to the waves
-    const int Tn = g.T, nqt = (Tn + 15) >> 4, units = g.G * nqt;
+    // (pooled: only the unit that holds query 0 of each image, G units per tile instead of G * nqt)
+    const int Tn = g.T, nqt = g.pooled ? 1 : (Tn + 15) >> 4, units = g.G * nqt;
     const int gl = lane >> 4, c = lane & 15;
     constexpr float L2E = 1.4426950408889634f;
     for (int u = wave; u < units; u += 8) {
@@ -2313,7 +2317,8 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
         }
         const float inv = __builtin_amdgcn_rcpf(sum);
         const int64_t grow = (int64_t)m0 + R0 + q;
-        TOut *op = reinterpret_cast<TOut *>(g.att) + grow * g.D + h_cur * 64 + gl * 4;
+        const int64_t orow = g.pooled ? (int64_t)(m0 / Tn) + img : grow;      // pooled: compact row of the image
+        TOut *op = reinterpret_cast<TOut *>(g.att) + orow * g.D + h_cur * 64 + gl * 4;
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
             f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -2322,7 +2327,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
                 const uint4 vf = make_uint4(vt[nt][2 * ks].x, vt[nt][2 * ks].y, vt[nt][2 * ks + 1].x, vt[nt][2 * ks + 1].y);
                 o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf), __builtin_bit_cast(bf16x8_t, pf[ks]), o, 0, 0, 0);
             }
-            if (q < Tn && grow < g.M) {
+            if ((g.pooled ? q == 0 : q < Tn) && grow < g.M) {
                 const float v[4] = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
                 El<TOut>::store4(op + nt * 16, v);
             }
@@ -2954,7 +2959,7 @@ bool ivr_fused_qkv_attention_ok(int M, int T, int D, int heads, int causal) {
 }
 
 int ivr_launch_qkv_attention(const void *xn, const void *w, const float *bias, void *att, int n, int T, int D, int heads, bool out_fp8,
-                             hipStream_t s, int reverse) {
+                             hipStream_t s, int reverse, int pooled) {
     if (n <= 0) return IVR_OK;
     const int M = n * T;
     // the size policy is the caller's (ivr_fused_qkv_attention_ok); the shape limits hold whatever the environment says
@@ -2974,10 +2979,11 @@ int ivr_launch_qkv_attention(const void *xn, const void *w, const float *bias, v
     g.G = 256 / T;
     g.group_m = std::max(1, env_int("IVR_QKV_GROUP_M", 4));
     g.reverse = reverse;
+    g.pooled = pooled != 0;
     const int RT = g.G * T, MT = (M + RT - 1) / RT;
     const int grid = 8 * ((MT + 7) / 8) * heads;
-    // FLOP: the projection (2 M 3D D) and the attention products (4 T^2 64 per image and head)
-    IvrProf prof("gemm_qkv_attention", s, 2.0 * M * 3.0 * D * D + 4.0 * n * heads * (double)T * T * 64);
+    // FLOP: the projection (2 M 3D D) and the attention products (4 T^2 64 per image and head; pooled: one 16-query unit of T keys)
+    IvrProf prof("gemm_qkv_attention", s, 2.0 * M * 3.0 * D * D + 4.0 * n * heads * (double)(pooled ? std::min(T, 16) : T) * T * 64);
     const int qpers = env_int("IVR_QKV_PERS", 1);           // 0: never, 2: always (tests), default: from two tiles per CU on
     if (qpers == 2 || (qpers == 1 && (int64_t)MT * heads >= 2 * device_cu_count())) {
         const int pgrid = device_cu_count() / 8 * 8;
