@@ -261,6 +261,19 @@ constexpr int BM = 128, BN = 128, ROWB = 128;            // ROWB: bytes of K per
 constexpr int TILE_BYTES = BM * ROWB;                     // 16 KiB per operand per stage
 constexpr int GEMM_LDS = 2 * 2 * TILE_BYTES;              // 64 KiB
 
+// Tile order of the GEMMs and the fused QKV + attention kernel.  Workgroups b, b+8, b+16, ... share an XCD (one L2).  XCD x owns
+// the row panels p = x (mod 8); inside an XCD the panels are walked in groups of group_m: a group's X panels stay in that L2 while
+// its column tiles are swept, and neighbouring workgroups use the same W tile.  xcd_panels is the number of panels of an XCD, so
+// its list holds xcd_panels * NT tiles; xcd_tile maps position i < xcd_panels * NT of that list to (row panel tm, column tile tn).
+__device__ __forceinline__ int xcd_panels(int MT, int xcd) { return MT > xcd ? (MT - xcd + 7) >> 3 : 0; }
+__device__ __forceinline__ void xcd_tile(int i, int xcd, int MT, int NT, int gm, int reverse, int &tm, int &tn) {
+    const int per = gm * NT, grp = i / per, within = i - grp * per;
+    const int gme = min(gm, xcd_panels(MT, xcd) - grp * gm);
+    tm = xcd + 8 * (grp * gm + within % gme);
+    tn = within / gme;
+    if (reverse) tm = MT - 1 - tm;
+}
+
 template <typename T>
 __device__ __forceinline__ void mma_chunk(const u32x4 &w, const u32x4 &x, f32x4 &acc);
 template <>
@@ -283,21 +296,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: keeps the DMA addressing scalar
     const int wm = wave >> 1, wn = wave & 1;
     const int MT = (g.M + BM - 1) / BM, NT = (g.N + BN - 1) / BN;
-    // Tile order.  Workgroups b, b+8, b+16, ... share an XCD (one L2).  XCD x owns the row panels p = x (mod 8); inside
-    // an XCD the panels are walked in groups of GROUP_M: a group's X panels (GROUP_M x 128 rows x K) stay in that L2 while
-    // its column tiles are swept, and neighbouring workgroups use the same W tile.
+    const int xcd = blockIdx.x & 7, i = blockIdx.x >> 3;
+    if (i >= xcd_panels(MT, xcd) * NT) return;
     int tm, tn;
-    {
-        const int xcd = blockIdx.x & 7, i = blockIdx.x >> 3;
-        const int lx = MT > xcd ? (MT - xcd + 7) >> 3 : 0;      // panels owned by this XCD
-        if (i >= lx * NT) return;
-        const int gm = g.group_m;
-        const int per = gm * NT, grp = i / per, within = i - grp * per;
-        const int gme = min(gm, lx - grp * gm);
-        tm = xcd + 8 * (grp * gm + within % gme);
-        tn = within / gme;
-        if (g.reverse_m) tm = MT - 1 - tm;
-    }
+    xcd_tile(i, xcd, MT, NT, g.group_m, g.reverse_m, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     constexpr int EPR = ROWB / (int)sizeof(T);   // elements of K per step
     const int KT = g.K / EPR;
@@ -605,6 +607,17 @@ __device__ __forceinline__ void wait_vm_barrier() {
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
+// Fragment reads and waits of the software-pipelined K loops (gemm_big_tile, qkv_attn_body, gemm_pers_kernel): four 16-row
+// fragments 2048 bytes apart from one address, and a counted LDS wait that the scheduler moves nothing across.
+#define IVR_RD4(DST, ADDR, O0)                                                                            \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[0]) : "v"(ADDR), "n"(O0));                      \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[1]) : "v"(ADDR), "n"(O0 + 2048));               \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[2]) : "v"(ADDR), "n"(O0 + 4096));               \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[3]) : "v"(ADDR), "n"(O0 + 6144));
+#define IVR_LGKM(N)                                                                                       \
+    asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory");                                                \
+    __builtin_amdgcn_sched_barrier(0);
+
 // ---------------------------------------------------------------------------------------------
 // GEMM, large-tile version: 256 x 256 tile, 8 waves as 2(m) x 4(n), each wave 128 x 64 = 8 x 4 MFMA tiles.
 // Same staging scheme as gemm_kernel (two LDS buffers of 64 KiB filled by buffer_load ... lds, swizzled source, asm
@@ -634,7 +647,7 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &g, const int vb, u
     const int wm = wave >> 2, wn = wave & 3;
     const int MT = (g.M + LBM - 1) / LBM, NT = (g.N + LBN - 1) / LBN;
     int tm, tn;
-    {
+    {                                                 // xcd_tile's order, written out: through the helper this kernel schedules differently
         const int xcd = vb & 7, i = vb >> 3;          // vb: the tile's position in the launch order (blockIdx.x of the plain kernel)
         const int lx = MT > xcd ? (MT - xcd + 7) >> 3 : 0;
         if (i >= lx * NT) return;
@@ -692,14 +705,6 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &g, const int vb, u
 
 #define IVR_ROW(XF, WF, MT)                                                                                \
     _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) mma_chunk<T>(WF[nt], XF[MT], acc[nt][MT]);            \
-    __builtin_amdgcn_sched_barrier(0);
-#define IVR_RD4(DST, ADDR, O0)                                                                             \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[0]) : "v"(ADDR), "n"(O0));                      \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[1]) : "v"(ADDR), "n"(O0 + 2048));               \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[2]) : "v"(ADDR), "n"(O0 + 4096));               \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[3]) : "v"(ADDR), "n"(O0 + 6144));
-#define IVR_LGKM(N)                                                                                        \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory");                                                \
     __builtin_amdgcn_sched_barrier(0);
 
     u32x4 xa0[8], wa0[4], xa1[8], wa1[4];
@@ -775,8 +780,6 @@ __device__ __forceinline__ void gemm_big_tile(const GemmArgs &g, const int vb, u
     IVR_LGKM(0)
     IVR_STAMP(2)
 #undef IVR_ROW
-#undef IVR_RD4
-#undef IVR_LGKM
 
     if (sizeof(T) == 2 && (EPI == EPI_STORE || EPI == EPI_RESID) && g.wide_epi) {
         // (contains the barrier after which every wave has read its last fragments; N is a multiple of 64: a wave block is all in or all out)
@@ -894,7 +897,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big8_kernel(GemmArgs g) {
     const int wm = wave >> 2, wn = wave & 3;
     const int MT = (g.M + LBM - 1) / LBM, NT = (g.N + LBN - 1) / LBN;
     int tm, tn;
-    {
+    {                                                 // xcd_tile's order, written out: through the helper this kernel schedules differently
         const int xcd = blockIdx.x & 7, i = blockIdx.x >> 3;
         const int lx = MT > xcd ? (MT - xcd + 7) >> 3 : 0;
         if (i >= lx * NT) return;
@@ -1670,7 +1673,7 @@ __global__ __launch_bounds__(256, 5) void attention_mfma_short_kernel(const unsi
 //   * the (image, 16-query tile) units of the tile are dealt to the eight waves; each unit is the arithmetic of
 //     attention_mfma_short_kernel, operation for operation (S^T = K Q^T, base-2 softmax, P packed to bf16, O^T = V^T P^T), so
 //     the result is bit-identical to the unfused path; only att[rows, 64] is written.
-// Tile order as in the GEMMs: the 12 head workgroups of a row panel run on one XCD and share the panel through its L2.
+// Tile order as in the GEMMs (xcd_tile): the 12 head workgroups of a row panel run on one XCD and share the panel through its L2.
 // ---------------------------------------------------------------------------------------------
 struct QkvAttnArgs {
     const void *X = nullptr;      // LayerNorm output [rows, D] bf16
@@ -1683,358 +1686,33 @@ struct QkvAttnArgs {
 
 constexpr int QA_WBYTES = 192 * ROWB;                         // one W stage: q_h, k_h, v_h rows = 24 KiB
 constexpr int QA_LDS = 3 * LX_BYTES + 2 * QA_WBYTES;          // 144 KiB
+constexpr int QP_LDS = 160 * 1024;                            // persistent form
 constexpr int QA_REGION = 264 * ROWB;                         // Q / K / V image after the K loop: 256 rows + 8 zeroed pad rows
 
-template <typename TOut>
-__global__ __launch_bounds__(512, 2) void qkv_attn_kernel(QkvAttnArgs g) {
+// One body, two forms, which do the same arithmetic in the same order: their outputs are bit-identical to each other and to the
+// unfused path (tests/test_fused_qkv_attention_gpu.py runs both).
+//   * plain (qkv_attn_kernel, PERS = false): one workgroup per (row tile, head) item, 144 KiB of LDS (QA_LDS);
+//   * persistent (qkv_attn_pers_kernel, PERS = true, round 3): one workgroup per CU walks its items, and the NEXT item's stage 0
+//     is fetched by LDS-DMA during the attention phase of the current one: a tile's 4.2 k-cycle prologue (11 % of its 37.9 k
+//     cycles, stamps of round 2) becomes the landing time of stage 1 behind an already resident stage 0.  That needs a 160 KiB
+//     LDS layout (QP_LDS) in which stage 0 of the ring and the Q | K | V images are disjoint.
+// IVR_QKV_PERS=0 keeps the plain form at every size; the s_memtime stamps (-DIVR_GEMM_STAMPS) are the plain form's.
+template <typename TOut, bool PERS>
+__device__ __forceinline__ void qkv_attn_body(const QkvAttnArgs &g, unsigned char *smem) {
     typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
     typedef unsigned short T;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    IVR_STAMP(0)
+    if constexpr (!PERS) { IVR_STAMP(0) }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
     const int RT = g.G * g.T;                                  // rows per tile
     const int MT = (g.M + RT - 1) / RT, NT = g.heads;
-    int tm, h;
-    {
-        const int xcd = blockIdx.x & 7, i = blockIdx.x >> 3;
-        const int lx = MT > xcd ? (MT - xcd + 7) >> 3 : 0;
-        if (i >= lx * NT) return;
-        const int gm = g.group_m;
-        const int per = gm * NT, grp = i / per, within = i - grp * per;
-        const int gme = min(gm, lx - grp * gm);
-        tm = xcd + 8 * (grp * gm + within % gme);
-        h = within / gme;
-        if (g.reverse) tm = MT - 1 - tm;
-    }
-    const int m0 = tm * RT;
-    const int KT = g.D / 64;
-    const unsigned lds0 = (unsigned)(size_t)smem;
-
-    // DMA pieces of 1 KiB (8 rows x 128 B): 32 of X, 24 of W per stage; wave w issues X pieces 4w..4w+3 and W pieces 3w..3w+2.
-    // W piece p covers rows 8p..8p+7 of the 192-row head tile: third p >> 3 (q, k, v), rows h*64 + 8*(p & 7) of that third.
-    unsigned voffX[4], voffW;
-    {
-        const int c = (lane & 7) ^ (lane >> 3);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) voffX[j] = (unsigned)((8 * (wave * 4 + j) + (lane >> 3)) * g.D) * 2u + c * 16;
-        voffW = (unsigned)((lane >> 3) * g.D) * 2u + c * 16;
-    }
-    unsigned swW[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int p = wave * 3 + j;
-        swW[j] = (unsigned)(((p >> 3) * g.D + h * 64 + 8 * (p & 7)) * g.D) * 2u;
-    }
-    const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(g.X), 0, (int)((int64_t)g.M * g.D * 2), 0x00020000);
-    const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(g.W), 0, (int)((int64_t)3 * g.D * g.D * 2), 0x00020000);
-    const unsigned sx0 = (unsigned)m0 * (unsigned)g.D * 2u;
-    constexpr int WBASE = 3 * LX_BYTES;
-    auto piece = [&](int kt, int xs, int j) {          // j < 4: X piece (slot xs); 4..6: W piece (slot kt & 1)
-        const unsigned adv = (unsigned)kt * ROWB;
-        if (j < 4)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (__attribute__((address_space(3))) void *)(smem + xs * LX_BYTES + (wave * 4 + j) * 1024),
-                                                     16, voffX[j], sx0 + adv, 0, 0);
-        else
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                rsW, (__attribute__((address_space(3))) void *)(smem + WBASE + (kt & 1) * QA_WBYTES + (wave * 3 + j - 4) * 1024), 16, voffW,
-                swW[j - 4] + adv, 0, 0);
-    };
-    unsigned foX[2], foW[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        const unsigned f = (lane & 15) * ROWB + ((((kk << 2) + (lane >> 4)) ^ (lane & 7)) << 4);
-        foX[kk] = lds0 + (wm * 128) * ROWB + f;
-        foW[kk] = lds0 + WBASE + (wn * 48) * ROWB + f;
-    }
-
-    f32x4 acc[3][8];   // [nt][mt]
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // the bias of the wave's three column tiles, fetched now so that its latency is long gone when the epilogue needs it
-    float4 bq[3];
-#pragma unroll
-    for (int nt = 0; nt < 3; ++nt) {
-        const int col = wn * 48 + nt * 16 + 4 * (lane >> 4);
-        bq[nt] = *reinterpret_cast<const float4 *>(g.bias + (col >> 6) * g.D + h * 64 + (col & 63));
-    }
-
-#define QA_ROW(XF, WF, MTI)                                                                                \
-    _Pragma("unroll") for (int nt = 0; nt < 3; ++nt) mma_chunk<T>(WF[nt], XF[MTI], acc[nt][MTI]);          \
-    __builtin_amdgcn_sched_barrier(0);
-#define QA_RD4(DST, ADDR, O0)                                                                              \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[0]) : "v"(ADDR), "n"(O0));                      \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[1]) : "v"(ADDR), "n"(O0 + 2048));               \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[2]) : "v"(ADDR), "n"(O0 + 4096));               \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[3]) : "v"(ADDR), "n"(O0 + 6144));
-#define QA_RD3(DST, ADDR)                                                                                  \
-    asm volatile("ds_read_b128 %0, %1" : "=v"(DST[0]) : "v"(ADDR));                                         \
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(DST[1]) : "v"(ADDR));                             \
-    asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(DST[2]) : "v"(ADDR));
-#define QA_LGKM(N)                                                                                         \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory");                                                \
-    __builtin_amdgcn_sched_barrier(0);
-
-    u32x4 xa0[8], wa0[3], xa1[8], wa1[3];
-    u32x4 *x0lo = xa0, *x0hi = xa0 + 4, *x1lo = xa1, *x1hi = xa1 + 4;
-    // prologue (KT >= 3 is checked by the launcher): stage 0, stage 1, X(2), in the order the counted waits rely on
-#pragma unroll
-    for (int j = 0; j < 7; ++j) piece(0, 0, j);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) piece(1, 1, j);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) piece(2, 2, j);
-    asm volatile("s_waitcnt vmcnt(11)\n\ts_barrier" ::: "memory");
-    IVR_STAMP(1)
-    QA_RD3(wa0, foW[0])
-    QA_RD4(x0lo, foX[0], 0)
-    QA_RD4(x0hi, foX[0], 8192)
-    int xs = 0;
-    for (int kt = 0; kt < KT; ++kt) {
-        const int xs1 = xs == 2 ? 0 : xs + 1;
-        const unsigned xoff = xs * LX_BYTES, woff = (kt & 1) * QA_WBYTES, nxoff = xs1 * LX_BYTES, nwoff = ((kt + 1) & 1) * QA_WBYTES;
-        const bool tail = kt >= 1 && kt + 2 < KT;
-        const bool morew = kt + 2 < KT, morex = kt + 3 < KT, next = kt + 1 < KT;
-        const unsigned wa = foW[1] + woff, xa = foX[1] + xoff, nwa = foW[0] + nwoff, nxa = foX[0] + nxoff;
-        QA_LGKM(4)                      // W + first four X fragments of set 0
-        QA_ROW(xa0, wa0, 0)
-        if (tail) piece(kt + 2, xs1 == 2 ? 0 : xs1 + 1, 2);
-        QA_ROW(xa0, wa0, 1)
-        QA_RD3(wa1, wa)
-        QA_ROW(xa0, wa0, 2)
-        if (tail) piece(kt + 2, xs1 == 2 ? 0 : xs1 + 1, 3);
-        QA_ROW(xa0, wa0, 3)
-        QA_RD4(x1lo, xa, 0)
-        QA_LGKM(7)                      // all of set 0
-        QA_ROW(xa0, wa0, 4)
-        QA_ROW(xa0, wa0, 5)
-        QA_RD4(x1hi, xa, 8192)
-        QA_ROW(xa0, wa0, 6)
-        QA_ROW(xa0, wa0, 7)
-        QA_LGKM(0)
-        if (next) {
-            if (kt + 2 < KT) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-        QA_ROW(xa1, wa1, 0)
-        if (morew) piece(kt + 2, 0, 4);
-        QA_ROW(xa1, wa1, 1)
-        if (next) { QA_RD3(wa0, nwa) }
-        if (morew) piece(kt + 2, 0, 5);
-        QA_ROW(xa1, wa1, 2)
-        if (morew) piece(kt + 2, 0, 6);
-        QA_ROW(xa1, wa1, 3)
-        if (next) { QA_RD4(x0lo, nxa, 0) }
-        QA_ROW(xa1, wa1, 4)
-        if (morex) piece(kt + 3, xs, 0);
-        QA_ROW(xa1, wa1, 5)
-        if (next) { QA_RD4(x0hi, nxa, 8192) }
-        QA_ROW(xa1, wa1, 6)
-        if (morex) piece(kt + 3, xs, 1);
-        QA_ROW(xa1, wa1, 7)
-        xs = xs1;
-    }
-    QA_LGKM(0)
-#undef QA_ROW
-#undef QA_RD4
-#undef QA_RD3
-#undef QA_LGKM
-    IVR_STAMP(2)
-    __builtin_amdgcn_s_barrier();                             // every wave has read its last fragments: the LDS is free
-
-    // ---- accumulators + bias -> bf16 Q | K | V images in LDS
-    unsigned char *const qreg = smem, *const kreg = smem + QA_REGION, *const vreg = smem + 2 * QA_REGION;
-    {
-        const int r = lane & 15, gq = lane >> 4;
-#pragma unroll
-        for (int nt = 0; nt < 3; ++nt) {
-            const int col = wn * 48 + nt * 16 + 4 * gq;       // 0..191: region col >> 6, head dim col & 63
-            const int reg3 = col >> 6, dh = col & 63, ch = dh >> 3;
-            const float4 bv = bq[nt];
-            unsigned char *base = smem + reg3 * QA_REGION + (dh & 7) * 2;
-#pragma unroll
-            for (int mt = 0; mt < 8; ++mt) {
-                const int m = wm * 128 + mt * 16 + r;
-                const f32x4 a = acc[nt][mt];
-                uint2 o;
-                o.x = ivr_pack_bf16x2(a[0] + bv.x, a[1] + bv.y);
-                o.y = ivr_pack_bf16x2(a[2] + bv.z, a[3] + bv.w);
-                const unsigned pos = reg3 == 2 ? (unsigned)((((ch >> 1) ^ ((m >> 1) & 3)) << 5) | ((ch & 1) << 4))
-                                               : (unsigned)((ch ^ (m & 7)) << 4);
-                *reinterpret_cast<uint2 *>(base + m * ROWB + pos) = o;
-            }
-        }
-        // rows 256..263 behind the K and V images: key blocks of the tile's last image may reach them (masked scores, P = 0)
-        if (tid < 128) *reinterpret_cast<uint4 *>((tid < 64 ? kreg : vreg) + 256 * ROWB + (tid & 63) * 16) = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __syncthreads();
-#ifdef IVR_GEMM_STAMPS
-    if (threadIdx.x == 0 && blockIdx.x < 16384) ivr_gemm_stamps[blockIdx.x][6] = __builtin_amdgcn_s_memtime();
-#endif
-
-    // ---- attention: units (image, 16-query tile) dealt round-robin to the waves
-    // (pooled: only the unit that holds query 0 of each image, G units per tile instead of G * nqt)
-    const int Tn = g.T, nqt = g.pooled ? 1 : (Tn + 15) >> 4, units = g.G * nqt;
-    const int gl = lane >> 4, c = lane & 15;
-    constexpr float L2E = 1.4426950408889634f;
-    for (int u = wave; u < units; u += 8) {
-        const int img = u / nqt, qt = u - img * nqt;
-        const int R0 = img * Tn;                                // first tile row of the image
-        if (m0 + R0 >= g.M) continue;                           // image past the end of the batch (last panel)
-        const int q = qt * 16 + c;
-        // All LDS reads of the unit go out together - Q fragments (B operand of S^T: row R0 + q, chunks 4 ks + gl), K fragments
-        // (A operand: rows R0 + 16 kt + c) and the sixteen transposed V^T pieces, which do not depend on the softmax - and are
-        // waited for once: issued one dependent group at a time the unit was a chain of ten LDS round trips.
-        uint4 qf[2], kf[2][4];
-        uint2 vt[4][4];                                         // [dh tile nt][16-key block]
-        {
-            const int rq = R0 + q;
-            const unsigned qa = (unsigned)(size_t)qreg + rq * ROWB, qx = rq & 7;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) asm volatile("ds_read_b128 %0, %1" : "=v"(qf[ks]) : "v"(qa + (((4 * ks + gl) ^ qx) << 4)));
-            // the four key tiles are 16 rows = 2048 bytes apart and share (row & 7)
-            const int rk = R0 + c;
-            const unsigned ka = (unsigned)(size_t)kreg + rk * ROWB, kx = rk & 7;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const unsigned a0 = ka + (((4 * ks + gl) ^ kx) << 4);
-                asm volatile("ds_read_b128 %0, %1" : "=v"(kf[ks][0]) : "v"(a0));
-                asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(kf[ks][1]) : "v"(a0));
-                asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(kf[ks][2]) : "v"(a0));
-                asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(kf[ks][3]) : "v"(a0));
-            }
-            // V^T: this lane addresses key row 4 gl + (c >> 2) of a 16-key block, 8 bytes (c & 3) of the 32-byte segment nt
-            const int vrow = R0 + 4 * gl + (c >> 2);
-            const unsigned vbase = (unsigned)(size_t)vreg + (unsigned)vrow * ROWB + (c & 3) * 8;
-            const int xr = (vrow >> 1) & 3;                      // key blocks start 16 rows apart: (row >> 1) & 3 is the same in all four
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                const unsigned va = vbase + ((nt ^ xr) << 5);
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(vt[nt][0]) : "v"(va));
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "=v"(vt[nt][1]) : "v"(va));
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:4096" : "=v"(vt[nt][2]) : "v"(va));
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:6144" : "=v"(vt[nt][3]) : "v"(va));
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            // Key blocks of the tile's LAST images can reach past the 8 zeroed pad rows (T = 10: row 303, T = 26: 271) into the
-            // next region or stale staging bytes.  Their scores are masked below (P = 0), but 0 x Inf/NaN is NaN inside the MFMA:
-            // select zeros into the V elements of keys >= T whenever the shape can reach past row 263 (wave-uniform; never for
-            // T = 50, where (G-1) T + 63 = 263).  Element r of vt[nt][kb] is key 16 kb + 4 gl + r.
-            if ((g.G - 1) * Tn + 63 > 263) {
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    if (kb * 16 + 15 < Tn) continue;
-                    const int k0 = kb * 16 + gl * 4;
-                    const unsigned mlo = (k0 < Tn ? 0x0000ffffu : 0u) | (k0 + 1 < Tn ? 0xffff0000u : 0u);
-                    const unsigned mhi = (k0 + 2 < Tn ? 0x0000ffffu : 0u) | (k0 + 3 < Tn ? 0xffff0000u : 0u);
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) {
-                        vt[nt][kb].x &= mlo;
-                        vt[nt][kb].y &= mhi;
-                    }
-                }
-            }
-        }
-        f32x4 sc[4];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-            f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kf[0][kt]), __builtin_bit_cast(bf16x8_t, qf[0]), a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kf[1][kt]), __builtin_bit_cast(bf16x8_t, qf[1]), a, 0, 0, 0);
-            if (kt * 16 + 15 >= Tn) {             // wave-uniform: only a tile that reaches past the sequence needs the mask
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (kt * 16 + gl * 4 + r >= Tn) a[r] = -INFINITY;
-            }
-            mx = vmax3(mx, a[0], a[1]);
-            mx = vmax3(mx, a[2], a[3]);
-            sc[kt] = a;
-        }
-        mx = quad_max(mx);                    // finite: key 0 is visible to every query
-        const float mb = -mx * L2E;
-        float sum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float pv = __builtin_amdgcn_exp2f(fmaf(sc[kt][r], L2E, mb));      // masked (-inf) -> 0
-                sc[kt][r] = pv;
-                sum += pv;
-            }
-        sum = quad_sum(sum);
-        uint4 pf[2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            pf[ks].x = ivr_pack_bf16x2(sc[2 * ks][0], sc[2 * ks][1]);
-            pf[ks].y = ivr_pack_bf16x2(sc[2 * ks][2], sc[2 * ks][3]);
-            pf[ks].z = ivr_pack_bf16x2(sc[2 * ks + 1][0], sc[2 * ks + 1][1]);
-            pf[ks].w = ivr_pack_bf16x2(sc[2 * ks + 1][2], sc[2 * ks + 1][3]);
-        }
-        const float inv = __builtin_amdgcn_rcpf(sum);
-        const int64_t grow = (int64_t)m0 + R0 + q;
-        const int64_t orow = g.pooled ? (int64_t)(m0 / Tn) + img : grow;      // pooled: compact row of the image
-        TOut *op = reinterpret_cast<TOut *>(g.att) + orow * g.D + h * 64 + gl * 4;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            f32x4 o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const uint4 vf = make_uint4(vt[nt][2 * ks].x, vt[nt][2 * ks].y, vt[nt][2 * ks + 1].x, vt[nt][2 * ks + 1].y);
-                o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf), __builtin_bit_cast(bf16x8_t, pf[ks]), o, 0, 0, 0);
-            }
-            if ((g.pooled ? q == 0 : q < Tn) && grow < g.M) {
-                const float v[4] = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
-                El<TOut>::store4(op + nt * 16, v);
-            }
-        }
-    }
-#ifdef IVR_GEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                                            // the slowest wave of the workgroup
-    IVR_STAMP(3)
-#endif
-}
-
-// ---------------------------------------------------------------------------------------------
-// Persistent form of qkv_attn_kernel (round 3): one workgroup per CU walks its (row tile, head) items; the LDS is laid out so that
-// stage 0 of the K-loop ring (bottom 56 KiB) and the Q | K | V images (top 99 KiB) are disjoint, and the NEXT item's stage 0 is
-// fetched by LDS-DMA during the attention phase of the current one: a tile's 4.2 k-cycle prologue (11 % of its 37.9 k cycles, stamps
-// of round 2) becomes the landing time of stage 1 behind an already resident stage 0.  Everything else - K loop, accumulators ->
-// images, attention - is qkv_attn_kernel's code operation for operation, so the output is bit-identical to it (and to the unfused
-// path): tests/test_fused_qkv_attention_gpu.py runs both.  IVR_QKV_PERS=0 keeps the one-tile-per-workgroup kernel.
-// ---------------------------------------------------------------------------------------------
-constexpr int QP_LDS = 160 * 1024;
-
-template <typename TOut>
-__global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
-    typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-    typedef unsigned short T;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int RT = g.G * g.T;                                  // rows per tile
-    const int MT = (g.M + RT - 1) / RT, NT = g.heads;
-    // persistent: one workgroup per CU walks items slot, slot + nslots, ... of its XCD's tile list (the order of qkv_attn_kernel)
+    // the workgroup's items are numbers slot, slot + nslots, ... of its XCD's tile list; the plain form has one
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-    const int lx = MT > xcd ? (MT - xcd + 7) >> 3 : 0;
-    const int nitems = lx * NT;
+    const int nitems = xcd_panels(MT, xcd) * NT;
     if (slot >= nitems) return;
-    const int count = (nitems - slot + nslots - 1) / nslots;
-    auto locate = [&](int n, int &tm_, int &h_) {
-        const int i = slot + n * nslots;
-        const int gm = g.group_m;
-        const int per = gm * NT, grp = i / per, within = i - grp * per;
-        const int gme = min(gm, lx - grp * gm);
-        tm_ = xcd + 8 * (grp * gm + within % gme);
-        h_ = within / gme;
-        if (g.reverse) tm_ = MT - 1 - tm_;
-    };
+    const int count = PERS ? (nitems - slot + nslots - 1) / nslots : 1;
+    auto locate = [&](int n, int &tm_, int &h_) { xcd_tile(slot + n * nslots, xcd, MT, NT, g.group_m, g.reverse, tm_, h_); };
     const int KT = g.D / 64;
     const unsigned lds0 = (unsigned)(size_t)smem;
 
@@ -2058,11 +1736,12 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
     };
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(g.X), 0, (int)((int64_t)g.M * g.D * 2), 0x00020000);
     const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(g.W), 0, (int)((int64_t)3 * g.D * g.D * 2), 0x00020000);
-    // LDS (160 KiB), laid out so that stage 0 of the ring (X slot 0 + W slot 0 = the bottom 56 KiB) is disjoint from the Q | K | V
-    // images (the top 99 KiB): the NEXT item's stage 0 is fetched while the attention phase of the current one reads the images.
-    auto xbase = [](int xs) { return xs == 0 ? 0 : xs == 1 ? 57344 : 90112; };         // X slots: 0, 56 K, 88 K (32 KiB each)
-    auto wbase = [](int b) { return b ? 122880 : 32768; };                              // W slots: 32 K, 120 K (24 KiB each)
-    constexpr int IMG = 62464;                                                           // images: 61 K .. 160 K
+    // LDS.  Plain: three X slots of 32 KiB, then two W slots of 24 KiB; the Q | K | V images start at 0 once the K loop is done.
+    // Persistent: stage 0 of the ring (X slot 0 + W slot 0 = the bottom 56 KiB) is disjoint from the images (the top 99 KiB).
+    auto xbase = [](int xs) { return PERS ? (xs == 0 ? 0 : xs == 1 ? 57344 : 90112) : xs * LX_BYTES; };   // pers: 0, 56 K, 88 K
+    auto wbase = [](int b) { return PERS ? (b ? 122880 : 32768) : 3 * LX_BYTES + b * QA_WBYTES; };          // pers: 32 K, 120 K
+    constexpr int IMG = PERS ? 62464 : 0;                                                                   // pers: 61 K .. 160 K
+    static_assert(IMG + 3 * QA_REGION <= (PERS ? QP_LDS : QA_LDS), "Q | K | V images past the end of the LDS");
     auto piece = [&](unsigned sx, const unsigned (&sw)[3], int kt, int xs, int j) {      // j < 4: X piece (slot xs); 4..6: W piece (slot kt & 1)
         const unsigned adv = (unsigned)kt * ROWB;
         if (j < 4)
@@ -2087,22 +1766,15 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
 #define QA_ROW(XF, WF, MTI)                                                                                \
     _Pragma("unroll") for (int nt = 0; nt < 3; ++nt) mma_chunk<T>(WF[nt], XF[MTI], acc[nt][MTI]);          \
     __builtin_amdgcn_sched_barrier(0);
-#define QA_RD4(DST, ADDR, O0)                                                                              \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[0]) : "v"(ADDR), "n"(O0));                      \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[1]) : "v"(ADDR), "n"(O0 + 2048));               \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[2]) : "v"(ADDR), "n"(O0 + 4096));               \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[3]) : "v"(ADDR), "n"(O0 + 6144));
 #define QA_RD3(DST, ADDR)                                                                                  \
     asm volatile("ds_read_b128 %0, %1" : "=v"(DST[0]) : "v"(ADDR));                                         \
     asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(DST[1]) : "v"(ADDR));                             \
     asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(DST[2]) : "v"(ADDR));
-#define QA_LGKM(N)                                                                                         \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory");                                                \
-    __builtin_amdgcn_sched_barrier(0);
 
     u32x4 xa0[8], wa0[3], xa1[8], wa1[3];
     u32x4 *x0lo = xa0, *x0hi = xa0 + 4, *x1lo = xa1, *x1hi = xa1 + 4;
-    // stage 0 of the first item; every later item finds its stage 0 fetched during the previous item's attention phase
+    // prologue (KT >= 3 is checked by the launcher): stage 0, then per item the bias, stage 1 and X(2); a later item of the
+    // persistent form finds its stage 0 fetched during the previous item's attention phase
 #pragma unroll
     for (int j = 0; j < 7; ++j) piece(sx0, swW, 0, 0, j);
   for (int n = 0; n < count; ++n) {
@@ -2112,6 +1784,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // the bias of the wave's three column tiles, fetched now so that its latency is long gone when the epilogue needs it
     float4 bq[3];
 #pragma unroll
     for (int nt = 0; nt < 3; ++nt) {
@@ -2125,9 +1798,10 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) piece(sx0, swW, 2, 2, j);
     asm volatile("s_waitcnt vmcnt(11)\n\ts_barrier" ::: "memory");
+    if constexpr (!PERS) { IVR_STAMP(1) }
     QA_RD3(wa0, foW[0] + wbase(0))
-    QA_RD4(x0lo, foX[0] + xbase(0), 0)
-    QA_RD4(x0hi, foX[0] + xbase(0), 8192)
+    IVR_RD4(x0lo, foX[0] + xbase(0), 0)
+    IVR_RD4(x0hi, foX[0] + xbase(0), 8192)
     int xs = 0;
     for (int kt = 0; kt < KT; ++kt) {
         const int xs1 = xs == 2 ? 0 : xs + 1;
@@ -2135,7 +1809,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
         const bool tail = kt >= 1 && kt + 2 < KT;
         const bool morew = kt + 2 < KT, morex = kt + 3 < KT, next = kt + 1 < KT;
         const unsigned wa = foW[1] + woff, xa = foX[1] + xoff, nwa = foW[0] + nwoff, nxa = foX[0] + nxoff;
-        QA_LGKM(4)                      // W + first four X fragments of set 0
+        IVR_LGKM(4)                     // W + first four X fragments of set 0
         QA_ROW(xa0, wa0, 0)
         if (tail) piece(sx0, swW, kt + 2, xs1 == 2 ? 0 : xs1 + 1, 2);
         QA_ROW(xa0, wa0, 1)
@@ -2143,14 +1817,14 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
         QA_ROW(xa0, wa0, 2)
         if (tail) piece(sx0, swW, kt + 2, xs1 == 2 ? 0 : xs1 + 1, 3);
         QA_ROW(xa0, wa0, 3)
-        QA_RD4(x1lo, xa, 0)
-        QA_LGKM(7)                      // all of set 0
+        IVR_RD4(x1lo, xa, 0)
+        IVR_LGKM(7)                     // all of set 0
         QA_ROW(xa0, wa0, 4)
         QA_ROW(xa0, wa0, 5)
-        QA_RD4(x1hi, xa, 8192)
+        IVR_RD4(x1hi, xa, 8192)
         QA_ROW(xa0, wa0, 6)
         QA_ROW(xa0, wa0, 7)
-        QA_LGKM(0)
+        IVR_LGKM(0)
         if (next) {
             if (kt + 2 < KT) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
@@ -2163,21 +1837,20 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
         QA_ROW(xa1, wa1, 2)
         if (morew) piece(sx0, swW, kt + 2, 0, 6);
         QA_ROW(xa1, wa1, 3)
-        if (next) { QA_RD4(x0lo, nxa, 0) }
+        if (next) { IVR_RD4(x0lo, nxa, 0) }
         QA_ROW(xa1, wa1, 4)
         if (morex) piece(sx0, swW, kt + 3, xs, 0);
         QA_ROW(xa1, wa1, 5)
-        if (next) { QA_RD4(x0hi, nxa, 8192) }
+        if (next) { IVR_RD4(x0hi, nxa, 8192) }
         QA_ROW(xa1, wa1, 6)
         if (morex) piece(sx0, swW, kt + 3, xs, 1);
         QA_ROW(xa1, wa1, 7)
         xs = xs1;
     }
-    QA_LGKM(0)
+    IVR_LGKM(0)
 #undef QA_ROW
-#undef QA_RD4
 #undef QA_RD3
-#undef QA_LGKM
+    if constexpr (!PERS) { IVR_STAMP(2) }
     __builtin_amdgcn_s_barrier();                             // every wave has read its last fragments: the LDS is free
 
     // ---- accumulators + bias -> bf16 Q | K | V images in LDS
@@ -2206,6 +1879,9 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
         if (tid < 128) *reinterpret_cast<uint4 *>((tid < 64 ? kreg : vreg) + 256 * ROWB + (tid & 63) * 16) = make_uint4(0u, 0u, 0u, 0u);
     }
     __syncthreads();
+#ifdef IVR_GEMM_STAMPS
+    if (!PERS && threadIdx.x == 0 && blockIdx.x < 16384) ivr_gemm_stamps[blockIdx.x][6] = __builtin_amdgcn_s_memtime();
+#endif
     // the next item's stage 0 goes into the bottom 56 KiB (nobody reads the ring any more) while the attention below reads the images
     const int h_cur = h;
     if (n + 1 < count) {
@@ -2335,8 +2011,26 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
     }
     if (n + 1 < count) __syncthreads();                         // every wave is done with the images: the ring may take stage 1 and X(2)
   }
+#ifdef IVR_GEMM_STAMPS
+    if constexpr (!PERS) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                        // the slowest wave of the workgroup
+        IVR_STAMP(3)
+    }
+#endif
 }
 
+template <typename TOut>
+__global__ __launch_bounds__(512, 2) void qkv_attn_kernel(QkvAttnArgs g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    qkv_attn_body<TOut, false>(g, smem);
+}
+
+template <typename TOut>
+__global__ __launch_bounds__(512, 2) void qkv_attn_pers_kernel(QkvAttnArgs g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    qkv_attn_body<TOut, true>(g, smem);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Persistent form of the 256 x 256 bf16 GEMM (round 3).  s_memtime stamps of gemm_big_kernel (tools/exp_epilogue_contention.py,
@@ -2379,7 +2073,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmArgs g) {
     const int S = count * KT;
     const unsigned lds0 = (unsigned)(size_t)smem;
     const int gm = g.group_m;
-    // item n of this workgroup = number slot + n * nslots of the XCD's tile list
+    // item n of this workgroup = number slot + n * nslots of the XCD's tile list (xcd_tile's order in unsigned arithmetic: through the
+    // signed helper this kernel compiles to different code)
     auto locate = [&](int n, int &tm, int &tn) {
         const unsigned i = (unsigned)(slot + n * nslots);
         const unsigned per = (unsigned)(gm * NT), grp = i / per, within = i - grp * per;
@@ -2449,14 +2144,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmArgs g) {
     _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) acc[nt][MT_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                 \
         __builtin_bit_cast(bf16x8_t, WF[nt]), __builtin_bit_cast(bf16x8_t, XF[MT_]), FIRST ? zero : acc[nt][MT_], 0, 0, 0);  \
     __builtin_amdgcn_sched_barrier(0);
-#define GP_RD4(DST, ADDR, O0)                                                                              \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[0]) : "v"(ADDR), "n"(O0));                      \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[1]) : "v"(ADDR), "n"(O0 + 2048));               \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[2]) : "v"(ADDR), "n"(O0 + 4096));               \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST[3]) : "v"(ADDR), "n"(O0 + 6144));
-#define GP_LGKM(N)                                                                                         \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory");                                                \
-    __builtin_amdgcn_sched_barrier(0);
 
     u32x4 xa0[8], wa0[4], xa1[8], wa1[4];
     u32x4 *x0lo = xa0, *x0hi = xa0 + 4, *x1lo = xa1, *x1hi = xa1 + 4;
@@ -2483,9 +2170,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmArgs g) {
     if (S > 2) asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");
     else if (S > 1) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    GP_RD4(wa0, foW0, 0)
-    GP_RD4(x0lo, foX0, 0)
-    GP_RD4(x0hi, foX0, 8192)
+    IVR_RD4(wa0, foW0, 0)
+    IVR_RD4(x0lo, foX0, 0)
+    IVR_RD4(x0hi, foX0, 8192)
 
     int xs = 0, cn = 0, ckt = 0;
     for (int s = 0; s < S; ++s) {
@@ -2496,19 +2183,19 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmArgs g) {
         const bool last = ckt == KT - 1;              // the item's last stage: its epilogue follows
         const unsigned wa = (foW0 ^ 64u) + woff, xa = (foX0 ^ 64u) + xoff, nwa = foW0 + nwoff, nxa = foX0 + nxoff;
 #define GP_SET0(FIRST)                                                                                     \
-        GP_LGKM(4)                                                                                         \
+        IVR_LGKM(4)                                                                                        \
         GP_ROW(xa0, wa0, 0, FIRST)                                                                         \
         if (tail) pieceX(xs2, 2);                                                                          \
         GP_ROW(xa0, wa0, 1, FIRST)                                                                         \
-        GP_RD4(wa1, wa, 0)                                                                                 \
+        IVR_RD4(wa1, wa, 0)                                                                                \
         GP_ROW(xa0, wa0, 2, FIRST)                                                                         \
         if (tail) pieceX(xs2, 3);                                                                          \
         GP_ROW(xa0, wa0, 3, FIRST)                                                                         \
-        GP_RD4(x1lo, xa, 0)                                                                                \
-        GP_LGKM(8)                                                                                         \
+        IVR_RD4(x1lo, xa, 0)                                                                               \
+        IVR_LGKM(8)                                                                                        \
         GP_ROW(xa0, wa0, 4, FIRST)                                                                         \
         GP_ROW(xa0, wa0, 5, FIRST)                                                                         \
-        GP_RD4(x1hi, xa, 8192)                                                                             \
+        IVR_RD4(x1hi, xa, 8192)                                                                            \
         GP_ROW(xa0, wa0, 6, FIRST)                                                                         \
         GP_ROW(xa0, wa0, 7, FIRST)
         if (ckt == 0) {
@@ -2517,7 +2204,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmArgs g) {
             GP_SET0(false)
         }
 #undef GP_SET0
-        GP_LGKM(0)
+        IVR_LGKM(0)
         if (s >= 1) advanceX();
         if (next) {
             // (an epilogue's global stores count in vmcnt too; they can only lengthen this wait, never release it early: scanq_kernel)
@@ -2527,17 +2214,17 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmArgs g) {
         GP_ROW(xa1, wa1, 0, false)
         if (morew) pieceW(s & 1, 0);
         GP_ROW(xa1, wa1, 1, false)
-        if (next) { GP_RD4(wa0, nwa, 0) }
+        if (next) { IVR_RD4(wa0, nwa, 0) }
         if (morew) pieceW(s & 1, 1);
         GP_ROW(xa1, wa1, 2, false)
         if (morew) pieceW(s & 1, 2);
         GP_ROW(xa1, wa1, 3, false)
-        if (next) { GP_RD4(x0lo, nxa, 0) }
+        if (next) { IVR_RD4(x0lo, nxa, 0) }
         if (morew) pieceW(s & 1, 3);
         GP_ROW(xa1, wa1, 4, false)
         if (morex) pieceX(xs, 0);
         GP_ROW(xa1, wa1, 5, false)
-        if (next) { GP_RD4(x0hi, nxa, 8192) }
+        if (next) { IVR_RD4(x0hi, nxa, 8192) }
         GP_ROW(xa1, wa1, 6, false)
         if (morex) pieceX(xs, 1);
         GP_ROW(xa1, wa1, 7, false)
@@ -2615,10 +2302,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmArgs g) {
             }
         }
     }
-    GP_LGKM(0)
+    IVR_LGKM(0)
 #undef GP_ROW
-#undef GP_RD4
-#undef GP_LGKM
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2750,6 +2435,9 @@ static int device_cu_count() {
     return c;
 }
 
+// grid of the XCD-grouped tile order (xcd_tile): every XCD gets the same number of ids; surplus ones exit
+static int xcd_grid(int MT, int NT) { return 8 * ((MT + 7) / 8) * NT; }
+
 template <typename T, int EPI, int ACT>
 int launch_gemm_t(const GemmArgs &g, hipStream_t s) {
     IvrProf prof(g.tag ? g.tag : "gemm", s, 2.0 * g.M * g.N * g.K);
@@ -2790,7 +2478,7 @@ int launch_gemm_t(const GemmArgs &g, hipStream_t s) {
             ga.wide_epi = wide_env && bias_ok && g.N % 64 == 0 && g.ldo % 8 == 0 && reinterpret_cast<uintptr_t>(g.out) % 16 == 0;
         else if (EPI == EPI_RESID)
             ga.wide_epi = wide_env && bias_ok && g.N % 64 == 0 && g.ldr % 4 == 0 && reinterpret_cast<uintptr_t>(g.resid) % 16 == 0;
-        const int grid = 8 * ((MT + 7) / 8) * NT;
+        const int grid = xcd_grid(MT, NT);
         // persistent form (gemm_pers_kernel): bf16 store / residual epilogues under the row-wide epilogue's alignment conditions,
         // problems of at least two tiles per CU.  IVR_GEMM_PERS=0 keeps the one-tile-per-workgroup kernel (A/B runs, parity tests).
         const int pers = env_int("IVR_GEMM_PERS", 1);          // 2: wherever the shape allows (tests), whatever the size
@@ -2820,7 +2508,7 @@ int launch_gemm_t(const GemmArgs &g, hipStream_t s) {
     const int MT = (g.M + BM - 1) / BM, NT = (g.N + BN - 1) / BN;
     if (int rc = ivr_func_max_lds(reinterpret_cast<const void *>(gemm_kernel<T, EPI, ACT>), GEMM_LDS)) return rc;
     ga.group_m = group_env ? group_env : 8;
-    const int grid = 8 * ((MT + 7) / 8) * NT;               // every XCD gets the same number of ids; surplus ones exit
+    const int grid = xcd_grid(MT, NT);
     hipLaunchKernelGGL((gemm_kernel<T, EPI, ACT>), dim3(grid), dim3(256), GEMM_LDS, s, ga);
     IVR_LAUNCH_CHECK();
     return IVR_OK;
@@ -2905,9 +2593,9 @@ int launch_gemm8_t(const GemmArgs &g, hipStream_t s) {
     if (EPI == EPI_RESID && g.skip_mod) {
         constexpr bool kSkip = EPI == EPI_RESID;
         if (int rc = ivr_func_max_lds(reinterpret_cast<const void *>(gemm_big8_kernel<EPI, ACT, OUT8, kSkip>), DEEP_LDS)) return rc;
-        hipLaunchKernelGGL((gemm_big8_kernel<EPI, ACT, OUT8, kSkip>), dim3(8 * ((MT + 7) / 8) * NT), dim3(512), DEEP_LDS, s, ga);
+        hipLaunchKernelGGL((gemm_big8_kernel<EPI, ACT, OUT8, kSkip>), dim3(xcd_grid(MT, NT)), dim3(512), DEEP_LDS, s, ga);
     } else {
-        hipLaunchKernelGGL((gemm_big8_kernel<EPI, ACT, OUT8>), dim3(8 * ((MT + 7) / 8) * NT), dim3(512), DEEP_LDS, s, ga);
+        hipLaunchKernelGGL((gemm_big8_kernel<EPI, ACT, OUT8>), dim3(xcd_grid(MT, NT)), dim3(512), DEEP_LDS, s, ga);
     }
     IVR_LAUNCH_CHECK();
     return IVR_OK;
@@ -2981,29 +2669,15 @@ int ivr_launch_qkv_attention(const void *xn, const void *w, const float *bias, v
     g.reverse = reverse;
     g.pooled = pooled != 0;
     const int RT = g.G * T, MT = (M + RT - 1) / RT;
-    const int grid = 8 * ((MT + 7) / 8) * heads;
     // FLOP: the projection (2 M 3D D) and the attention products (4 T^2 64 per image and head; pooled: one 16-query unit of T keys)
     IvrProf prof("gemm_qkv_attention", s, 2.0 * M * 3.0 * D * D + 4.0 * n * heads * (double)(pooled ? std::min(T, 16) : T) * T * 64);
     const int qpers = env_int("IVR_QKV_PERS", 1);           // 0: never, 2: always (tests), default: from two tiles per CU on
-    if (qpers == 2 || (qpers == 1 && (int64_t)MT * heads >= 2 * device_cu_count())) {
-        const int pgrid = device_cu_count() / 8 * 8;
-        if (out_fp8) {
-            if (int rc = ivr_func_max_lds(reinterpret_cast<const void *>(qkv_attn_pers_kernel<unsigned char>), QP_LDS)) return rc;
-            hipLaunchKernelGGL(qkv_attn_pers_kernel<unsigned char>, dim3(pgrid), dim3(512), QP_LDS, s, g);
-        } else {
-            if (int rc = ivr_func_max_lds(reinterpret_cast<const void *>(qkv_attn_pers_kernel<unsigned short>), QP_LDS)) return rc;
-            hipLaunchKernelGGL(qkv_attn_pers_kernel<unsigned short>, dim3(pgrid), dim3(512), QP_LDS, s, g);
-        }
-        IVR_LAUNCH_CHECK();
-        return IVR_OK;
-    }
-    if (out_fp8) {
-        if (int rc = ivr_func_max_lds(reinterpret_cast<const void *>(qkv_attn_kernel<unsigned char>), QA_LDS)) return rc;
-        hipLaunchKernelGGL(qkv_attn_kernel<unsigned char>, dim3(grid), dim3(512), QA_LDS, s, g);
-    } else {
-        if (int rc = ivr_func_max_lds(reinterpret_cast<const void *>(qkv_attn_kernel<unsigned short>), QA_LDS)) return rc;
-        hipLaunchKernelGGL(qkv_attn_kernel<unsigned short>, dim3(grid), dim3(512), QA_LDS, s, g);
-    }
+    const bool pers = qpers == 2 || (qpers == 1 && (int64_t)MT * heads >= 2 * device_cu_count());
+    void (*kern)(QkvAttnArgs) = pers ? (out_fp8 ? qkv_attn_pers_kernel<unsigned char> : qkv_attn_pers_kernel<unsigned short>)
+                                     : (out_fp8 ? qkv_attn_kernel<unsigned char> : qkv_attn_kernel<unsigned short>);
+    const int grid = pers ? device_cu_count() / 8 * 8 : xcd_grid(MT, heads), lds = pers ? QP_LDS : QA_LDS;
+    if (int rc = ivr_func_max_lds(reinterpret_cast<const void *>(kern), lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, g);
     IVR_LAUNCH_CHECK();
     return IVR_OK;
 }
