@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IVR_API_VERSION 5
+#define IVR_API_VERSION 6
 #define IVR_MAX_K 2048          /* reference: k=50 default, SearchOptions.limit <= 1000 (system.py:91) */
 
 typedef enum ivr_status {
@@ -232,6 +232,14 @@ int ivr_index_search(ivr_index *idx, const float *q /*DEV*/, int nq, int k, int 
  * scan copy, out[1] = number of queries of the LAST scan chunk (<= 64 queries) whose verification failed and which were redone by
  * the exact float32 scan.  Synchronises the device. */
 int ivr_index_scan_stats(ivr_index *index, int *out /*HOST [2]*/);
+/* Exact range search by inner product: for each query, every stored row with <q, row> > radius (strict, as faiss does for
+ * METRIC_INNER_PRODUCT).  lims: DEV int64 [nq+1], lims[0] = 0, results of query i at [lims[i], lims[i+1]), ids ascending
+ * within a query (id = id_base + row).  D/I: DEV, capacity `cap` entries; entries at positions >= cap are counted in lims
+ * but not written (the caller re-calls with cap >= lims[nq]).  Enqueues only: no host synchronisation.
+ * Scores are bit-identical to the ones ivr_index_search reports for the same rows.  radius must not be NaN (+-inf are allowed);
+ * an empty index gives all-zero lims. */
+int ivr_index_range_search(ivr_index *idx, const float *q /*DEV*/, int nq, float radius, int normalize_q, int64_t id_base,
+                           int64_t *lims /*DEV*/, float *D /*DEV*/, int64_t *I /*DEV*/, int64_t cap, ivr_stream stream);
 
 /* Merge per-shard candidate lists (the reference's concat + sort of peer results, system.py:1744-1746):
  * D_parts/I_parts DEV [parts, nq, k] with global ids, parts ordered by ascending id range. */

@@ -26,7 +26,7 @@ class TowerDesc(C.Structure):
                                                                       ("fp8_first_layer", C.c_int)]
 
 
-API_VERSION = 5
+API_VERSION = 6
 FP8_SITE = {"qkv": 1, "o": 2, "fc1": 4, "fc2": 8}
 
 
@@ -72,6 +72,7 @@ _SIGS = {
     "ivr_index_reconstruct": (_i, [_p, _i64, _i64, _p, _p]),
     "ivr_index_reserve_search": (_i, [_p, _i, _i]),
     "ivr_index_search": (_i, [_p, _p, _i, _i, _i, _i64, _p, _p, _p]),
+    "ivr_index_range_search": (_i, [_p, _p, _i, _f, _i, _i64, _p, _p, _p, _i64, _p]),
     "ivr_topk_merge": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_topk_pack": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "ivr_topk_merge_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),

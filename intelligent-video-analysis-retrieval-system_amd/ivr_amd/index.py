@@ -157,6 +157,53 @@ class FlatIPIndex:
                 torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
         return D, I
 
+    def range_search(self, x, radius):
+        """faiss range_search: every row with <q, row> > radius.  (lims int64 [nq+1], D float32 [lims[-1]], I int64 [lims[-1]])
+        numpy arrays; query i's results are D/I[lims[i]:lims[i+1]], ids ascending.  One host sync to read the total; a second
+        pass only when the first-guess capacity was too small."""
+        q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
+        if isinstance(q, np.ndarray) and q.ndim == 1:
+            q = q.reshape(1, -1)
+        t = _dev_f32(q, self.device)
+        cap = max(1024, 64 * t.shape[0])
+        lims, D, I, total = self.range_search_device(t, radius, cap=cap)
+        n = int(total.item())
+        if n > cap:
+            lims, D, I, total = self.range_search_device(t, radius, cap=n)
+        return lims.cpu().numpy(), D[:n].cpu().numpy(), I[:n].cpu().numpy()
+
+    def range_search_device(self, x, radius, normalize=False, id_base=0, cap=None):
+        """Device-resident range search: (lims [nq+1], D [cap], I [cap], total) CUDA tensors, total = lims[nq:] (the number of
+        results; entries at positions >= cap are counted but not written).  No host sync when `cap` is given; cap=None sizes
+        D and I exactly (a counting pass, one sync, then the full pass)."""
+        radius = float(radius)
+        if radius != radius:
+            raise ValueError("range_search: radius is NaN")
+        t = _dev_f32(x, self.device)
+        if t.dim() != 2 or t.shape[1] != self.d:
+            raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({self.d})")
+        nq = t.shape[0]
+        if nq < 1:
+            raise ValueError("range_search: no queries")
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=self.device)
+
+        def run(c):
+            D = torch.empty(max(c, 1), dtype=torch.float32, device=self.device)   # never a NULL pointer, even for cap 0
+            I = torch.empty(max(c, 1), dtype=torch.int64, device=self.device)
+            _ffi.check(self._lib.ivr_index_range_search(self._h, C.c_void_p(t.data_ptr()), nq, C.c_float(radius), int(bool(normalize)),
+                                                        int(id_base), C.c_void_p(lims.data_ptr()), C.c_void_p(D.data_ptr()),
+                                                        C.c_void_p(I.data_ptr()), int(c), _ffi.stream_ptr()), "ivr_index_range_search")
+            return D[:c], I[:c]
+
+        with torch.cuda.device(self.device):
+            if cap is None:
+                run(0)
+                cap = int(lims[nq].item())
+            D, I = run(int(cap))
+            if t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0):
+                torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
+        return lims, D, I, lims[nq:]
+
     def reserve_search(self, max_nq, max_k):
         with torch.cuda.device(self.device):
             _ffi.check(self._lib.ivr_index_reserve_search(self._h, int(max_nq), int(max_k)), "ivr_index_reserve_search")

@@ -10,7 +10,8 @@ The message is nq*k*12 bytes per rank (1000x10 -> 120 KB): latency-bound, so a s
 collective is the right shape; no other exchange exists on this path.
 
 The class is agnostic of how a shard is searched: `local` only needs
-`search_device(q, k, normalize=, id_base=) -> (D, I)` tensors, `add`, `ntotal`.  On GPUs that
+`search_device(q, k, normalize=, id_base=) -> (D, I)` tensors, `add`, `ntotal` (and
+`range_search_device(q, radius, normalize=, id_base=) -> (lims, D, I, total)` for range_search).  On GPUs that
 is `ivr_amd.index.FlatIPIndex`; the world_size-2 gloo tests on CPU plug the oracle in.
 """
 import numpy as np
@@ -52,6 +53,42 @@ def merge_host(D_parts, I_parts, k):
     return D, I
 
 
+def pack_range(D, I, n, width):
+    """The first n range-search results of one shard -> int32 [width, 3] (score bits, id lo, id hi), zero padded: the wire format
+    of the range search's all-gather."""
+    cand = torch.zeros((width, 3), dtype=torch.int32, device=D.device)
+    if n:
+        cand[:n, 0] = D[:n].contiguous().view(torch.int32)
+        cand[:n, 1] = (I[:n] & 0xFFFFFFFF).to(torch.int32)      # low word, wrapped into int32
+        cand[:n, 2] = (I[:n] >> 32).to(torch.int32)
+    return cand
+
+
+def merge_range(counts, packed):
+    """Merge per-shard range-search results: counts int64 [parts, nq] (results per query of each shard), packed int32
+    [parts, width, 3] (pack_range of each shard), parts in ascending id order -> (lims [nq+1], D, I).  Query i's results are the
+    shards' parts for query i in shard order, so ids stay ascending; only index arithmetic, no sort."""
+    parts, nq = counts.shape
+    dev = packed.device
+    lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    lims[1:] = torch.cumsum(counts.sum(0), 0)
+    totals = counts.sum(1)
+    # entry e of shard r that belongs to query i goes to lims[i] + (results of lower shards for query i) + (e - shard r's start of i)
+    before = torch.cumsum(counts, 0) - counts
+    starts = torch.cumsum(counts, 1) - counts
+    shift = (lims[:-1].unsqueeze(0) + before - starts).reshape(-1)
+    qid = torch.arange(parts * nq, device=dev).repeat_interleave(counts.reshape(-1))      # (shard, query) of each entry
+    local_e = torch.arange(qid.numel(), device=dev) - (torch.cumsum(totals, 0) - totals).repeat_interleave(totals)
+    flat = packed[qid // nq, local_e]
+    total = qid.numel()
+    D = torch.empty(total, dtype=torch.float32, device=dev)
+    I = torch.empty(total, dtype=torch.int64, device=dev)
+    dest = shift[qid] + local_e
+    D[dest] = flat[:, 0].contiguous().view(torch.float32)
+    I[dest] = (flat[:, 1].to(torch.int64) & 0xFFFFFFFF) | (flat[:, 2].to(torch.int64) << 32)
+    return lims, D, I
+
+
 class ShardedIndex:
     def __init__(self, local, d, group=None, merge="device"):
         self.local = local
@@ -89,6 +126,28 @@ class ShardedIndex:
         """q [nq,d] replicated on every rank -> (D [nq,k], I [nq,k] global ids), identical on every rank."""
         D, I = self.local.search_device(q, k, normalize=normalize, id_base=self.id_base)
         return self.exchange(D, I)
+
+    def range_search(self, q, radius, normalize=False):
+        """Exact range search over all shards: q [nq,d] replicated on every rank -> (lims [nq+1], D, I global ids), identical on
+        every rank and laid out like FlatIPIndex.range_search (ids ascending within a query).  Two collectives: an all-gather of the
+        per-query counts, then ONE all-gather of the packed (score, id) results padded to the largest rank's total.  Shards are
+        contiguous and ascending, so concatenating each query's parts in rank order keeps its ids ascending: no sort."""
+        lims, D, I, _ = self.local.range_search_device(q, radius, normalize=normalize, id_base=self.id_base)
+        if self.world == 1:
+            return lims, D, I
+        nq = lims.numel() - 1
+        dev = lims.device
+        counts = (lims[1:] - lims[:-1]).contiguous()
+        counts_all = torch.empty(self.world * nq, dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(counts_all, counts, group=self.group)
+        counts_all = counts_all.view(self.world, nq)
+        totals = counts_all.sum(1)
+        width = int(totals.max().item())
+        if width == 0:
+            return merge_range(counts_all, torch.empty((self.world, 0, 3), dtype=torch.int32, device=dev))
+        gathered = torch.empty((self.world * width, 3), dtype=torch.int32, device=dev)
+        dist.all_gather_into_tensor(gathered, pack_range(D, I, int(totals[self.rank].item()), width), group=self.group)
+        return merge_range(counts_all, gathered.view(self.world, width, 3))
 
     def exchange(self, D, I):
         """The single exchange step of the path: this rank's candidates (D [nq,k] scores, I [nq,k] GLOBAL ids, unused slots -1)
