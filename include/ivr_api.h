@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IVR_API_VERSION 6
+#define IVR_API_VERSION 7
 #define IVR_MAX_K 2048          /* reference: k=50 default, SearchOptions.limit <= 1000 (system.py:91) */
 
 typedef enum ivr_status {
@@ -168,6 +168,37 @@ int ivr_linear(ivr_ctx *ctx, int f32_mode, int epilogue, const void *x /*DEV*/, 
 int ivr_linear_fp8(ivr_ctx *ctx, int epilogue, const void *x /*DEV*/, const void *w /*DEV*/, const float *colscale /*DEV*/,
                    const float *bias /*DEV*/, int M, int N, int K, int act, void *out /*DEV*/, int out_fp8,
                    float *resid /*DEV*/, ivr_stream stream);
+
+/* Every GEMM call site of the towers, exposed for the per-element tests: the GemmArgs fields the towers set, routed through the
+ * same launchers (kernel choice, slabs of row operands beyond 2 GiB and the IVR_GEMM* switches included).
+ *   y[m, n] = sum_k A[m*lda + k] W[n*ldw + k] (* colscale[n], e4m3 only) (+ bias[n])
+ *   IVR_EPI_STORE: out[m*ldo + n] = act(y) in the operand dtype (e4m3: bf16, or saturated e4m3 bytes with out8 = 1)
+ *   IVR_EPI_RESID: resid[m*ldr + n] += y, except rows m % skip_mod == 0 (skip_mod > 0), which are left untouched
+ *   IVR_EPI_PATCH: resid[((m / G2) * T + 1 + m % G2) * ldr + n] = y + pos[(1 + m % G2) * N + n] (patch embedding: token 0 of every
+ *                  image is not written); bf16 / float32 operands, M % G2 == 0, T > G2
+ *   IVR_EPI_F32:   out[m*ldo + n] = y as float32 (bf16 / float32 operands)
+ * Limits: bf16 K % 64 == 0, float32 K % 32 == 0, N % 4 == 0; e4m3 K % 128 == 0, N % 64 == 0, lda and ldw % 16 == 0.  K <= lda, ldw;
+ * N <= ldo (STORE, F32), ldr (RESID, PATCH); every leading dimension at most 2^21, lda and ldw whole multiples of 16 bytes, ldo and
+ * ldr multiples of 4 (e4m3 output: ldo % 16 == 0, bf16 output of e4m3: ldo % 8 == 0), pointers 16-byte aligned.  act (IVR_ACT_*, -1 none) only with IVR_EPI_STORE, skip_mod only with IVR_EPI_RESID, colscale and out8 only with e4m3.
+ * reverse_m = 1 walks the row panels from the last to the first (same result).  M = 0 is a no-op. */
+enum { IVR_GEMM_BF16 = 0, IVR_GEMM_F32 = 1, IVR_GEMM_E4M3 = 2 };
+enum { IVR_EPI_STORE = 0, IVR_EPI_RESID = 1, IVR_EPI_PATCH = 2, IVR_EPI_F32 = 3 };
+typedef struct ivr_gemm_desc {
+    int dtype, epilogue, act;            /* IVR_GEMM_*, IVR_EPI_*, -1 or IVR_ACT_* */
+    int M, N, K;
+    const void *A;                       /* DEV [M, lda] */
+    int lda;
+    const void *W;                       /* DEV [N, ldw] */
+    int ldw;
+    const float *bias, *colscale;        /* DEV float32 [N] or NULL */
+    void *out;                           /* DEV [M, ldo] */
+    int ldo, out8;
+    float *resid;                        /* DEV float32: [M, ldr] (RESID), [(M / G2) * T, ldr] (PATCH) */
+    int ldr;
+    const float *pos;                    /* DEV float32 [T, N] (PATCH) */
+    int T, G2, skip_mod, reverse_m;
+} ivr_gemm_desc;
+int ivr_gemm(ivr_ctx *ctx, const ivr_gemm_desc *desc, ivr_stream stream);
 
 /* Attention of the towers, exposed for parity tests and kernel benchmarks: att[n*T, D] = softmax(Q K^T [+ causal mask]) V per
  * (image, head), the scaled_dot_product_attention inside the HF attention modules (modeling_clip.py:259-277).  qkv: DEV

@@ -685,6 +685,71 @@ int ivr_linear_fp8(ivr_ctx *ctx, int epilogue, const void *x, const void *w, con
 
 static bool al16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
+int ivr_gemm(ivr_ctx *ctx, const ivr_gemm_desc *d, ivr_stream stream) {
+    IVR_REQUIRE(ctx && d, "ivr_gemm: NULL argument");
+    const int dt = d->dtype, epi = d->epilogue;
+    IVR_REQUIRE(dt == IVR_GEMM_BF16 || dt == IVR_GEMM_F32 || dt == IVR_GEMM_E4M3, "ivr_gemm: dtype=%d", dt);
+    IVR_REQUIRE(epi == EPI_STORE || epi == EPI_RESID || epi == EPI_PATCH || epi == EPI_F32, "ivr_gemm: epilogue=%d", epi);
+    IVR_REQUIRE(dt != IVR_GEMM_E4M3 || epi == EPI_STORE || epi == EPI_RESID, "ivr_gemm: e4m3 takes the store and residual epilogues only");
+    IVR_REQUIRE(d->act == -1 || ((d->act == IVR_ACT_QUICK_GELU || d->act == IVR_ACT_GELU_ERF) && epi == EPI_STORE),
+                "ivr_gemm: act=%d (an activation only with the store epilogue)", d->act);
+    IVR_REQUIRE(d->out8 == 0 || (d->out8 == 1 && dt == IVR_GEMM_E4M3 && epi == EPI_STORE), "ivr_gemm: out8=%d (e4m3 store only)", d->out8);
+    IVR_REQUIRE(!d->colscale || dt == IVR_GEMM_E4M3, "ivr_gemm: colscale is the e4m3 weight scale");
+    IVR_REQUIRE(d->skip_mod >= 0 && (d->skip_mod == 0 || epi == EPI_RESID), "ivr_gemm: skip_mod=%d (residual epilogue only)", d->skip_mod);
+    IVR_REQUIRE(d->reverse_m == 0 || d->reverse_m == 1, "ivr_gemm: reverse_m=%d", d->reverse_m);
+    // sizes and strides bounded before any product of them is formed
+    IVR_REQUIRE(d->M >= 0 && d->N >= 4 && d->K >= 1, "ivr_gemm: M=%d N=%d K=%d", d->M, d->N, d->K);
+    const int kq = dt == IVR_GEMM_BF16 ? 64 : dt == IVR_GEMM_F32 ? 32 : 128, nq = dt == IVR_GEMM_E4M3 ? 64 : 4;
+    IVR_REQUIRE(d->K % kq == 0 && d->N % nq == 0, "ivr_gemm: K=%d must be a multiple of %d and N=%d of %d", d->K, kq, d->N, nq);
+    const int64_t es = dt == IVR_GEMM_BF16 ? 2 : dt == IVR_GEMM_F32 ? 4 : 1;
+    constexpr int kMaxLd = 1 << 21;
+    const bool to_out = epi == EPI_STORE || epi == EPI_F32;
+    IVR_REQUIRE(d->lda >= d->K && d->lda <= kMaxLd && d->ldw >= d->K && d->ldw <= kMaxLd && d->lda * es % 16 == 0 && d->ldw * es % 16 == 0,
+                "ivr_gemm: lda=%d ldw=%d (K=%d <= ld <= 2^21, rows of whole 16 bytes)", d->lda, d->ldw, d->K);
+    if (to_out)
+        IVR_REQUIRE(d->out && al16(d->out) && d->ldo >= d->N && d->ldo <= kMaxLd && d->ldo % 4 == 0,
+                    "ivr_gemm: out / ldo=%d (N=%d <= ldo <= 2^21, ldo %% 4 == 0)", d->ldo, d->N);
+    else
+        IVR_REQUIRE(d->resid && al16(d->resid) && d->ldr >= d->N && d->ldr <= kMaxLd && d->ldr % 4 == 0,
+                    "ivr_gemm: resid / ldr=%d (N=%d <= ldr <= 2^21, ldr %% 4 == 0)", d->ldr, d->N);
+    if (epi == EPI_PATCH) {
+        IVR_REQUIRE(d->pos && al16(d->pos), "ivr_gemm: the patch epilogue needs pos");
+        IVR_REQUIRE(d->G2 >= 1 && d->T > d->G2 && d->T <= kMaxLd && d->M % d->G2 == 0, "ivr_gemm: patch epilogue T=%d G2=%d M=%d (T > G2, M %% G2 == 0)",
+                    d->T, d->G2, d->M);
+    }
+    IVR_REQUIRE(d->A && d->W && al16(d->A) && al16(d->W) && al16(d->bias) && al16(d->colscale), "ivr_gemm: A, W, bias and colscale must be "
+                "16-byte aligned (A and W not NULL)");
+    if (d->M == 0) return IVR_OK;
+    IVR_HIP(hipSetDevice(ctx->device));
+    GemmArgs g;
+    g.A = d->A;
+    g.lda = d->lda;
+    g.W = d->W;
+    g.ldw = d->ldw;
+    g.M = d->M;
+    g.N = d->N;
+    g.K = d->K;
+    g.bias = d->bias;
+    g.colscale = d->colscale;
+    g.out = to_out ? d->out : nullptr;
+    g.ldo = to_out ? d->ldo : 0;
+    g.out8 = d->out8;
+    g.resid = to_out ? nullptr : d->resid;
+    g.ldr = to_out ? 0 : d->ldr;
+    if (epi == EPI_PATCH) {
+        g.pos = d->pos;
+        g.T = d->T;
+        g.G2 = d->G2;
+    }
+    g.act = d->act;
+    g.skip_mod = d->skip_mod;
+    g.reverse_m = d->reverse_m;
+    g.tag = "gemm";
+    // the routing of layer_gemm
+    if (dt == IVR_GEMM_E4M3) return ivr_launch_gemm_fp8(epi, g, (hipStream_t)stream);
+    return ivr_launch_gemm(dt == IVR_GEMM_F32, epi, g, (hipStream_t)stream);
+}
+
 int ivr_attention(ivr_ctx *ctx, int f32_mode, const void *qkv, int n, int T, int D, int heads, int causal, int out_fp8, void *att,
                   ivr_stream stream) {
     IVR_REQUIRE(ctx && (n == 0 || (qkv && att)), "ivr_attention: NULL argument");

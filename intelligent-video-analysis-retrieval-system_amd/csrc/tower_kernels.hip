@@ -633,6 +633,8 @@ __device__ __forceinline__ void wait_vm_barrier() {
 //     MFMA queued behind them).  The last two pieces of a stage go out early in the following stage.
 //   * s_memtime stamps (-DIVR_GEMM_STAMPS, tools/gemm_stamps.py) on a K=768 qkv tile: prologue 2.5k, K loop 30.8k
 //     (2566 cycles per stage, 2048 = MFMA-bound), epilogue 6.7k cycles.
+//   * same bits as gemm_kernel for every epilogue: one fp32 accumulator per output, the same MFMA per 16-byte chunk with K
+//     ascending, the same epilogue expressions (tests/test_gemm_gpu.py::test_128_and_256_tiles_give_the_same_bits).
 // ---------------------------------------------------------------------------------------------
 constexpr int LBM = 256, LBN = 256, LX_BYTES = LBM * ROWB, LW_BYTES = LBN * ROWB;
 constexpr int DEEP_LDS = 3 * LX_BYTES + 2 * LW_BYTES;   // 160 KiB (bf16 / f32 kernel: three X slots, two W slots)

@@ -26,7 +26,16 @@ class TowerDesc(C.Structure):
                                                                       ("fp8_first_layer", C.c_int)]
 
 
-API_VERSION = 6
+class GemmDesc(C.Structure):
+    """ivr_gemm_desc (include/ivr_api.h)."""
+    _fields_ = ([(n, C.c_int) for n in ("dtype", "epilogue", "act", "M", "N", "K")]
+                + [("A", C.c_void_p), ("lda", C.c_int), ("W", C.c_void_p), ("ldw", C.c_int), ("bias", C.c_void_p),
+                   ("colscale", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int), ("out8", C.c_int), ("resid", C.c_void_p),
+                   ("ldr", C.c_int), ("pos", C.c_void_p)]
+                + [(n, C.c_int) for n in ("T", "G2", "skip_mod", "reverse_m")])
+
+
+API_VERSION = 7
 FP8_SITE = {"qkv": 1, "o": 2, "fc1": 4, "fc2": 8}
 
 
@@ -58,6 +67,7 @@ _SIGS = {
     "ivr_qkv_attention": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "ivr_layernorm": (_i, [_p, _i, _p, _i, _p, _p, _p, _f, _i, _i, _i, _p, _p]),
     "ivr_linear_fp8": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p]),
+    "ivr_gemm": (_i, [_p, C.POINTER(GemmDesc), _p]),
     "ivr_l2_normalize": (_i, [_p, _p, _i64, _i, _p, _p]),
     "ivr_index_create": (_i, [_p, _i, _i64, C.POINTER(_p)]),
     "ivr_index_destroy": (_i, [_p]),

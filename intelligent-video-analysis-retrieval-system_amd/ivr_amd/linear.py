@@ -61,3 +61,32 @@ def linear_fp8(x8, w8, colscale=None, bias=None, act=-1, epilogue=EPI_STORE, out
     if epilogue == EPI_RESID:
         return resid
     return out.view(torch.float8_e4m3fn) if out_fp8 else out
+
+
+EPI_PATCH = 2
+DTYPE = {torch.bfloat16: 0, torch.float32: 1, torch.float8_e4m3fn: 2, torch.uint8: 2}
+
+
+def gemm(a, w, *, M=None, N=None, K=None, lda=None, ldw=None, epilogue=EPI_STORE, act=-1, bias=None, colscale=None, out=None, ldo=None,
+         out8=False, resid=None, ldr=None, pos=None, T=0, G2=0, skip_mod=0, reverse_m=0, stream=None):
+    """ivr_gemm: one call of the towers' GEMM with every GemmArgs field the towers set (strided operands and outputs, the patch
+    epilogue, skipped residual rows, reversed row order).  a, w: CUDA tensors of the operand dtype (bf16, float32, or e4m3 as
+    float8_e4m3fn / uint8) whose storage holds [M, lda] and [N, ldw]; the outputs are written in place into `out` / `resid`, which the
+    caller allocates (and may fill with sentinels).  M, N, K and the leading dimensions default to the dense shapes of a and w."""
+    lib = _ffi.load()
+    dt = DTYPE.get(a.dtype)
+    if dt is None or DTYPE.get(w.dtype) != dt:
+        raise ValueError("a and w must share one of bf16, float32, e4m3")
+    M = a.shape[0] if M is None else M
+    N = w.shape[0] if N is None else N
+    K = a.shape[1] if K is None else K
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    d = _ffi.GemmDesc(dtype=dt, epilogue=int(epilogue), act=int(act), M=int(M), N=int(N), K=int(K),
+                      A=ptr(a), lda=int(a.stride(0) if lda is None else lda), W=ptr(w), ldw=int(w.stride(0) if ldw is None else ldw),
+                      bias=ptr(bias), colscale=ptr(colscale), out=ptr(out),
+                      ldo=int(ldo if ldo is not None else (out.stride(0) if out is not None else 0)), out8=int(bool(out8)),
+                      resid=ptr(resid), ldr=int(ldr if ldr is not None else (resid.stride(0) if resid is not None else 0)),
+                      pos=ptr(pos), T=int(T), G2=int(G2), skip_mod=int(skip_mod), reverse_m=int(reverse_m))
+    with torch.cuda.device(a.device):
+        _ffi.check(lib.ivr_gemm(_ffi.context(a.device.index), C.byref(d), _ffi.stream_ptr(stream)), "ivr_gemm")
+    return out if out is not None else resid

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from ivr_amd import config as C
+from oracle.gemm_ref import error_ratio
 
 pytestmark = pytest.mark.gpu
 
@@ -50,9 +51,11 @@ def test_fp8_gemm_bf16_output(M, N, K):
         y = linear_fp8(x8, w8, ws, b, act=act).float().cpu()
         ref = _ref(x8, w8, ws, b, act)
         assert (y - ref).abs().max() <= 1.2e-2 * max(1.0, ref.abs().max()), (act, (y - ref).abs().max())
+        assert error_ratio(y, x8, w8, "e4m3", "bf16", colscale=ws, bias=b, act=act) <= 1.0, act   # per element (oracle/gemm_ref.py)
     y = linear_fp8(x8, w8, None, None).float().cpu()            # no scale, no bias
     ref = x8.float().cpu() @ w8.view(torch.float8_e4m3fn).float().cpu().T
     assert (y - ref).abs().max() <= 1.2e-2 * max(1.0, ref.abs().max())
+    assert error_ratio(y, x8, w8, "e4m3", "bf16") <= 1.0
 
 
 def test_fp8_gemm_exact_small_integers():
@@ -76,12 +79,14 @@ def test_fp8_gemm_residual_and_e4m3_output():
     linear_fp8(x8, w8, ws, b, epilogue=EPI_RESID, resid=r)
     ref = _ref(x8, w8, ws, b, -1)
     assert (r.cpu() - (r0.cpu() + ref)).abs().max() < 1e-4 * max(1.0, ref.abs().max())
+    assert error_ratio(r, x8, w8, "e4m3", "f32", colscale=ws, bias=b, r=r0) <= 1.0
     for act in (-1, 0):
         y8 = linear_fp8(x8, w8, ws, b, act=act, out_fp8=True)
         ref = _ref(x8, w8, ws, b, act)
         y = y8.float().cpu()
         # one e4m3 step: 2^-3 of the value for normals, 2^-9 absolute in the subnormal range
         assert ((y - ref).abs() <= 0.0626 * ref.abs() + 2.0 ** -9).all(), (act, (y - ref).abs().max())
+        assert error_ratio(y8, x8, w8, "e4m3", "e4m3", colscale=ws, bias=b, act=act) <= 1.0, act
     big = linear_fp8(x8, w8, ws * 1e4, b, out_fp8=True).float()      # saturation, not NaN / inf
     assert torch.isfinite(big).all() and big.abs().max() == 448.0
 

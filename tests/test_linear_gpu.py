@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from oracle.gemm_ref import error_ratio
+
 pytestmark = pytest.mark.gpu
 
 
@@ -43,8 +45,11 @@ def test_store_epilogue_with_activations(dtype, M, N, K, kernel):
         ref = _ref(x, w, b, act)
         tol = 2e-5 if dtype == torch.float32 else 1.2e-2       # bf16 output rounding: 2^-8 relative
         assert (y - ref).abs().max() <= tol * max(1.0, ref.abs().max()), (act, (y - ref).abs().max())
+        kind = "f32" if dtype == torch.float32 else "bf16"
+        assert error_ratio(y, x, w, kind, kind, bias=b, act=act) <= 1.0, act     # per element (oracle/gemm_ref.py)
     y = linear(x, w, None)                                      # no bias
     assert (y.float().cpu() - _ref(x, w, None, -1)).abs().max() <= (2e-5 if dtype == torch.float32 else 1.2e-2) * 4
+    assert error_ratio(y, x, w, kind, kind) <= 1.0
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -60,8 +65,11 @@ def test_residual_and_f32_epilogues(dtype, M, N, K, kernel):
     linear(x, w, b, epilogue=EPI_RESID, resid=r)
     ref = r0.cpu() + _ref(x, w, b, -1)
     assert (r.cpu() - ref).abs().max() < 2e-5 * 4               # accumulation and the residual stay in float32
+    kind = "f32" if dtype == torch.float32 else "bf16"
+    assert error_ratio(r, x, w, kind, "f32", bias=b, r=r0) <= 1.0
     y = linear(x, w, None, epilogue=EPI_F32)
     assert y.dtype == torch.float32 and (y.cpu() - _ref(x, w, None, -1)).abs().max() < 2e-5 * 4
+    assert error_ratio(y, x, w, kind, "f32") <= 1.0
 
 
 def test_exact_integer_operands_catch_layout_errors(kernel):
@@ -104,12 +112,14 @@ def test_row_operand_beyond_2gib_runs_in_slabs():
                         device="cuda")
     ref = x[rows].float() @ w.float().T + b
     assert (y[rows].float() - ref).abs().max() <= 1.2e-2 * max(1.0, float(ref.abs().max()))
+    assert error_ratio(y[rows], x[rows], w, "bf16", "bf16", bias=b) <= 1.0
     # every row was written: an unwritten slab would leave torch.empty garbage, caught by a checksum against a chunked product
     tot = sum(float((x[i:i + 100_000].float() @ w.float().T + b).double().sum()) for i in range(0, M, 100_000))
     assert abs(float(y.double().sum()) - tot) <= 2e-3 * M ** 0.5 * N ** 0.5 + 1e-6 * abs(tot) + 50.0
     r = torch.zeros((M, N), dtype=torch.float32, device="cuda")
     linear(x, w, b, epilogue=EPI_RESID, resid=r)
     assert (r[rows] - ref).abs().max() < 2e-4 * max(1.0, float(ref.abs().max()))
+    assert error_ratio(r[rows], x[rows], w, "bf16", "f32", bias=b, r=torch.zeros_like(r[rows])) <= 1.0
 
 
 @pytest.mark.parametrize("M,N,K,act", [(40_000, 768, 768, -1), (11_003, 3072, 768, 0), (70_001, 768, 3072, -1), (131_072, 256, 128, 1),
@@ -143,6 +153,8 @@ def test_persistent_kernel_is_bit_identical_to_the_tile_per_workgroup_kernel(M, 
     elif act == 1:
         ref = torch.nn.functional.gelu(ref)
     assert (outs[("2", "3")][0][rows].float() - ref).abs().max() <= 1.2e-2 * max(1.0, float(ref.abs().max()))
+    assert error_ratio(outs[("2", "3")][0][rows], x[rows], w, "bf16", "bf16", bias=b, act=act) <= 1.0
+    assert error_ratio(outs[("2", "3")][1][rows], x[rows], w, "bf16", "f32", bias=b, r=r0[rows]) <= 1.0
     xi = torch.randint(-3, 4, (M, K), generator=g, device="cuda").to(torch.bfloat16)
     wi = torch.randint(-3, 4, (N, K), generator=g, device="cuda").to(torch.bfloat16)
     monkeypatch.setenv("IVR_GEMM_PERS", "2")
@@ -177,3 +189,7 @@ def test_skinny_kernel_is_bit_identical_to_the_tiled_kernels(dtype, M, N, K, mon
         assert torch.equal(a, t)
     ref = _ref(x, w, b, -1)
     assert (skinny[0].float().cpu() - ref).abs().max() <= (2e-5 if dtype == torch.float32 else 1.2e-2) * max(1.0, ref.abs().max())
+    kind = "f32" if dtype == torch.float32 else "bf16"
+    for a, out in zip((-1, 0, 1), skinny[:3]):
+        assert error_ratio(out, x, w, kind, kind, bias=b, act=a) <= 1.0, a
+    assert error_ratio(skinny[4], x, w, kind, "f32", bias=b, r=r0) <= 1.0
