@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IVR_API_VERSION 7
+#define IVR_API_VERSION 8
 #define IVR_MAX_K 2048          /* reference: k=50 default, SearchOptions.limit <= 1000 (system.py:91) */
 
 typedef enum ivr_status {
@@ -271,6 +271,25 @@ int ivr_index_scan_stats(ivr_index *index, int *out /*HOST [2]*/);
  * an empty index gives all-zero lims. */
 int ivr_index_range_search(ivr_index *idx, const float *q /*DEV*/, int nq, float radius, int normalize_q, int64_t id_base,
                            int64_t *lims /*DEV*/, float *D /*DEV*/, int64_t *I /*DEV*/, int64_t cap, ivr_stream stream);
+
+/* Filtered search (faiss SearchParameters(sel=IDSelector...)): which ids a filtered search may return (id = id_base + row).  An id is
+ * allowed iff lo <= id < hi and, when bits != NULL, id < nbits && ((bits[id >> 3] >> (id & 7)) & 1): faiss IDSelectorBitmap order =
+ * numpy.packbits(mask, bitorder="little").  A bitmap byte is only read for an id inside [lo, hi), so bits may point in front of the
+ * caller's buffer by the bytes below lo >> 3. */
+typedef struct ivr_id_filter {
+    int64_t lo, hi;          /* lo >= hi: nothing allowed */
+    const uint8_t *bits;     /* DEV, or NULL: the range alone */
+    int64_t nbits;           /* >= 0 */
+} ivr_id_filter;
+/* ivr_index_search / ivr_index_range_search limited to the allowed rows: top k (or every row above radius) among them only, ties to the
+ * lower id, unused slots (-FLT_MAX, -1); each score is bit-identical to the one ivr_index_search reports for that row.  Only the 64-row
+ * groups that overlap the allowed id range are scanned.  Enqueues only (no host synchronisation) and allocates nothing the unfiltered
+ * call would not.  filter: HOST, read during the call; NULL = the unfiltered call. */
+int ivr_index_search_filtered(ivr_index *idx, const float *q /*DEV*/, int nq, int k, int normalize_q, int64_t id_base,
+                              const ivr_id_filter *filter /*HOST*/, float *D /*DEV*/, int64_t *I /*DEV*/, ivr_stream stream);
+int ivr_index_range_search_filtered(ivr_index *idx, const float *q /*DEV*/, int nq, float radius, int normalize_q, int64_t id_base,
+                                    const ivr_id_filter *filter /*HOST*/, int64_t *lims /*DEV*/, float *D /*DEV*/, int64_t *I /*DEV*/,
+                                    int64_t cap, ivr_stream stream);
 
 /* Merge per-shard candidate lists (the reference's concat + sort of peer results, system.py:1744-1746):
  * D_parts/I_parts DEV [parts, nq, k] with global ids, parts ordered by ascending id range. */

@@ -17,6 +17,8 @@
 //   pass 3   re-score the selected groups with the same MFMA sequence (bit-identical scores) and emit
 //            64-bit keys (ordered score, ~row).
 //   pass 4   per query, radix-select + bitonic sort of the k best keys -> D (float32), I (int64).
+//   filtered (ivr_index_search_filtered): the same passes over the 256-row blocks that cover the allowed id range,
+//            on the masked instantiations (MASK): rows that are not allowed count as -inf in every maximum and get no key.
 #include "ivr_common.h"
 #include "search_internal.h"
 
@@ -281,9 +283,12 @@ __device__ __forceinline__ void score_group(const float4 *__restrict__ a, int64_
 
 // pass 1.  gmax layout: [16*QT queries][mstride groups]
 // the wave loop of the exact scan: every 64-row group against the 16*QT queries staged in qs
-template <int QT>
+// MASK (filtered search): rows that are not allowed count as -inf, allowed ones as max(score, -FLT_MAX) (search_internal.h)
+// The masked instantiations take the mask as a trailing parameter pack (one RowMask; empty for the plain ones, whose parameter lists and
+// code stay exactly what they were).
+template <int QT, bool MASK = false, typename... M>
 __device__ __forceinline__ void scan_groups_body(const float4 *__restrict__ qs, const float *__restrict__ data, int dp4, int64_t ngroups,
-                                                 int64_t ntotal, float *__restrict__ gmax, int64_t mstride) {
+                                                 int64_t ntotal, float *__restrict__ gmax, int64_t mstride, const M &...rm) {
     const int per_tile = dp4 * 16;   // float4 per 16-row tile
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int kchunks = dp4 >> 2;
@@ -291,17 +296,22 @@ __device__ __forceinline__ void scan_groups_body(const float4 *__restrict__ qs, 
     for (int64_t g = (int64_t)blockIdx.x * nw + wave; g < ngroups; g += (int64_t)gridDim.x * nw) {
         f32x4 acc[QT][4];
         const float4 *a = reinterpret_cast<const float4 *>(data) + g * 4 * (int64_t)per_tile + lane;
+        uint32_t mbyte = 0;
+        if constexpr (MASK) mbyte = row_mask_fetch(rm..., g * kGroupRows);
         score_group<QT>(a, per_tile, kchunks, bload, acc);
         const bool partial = (g + 1) * kGroupRows > ntotal;   // wave-uniform: only the last group
+        uint64_t mw = 0;
+        if constexpr (MASK) mw = row_mask_word(rm..., g * kGroupRows, mbyte) >> ((lane >> 4) * 4);
 #pragma unroll
         for (int q = 0; q < QT; ++q) {
-            float m = -FLT_MAX;
+            float m = MASK ? -INFINITY : -FLT_MAX;
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float s = acc[q][t][r];
-                    if (partial && g * kGroupRows + t * 16 + (lane >> 4) * 4 + r >= ntotal) s = -FLT_MAX;
+                    if constexpr (MASK) s = row_mask_score(mw, t * 16 + r, s);
+                    else if (partial && g * kGroupRows + t * 16 + (lane >> 4) * 4 + r >= ntotal) s = -FLT_MAX;
                     m = fmaxf(m, s);
                 }
             m = fmaxf(m, __shfl_xor(m, 16, 64));
@@ -311,12 +321,12 @@ __device__ __forceinline__ void scan_groups_body(const float4 *__restrict__ qs, 
     }
 }
 
-template <int QT>
+template <int QT, bool MASK, typename... M>
 __global__ __launch_bounds__(512) void scan_groupmax_kernel(const float *__restrict__ data,
                                                             const float *__restrict__ qtiled, int dp4,
                                                             int64_t ngroups, int64_t ntotal,
                                                             float *__restrict__ gmax, int64_t mstride,
-                                                            const int *__restrict__ tile_flag) {
+                                                            const int *__restrict__ tile_flag, M... rm) {
     extern __shared__ __attribute__((aligned(16))) float4 qs[];
     if (tile_flag) {       // fallback pass behind the bf16 candidate scan: only query tiles that failed their verification
         bool any = false;
@@ -327,18 +337,18 @@ __global__ __launch_bounds__(512) void scan_groupmax_kernel(const float *__restr
     const int per_tile = dp4 * 16;
     for (int i = threadIdx.x; i < QT * per_tile; i += blockDim.x) qs[i] = reinterpret_cast<const float4 *>(qtiled)[i];
     __syncthreads();
-    scan_groups_body<QT>(qs, data, dp4, ngroups, ntotal, gmax, mstride);
+    scan_groups_body<QT, MASK>(qs, data, dp4, ngroups, ntotal, gmax, mstride, rm...);
 }
 
 // Exact pass behind the LARGE-batch candidate scan: the queries whose verification failed were appended to `list` by the final
 // selection (count = *nlist, known on the device only).  Each chunk of 16*QT listed queries is gathered from the tiled query
 // buffer straight into LDS (element (kc, lane) of a staged tile = the float4 of query (lane & 15), quad (lane >> 4), chunk kc)
 // and scanned like any other; nothing listed: every workgroup exits at once.  gmax row = position in the list.
-template <int QT>
+template <int QT, bool MASK, typename... M>
 __global__ __launch_bounds__(512) void scan_groupmax_list_kernel(const float *__restrict__ data, const float *__restrict__ qtiled,
                                                                  int dp4, int64_t ngroups, int64_t ntotal, float *__restrict__ gmax,
                                                                  int64_t mstride, const int *__restrict__ nlist,
-                                                                 const int *__restrict__ list) {
+                                                                 const int *__restrict__ list, M... rm) {
     extern __shared__ __attribute__((aligned(16))) float4 qs[];
     const int nf = *nlist;
     const int per_tile = dp4 * 16;
@@ -355,7 +365,7 @@ __global__ __launch_bounds__(512) void scan_groupmax_list_kernel(const float *__
             qs[i] = v;
         }
         __syncthreads();
-        scan_groups_body<QT>(qs, data, dp4, ngroups, ntotal, gmax + (int64_t)c0 * mstride, mstride);
+        scan_groups_body<QT, MASK>(qs, data, dp4, ngroups, ntotal, gmax + (int64_t)c0 * mstride, mstride, rm...);
     }
 }
 
@@ -367,10 +377,10 @@ __global__ __launch_bounds__(512) void scan_groupmax_list_kernel(const float *__
 // If that is strictly below the k-th exact score found among the kp re-scored groups, no excluded row can enter or tie the
 // top k.  Queries that fail the check are redone by the exact float32 scan (same launch sequence, predicated on device).
 // ---------------------------------------------------------------------------------------------
-template <int QT>
+template <int QT, bool MASK, typename... M>
 __global__ __launch_bounds__(512) void scan16_groupmax_kernel(const uint4 *__restrict__ data16, const uint4 *__restrict__ qhi,
                                                               const uint4 *__restrict__ qlo, int pieces, int64_t ngroups,
-                                                              int64_t ntotal, float *__restrict__ gmax, int64_t mstride) {
+                                                              int64_t ntotal, float *__restrict__ gmax, int64_t mstride, M... rm) {
     typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
     extern __shared__ __attribute__((aligned(16))) uint4 qs16[];      // [QT][2][pieces][64]
     const int per_q = pieces * 64;
@@ -388,6 +398,8 @@ __global__ __launch_bounds__(512) void scan16_groupmax_kernel(const uint4 *__res
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[q][t] = f32x4{0.f, 0.f, 0.f, 0.f};
         const uint4 *a = data16 + g * 4 * (int64_t)per_q + lane;
+        uint32_t mbyte = 0;
+        if constexpr (MASK) mbyte = row_mask_fetch(rm..., g * kGroupRows);
         // K outermost: a query fragment pair (hi, lo) is read from LDS once and used for the four row tiles (one LDS read per
         // four MFMAs; tile-outermost it is one per MFMA, which saturates the LDS port from two query tiles on)
         int kb = 0;
@@ -422,15 +434,18 @@ __global__ __launch_bounds__(512) void scan16_groupmax_kernel(const uint4 *__res
             }
         }
         const bool partial = (g + 1) * kGroupRows > ntotal;   // wave-uniform: only the last group
+        uint64_t mw = 0;
+        if constexpr (MASK) mw = row_mask_word(rm..., g * kGroupRows, mbyte) >> ((lane >> 4) * 4);
 #pragma unroll
         for (int q = 0; q < QT; ++q) {
-            float m = -FLT_MAX;
+            float m = MASK ? -INFINITY : -FLT_MAX;
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float s = acc[q][t][r];
-                    if (partial && g * kGroupRows + t * 16 + (lane >> 4) * 4 + r >= ntotal) s = -FLT_MAX;
+                    if constexpr (MASK) s = row_mask_score(mw, t * 16 + r, s);
+                    else if (partial && g * kGroupRows + t * 16 + (lane >> 4) * 4 + r >= ntotal) s = -FLT_MAX;
                     m = fmaxf(m, s);
                 }
             m = fmaxf(m, __shfl_xor(m, 16, 64));
@@ -448,10 +463,13 @@ __global__ __launch_bounds__(512) void scan16_groupmax_kernel(const uint4 *__res
 // The query fragments (hi + lo) live in registers (2 x PIECES x 4 VGPRs), the LDS holds nothing but the rings; a wave reads only what
 // it requested itself, so its own counted vmcnt orders every read (no workgroup barrier anywhere in the loop).  MFMA sequence per
 // accumulator = scan16_groupmax_kernel<1>'s (hi then lo, ascending K), so the group maxima are bit-identical to it.
-template <int PIECES>
+// MASK: the bitmap bytes of a group are loaded where the group's tile 0 is requested (right behind its piece 0), one load per lane.
+// The counted waits stay as they are: that load is one more in flight among the ring's, and loads retire in order, so a wait can
+// only become longer (by one piece, until the load has landed), never release a slot early.
+template <int PIECES, bool MASK, typename... M>
 __global__ __launch_bounds__(512) void scan16_ring_kernel(const uint4 *__restrict__ data16, const uint4 *__restrict__ qhi,
                                                           const uint4 *__restrict__ qlo, int64_t ngroups, int64_t ntotal,
-                                                          float *__restrict__ gmax, int64_t mstride) {
+                                                          float *__restrict__ gmax, int64_t mstride, M... rm) {
     typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) unsigned char ring_all[];
@@ -477,12 +495,16 @@ __global__ __launch_bounds__(512) void scan16_ring_kernel(const uint4 *__restric
     __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(reinterpret_cast<const char *>(data16)) + (G) * (int64_t)kGroupBytes, 0, \
                                       (int)kGroupBytes, 0x00020000)
     // prologue: tile 0 of the first group
+    uint32_t mbyte = 0, mbyte_next = 0;
     {
         const auto rs0 = IVR_GROUP_RSRC(g0);
 #pragma unroll
-        for (int kb = 0; kb < PIECES; ++kb)
+        for (int kb = 0; kb < PIECES; ++kb) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (__attribute__((address_space(3))) void *)(ring + kb * 1024), 16, voff, (unsigned)kb * 1024u, 0,
                                                      0);
+            if constexpr (MASK)
+                if (kb == 0) mbyte = row_mask_fetch(rm..., g0 * kGroupRows);
+        }
     }
     for (int64_t g = g0; g < ngroups; g += gstep) {
         const bool more = g + gstep < ngroups;
@@ -509,21 +531,30 @@ __global__ __launch_bounds__(512) void scan16_ring_kernel(const uint4 *__restric
                 if (t < 3)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)(ring + kb * 1024), 16, voff,
                                                              (unsigned)((t + 1) * PIECES + kb) * 1024u, 0, 0);
-                else if (more)
+                else if (more) {
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_next, (__attribute__((address_space(3))) void *)(ring + kb * 1024), 16, voff,
                                                              (unsigned)kb * 1024u, 0, 0);
+                    if constexpr (MASK)
+                        if (kb == 0) mbyte_next = row_mask_fetch(rm..., (g + gstep) * kGroupRows);
+                }
                 acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, bh[kb]), acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, bl[kb]), acc[t], 0, 0, 0);
             }
         }
         const bool partial = (g + 1) * kGroupRows > ntotal;   // wave-uniform: only the last group
-        float m = -FLT_MAX;
+        uint64_t mw = 0;
+        if constexpr (MASK) {
+            mw = row_mask_word(rm..., g * kGroupRows, mbyte) >> ((lane >> 4) * 4);
+            mbyte = mbyte_next;
+        }
+        float m = MASK ? -INFINITY : -FLT_MAX;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float sc = acc[t][r];
-                if (partial && g * kGroupRows + t * 16 + (lane >> 4) * 4 + r >= ntotal) sc = -FLT_MAX;
+                if constexpr (MASK) sc = row_mask_score(mw, t * 16 + r, sc);
+                else if (partial && g * kGroupRows + t * 16 + (lane >> 4) * 4 + r >= ntotal) sc = -FLT_MAX;
                 m = fmaxf(m, sc);
             }
         m = fmaxf(m, __shfl_xor(m, 16, 64));
@@ -583,12 +614,13 @@ struct PruneArgs {
     float acc_eps = 0.f;
 };
 
-template <bool TILES>
+// MASK: rows that are not allowed get key 0 (absent), like rows past ntotal
+template <bool TILES, bool MASK, typename... M>
 __global__ __launch_bounds__(256) void rescore_groups_kernel(const float *__restrict__ data,
                                                              const float *__restrict__ qtiled, int dp4,
                                                              int64_t ntotal, const uint32_t *__restrict__ sel,
                                                              int sel_stride, int ksel, int nq, uint64_t *__restrict__ cand,
-                                                             const int *__restrict__ skip, ListArgs la, PruneArgs pr = PruneArgs()) {
+                                                             const int *__restrict__ skip, ListArgs la, PruneArgs pr, M... rm) {
     constexpr int kRows = TILES ? 16 : kGroupRows, kSplit = TILES ? 1 : 4;
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -620,6 +652,8 @@ __global__ __launch_bounds__(256) void rescore_groups_kernel(const float *__rest
     const int per_tile = dp4 * 16, kchunks = dp4 >> 2;
     const float4 *b = reinterpret_cast<const float4 *>(qtiled) + (int64_t)(qs >> 4) * per_tile + lane;
     const float4 *a = reinterpret_cast<const float4 *>(data) + ((int64_t)g * kSplit + t) * per_tile + lane;
+    uint32_t mbyte = 0;
+    if constexpr (MASK) mbyte = row_mask_fetch(rm..., (int64_t)g * kRows + t * 16);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int kc = 0;
     for (; kc + 16 <= kchunks; kc += 16) {
@@ -643,13 +677,15 @@ __global__ __launch_bounds__(256) void rescore_groups_kernel(const float *__rest
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv.z, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bv.w, acc, 0, 0, 0);
     }
+    uint64_t mw = 0;
+    if constexpr (MASK) mw = row_mask_word(rm..., (int64_t)g * kRows + t * 16, mbyte);
     if ((lane & 15) == (qs & 15)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int rl = (lane >> 4) * 4 + r;
             const int64_t row = (int64_t)g * kRows + t * 16 + rl;
             uint64_t key = 0;
-            if (row < ntotal) key = ((uint64_t)ivr_f2ord(acc[r]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)row);
+            if (MASK ? ((mw >> rl) & 1ull) != 0 : row < ntotal) key = ((uint64_t)ivr_f2ord(acc[r]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)row);
             out[rl] = key;
         }
     }
@@ -1078,6 +1114,39 @@ int pick_qt(int nq) { return nq <= 16 ? 1 : nq <= 32 ? 2 : nq <= 48 ? 3 : 4; }
 // groups re-scored exactly behind the bf16 candidate scan: k plus slack for what the approximate ranking may displace
 int fast_groups(int k) { return k + std::max(22, k); }
 
+// The rows one search scans: the whole index, or for a filtered search the whole 256-row blocks that cover the allowed rows, treated as
+// an index of their own (the tiled layouts are contiguous per 16-row tile, so data and data16 are offset by whole blocks and the ids
+// shifted by the same rows; whole 256-row blocks keep the large-batch scan's block reads inside the allocation).  mask != NULL: the
+// masked kernels run, with the allowed rows in this view's numbering.
+struct View {
+    const float *data;
+    const uint4 *data16;
+    int64_t ntotal, ngroups, id_base;
+    const RowMask *mask;
+};
+
+View full_view(const ivr_index *x, int64_t id_base) {
+    return View{x->data, x->data16, x->ntotal, ivr_ceil_div(x->ntotal, kGroupRows), id_base, nullptr};
+}
+
+// filter (id = id_base + row) -> the view it scans and the mask of its allowed rows; a view of 0 rows when nothing is allowed
+View filtered_view(const ivr_index *x, int64_t id_base, const ivr_id_filter &f, RowMask &m) {
+    __int128 lo = f.lo, hi = f.hi;
+    if (f.bits) {                               // ids the bitmap covers: [0, nbits)
+        lo = std::max<__int128>(lo, 0);
+        hi = std::min<__int128>(hi, f.nbits);
+    }
+    const __int128 rlo = std::max<__int128>(lo - id_base, 0), rhi = std::min<__int128>(hi - id_base, x->ntotal);
+    if (rlo >= rhi) return View{x->data, x->data16, 0, 0, id_base, &m};
+    const int64_t b0 = (int64_t)rlo / 256 * 256, n = (int64_t)rhi - b0;
+    View v{x->data + b0 * x->dp, x->data16 ? x->data16 + (b0 / 16) * x->pieces * 64 : nullptr, n, ivr_ceil_div(n, kGroupRows), id_base + b0, &m};
+    m.lo = (int64_t)rlo - b0;
+    m.hi = n;
+    m.bits = f.bits;
+    m.bit0 = v.id_base;
+    return v;
+}
+
 // more than 64 queries: the tiled large-batch scan (search_scanq.hip) instead of chunks of 64 queries past the streamed index
 bool use_big(const ivr_index *x, int nq, int k) { return x->scan16 && x->bigq && nq > 64 && k <= kBigMaxK; }
 
@@ -1179,7 +1248,8 @@ int reserve_search(ivr_index *x, int nq, int k) {
 }
 
 template <int QT>
-void launch_scan(ivr_index *x, const float *qt, int64_t ngroups, int64_t mstride, hipStream_t s, const int *tile_flag = nullptr) {
+void launch_scan(ivr_index *x, const View &v, const float *qt, int64_t mstride, hipStream_t s, const int *tile_flag = nullptr) {
+    const int64_t ngroups = v.ngroups;
     const size_t lds = (size_t)QT * 16 * x->dp * 4;
     // 8 waves per workgroup share one staged query tile; size the grid so every CU holds as many
     // workgroups as the LDS allows and let each wave stride over the groups
@@ -1187,71 +1257,116 @@ void launch_scan(ivr_index *x, const float *qt, int64_t ngroups, int64_t mstride
     int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / std::max<size_t>(lds, 1)));
     int64_t grid = std::min<int64_t>(ivr_ceil_div(ngroups, nw), (int64_t)x->ctx->cu_count * per_cu);
     grid = std::max<int64_t>(grid, 1);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(scan_groupmax_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)lds);
+    (void)hipFuncSetAttribute(v.mask ? reinterpret_cast<const void *>(scan_groupmax_kernel<QT, true, RowMask>)
+                                     : reinterpret_cast<const void *>(scan_groupmax_kernel<QT, false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     // algorithmic bytes: every stored row once + the query tile + one maximum per (group, query)
-    IvrProf prof("scan_groupmax", s, (double)x->ntotal * x->dp * 4 + (double)QT * 16 * x->dp * 4 + (double)ngroups * QT * 16 * 4,
+    IvrProf prof("scan_groupmax", s, (double)v.ntotal * x->dp * 4 + (double)QT * 16 * x->dp * 4 + (double)ngroups * QT * 16 * 4,
                  tile_flag != nullptr);      // behind the bf16 candidate scan it is the predicated fallback and normally exits at once
-    hipLaunchKernelGGL(scan_groupmax_kernel<QT>, dim3((unsigned)grid), dim3(threads), lds, s, x->data, qt, x->dp4, ngroups,
-                       x->ntotal, x->gmax, mstride, tile_flag);
+    if (v.mask)
+        hipLaunchKernelGGL((scan_groupmax_kernel<QT, true, RowMask>), dim3((unsigned)grid), dim3(threads), lds, s, v.data, qt, x->dp4, ngroups, v.ntotal,
+                           x->gmax, mstride, tile_flag, *v.mask);
+    else
+        hipLaunchKernelGGL((scan_groupmax_kernel<QT, false>), dim3((unsigned)grid), dim3(threads), lds, s, v.data, qt, x->dp4, ngroups,
+                           v.ntotal, x->gmax, mstride, tile_flag);
+}
+
+void launch_scan_qt(ivr_index *x, const View &v, int qt, const float *qtile, int64_t mstride, hipStream_t s, const int *tile_flag = nullptr) {
+    switch (qt) {
+        case 1: launch_scan<1>(x, v, qtile, mstride, s, tile_flag); break;
+        case 2: launch_scan<2>(x, v, qtile, mstride, s, tile_flag); break;
+        case 3: launch_scan<3>(x, v, qtile, mstride, s, tile_flag); break;
+        default: launch_scan<4>(x, v, qtile, mstride, s, tile_flag); break;
+    }
 }
 
 template <int QT>
-void launch_scan16(ivr_index *x, int64_t tile0, int64_t ngroups, int64_t mstride, hipStream_t s) {
+void launch_scan16(ivr_index *x, const View &v, int64_t tile0, int64_t mstride, hipStream_t s) {
+    const int64_t ngroups = v.ngroups;
     const size_t lds = (size_t)QT * 2 * x->pieces * 1024;
     const int threads = 512, nw = threads / 64;
     int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / std::max<size_t>(lds, 1)));
     int64_t grid = std::min<int64_t>(ivr_ceil_div(ngroups, nw), (int64_t)x->ctx->cu_count * per_cu);
     grid = std::max<int64_t>(grid, 1);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(scan16_groupmax_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
+    (void)hipFuncSetAttribute(v.mask ? reinterpret_cast<const void *>(scan16_groupmax_kernel<QT, true, RowMask>)
+                                     : reinterpret_cast<const void *>(scan16_groupmax_kernel<QT, false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     // algorithmic bytes: the bf16 copy of every stored row once + the split query tiles + one maximum per (group, query)
-    IvrProf prof("scan16_groupmax", s, (double)x->ntotal * x->pieces * 64 + (double)QT * 2 * x->pieces * 1024 + (double)ngroups * QT * 16 * 4);
-    hipLaunchKernelGGL(scan16_groupmax_kernel<QT>, dim3((unsigned)grid), dim3(threads), lds, s, x->data16, x->q16hi + tile0 * x->pieces * 64,
-                       x->q16lo + tile0 * x->pieces * 64, x->pieces, ngroups, x->ntotal, x->gmax, mstride);
+    IvrProf prof("scan16_groupmax", s, (double)v.ntotal * x->pieces * 64 + (double)QT * 2 * x->pieces * 1024 + (double)ngroups * QT * 16 * 4);
+    if (v.mask)
+        hipLaunchKernelGGL((scan16_groupmax_kernel<QT, true, RowMask>), dim3((unsigned)grid), dim3(threads), lds, s, v.data16,
+                           x->q16hi + tile0 * x->pieces * 64, x->q16lo + tile0 * x->pieces * 64, x->pieces, ngroups, v.ntotal, x->gmax, mstride,
+                           *v.mask);
+    else
+        hipLaunchKernelGGL((scan16_groupmax_kernel<QT, false>), dim3((unsigned)grid), dim3(threads), lds, s, v.data16, x->q16hi + tile0 * x->pieces * 64,
+                           x->q16lo + tile0 * x->pieces * 64, x->pieces, ngroups, v.ntotal, x->gmax, mstride);
 }
 
 // at most 16 queries and a piece count the ring kernel is built for: stream the index through the LDS-DMA rings
 template <int PIECES>
-void launch_scan16_ring(ivr_index *x, int64_t tile0, int64_t ngroups, int64_t mstride, hipStream_t s) {
+void launch_scan16_ring(ivr_index *x, const View &v, int64_t tile0, int64_t mstride, hipStream_t s) {
+    const int64_t ngroups = v.ngroups;
     const int threads = 512, nw = threads / 64;
     const size_t lds = (size_t)nw * PIECES * 1024;
     // one workgroup per CU (its 8 rings already keep PIECES x 8 KiB in flight); groups are dealt round-robin to the waves of the grid
     int64_t grid = std::max<int64_t>(1, std::min<int64_t>(ivr_ceil_div(ngroups, nw), (int64_t)x->ctx->cu_count * (lds <= 64 * 1024 ? 2 : 1)));
-    (void)ivr_func_max_lds(reinterpret_cast<const void *>(scan16_ring_kernel<PIECES>), (int)lds);
-    IvrProf prof("scan16_groupmax", s, (double)x->ntotal * x->pieces * 64 + (double)2 * x->pieces * 1024 + (double)ngroups * 16 * 4);
-    hipLaunchKernelGGL(scan16_ring_kernel<PIECES>, dim3((unsigned)grid), dim3(threads), lds, s, x->data16, x->q16hi + tile0 * x->pieces * 64,
-                       x->q16lo + tile0 * x->pieces * 64, ngroups, x->ntotal, x->gmax, mstride);
+    (void)ivr_func_max_lds(v.mask ? reinterpret_cast<const void *>(scan16_ring_kernel<PIECES, true, RowMask>)
+                                  : reinterpret_cast<const void *>(scan16_ring_kernel<PIECES, false>), (int)lds);
+    IvrProf prof("scan16_groupmax", s, (double)v.ntotal * x->pieces * 64 + (double)2 * x->pieces * 1024 + (double)ngroups * 16 * 4);
+    if (v.mask)
+        hipLaunchKernelGGL((scan16_ring_kernel<PIECES, true, RowMask>), dim3((unsigned)grid), dim3(threads), lds, s, v.data16,
+                           x->q16hi + tile0 * x->pieces * 64, x->q16lo + tile0 * x->pieces * 64, ngroups, v.ntotal, x->gmax, mstride, *v.mask);
+    else
+        hipLaunchKernelGGL((scan16_ring_kernel<PIECES, false>), dim3((unsigned)grid), dim3(threads), lds, s, v.data16, x->q16hi + tile0 * x->pieces * 64,
+                           x->q16lo + tile0 * x->pieces * 64, ngroups, v.ntotal, x->gmax, mstride);
 }
 
 // the bf16 candidate scan of one chunk of at most 64 queries (16*qt query columns from tile tile0 on): the LDS-DMA ring for at most
 // 16 queries when it is built for the piece count, else the register-streamed kernel
-void launch_fast_scan(ivr_index *x, int qt, int64_t tile0, int64_t ngroups, int64_t mstride, hipStream_t s) {
+void launch_fast_scan(ivr_index *x, const View &v, int qt, int64_t tile0, int64_t mstride, hipStream_t s) {
     switch (qt) {
         case 1:
-            if (x->ring && x->pieces == 16) launch_scan16_ring<16>(x, tile0, ngroups, mstride, s);
-            else if (x->ring && x->pieces == 12) launch_scan16_ring<12>(x, tile0, ngroups, mstride, s);
-            else if (x->ring && x->pieces == 8) launch_scan16_ring<8>(x, tile0, ngroups, mstride, s);
-            else launch_scan16<1>(x, tile0, ngroups, mstride, s);
+            if (x->ring && x->pieces == 16) launch_scan16_ring<16>(x, v, tile0, mstride, s);
+            else if (x->ring && x->pieces == 12) launch_scan16_ring<12>(x, v, tile0, mstride, s);
+            else if (x->ring && x->pieces == 8) launch_scan16_ring<8>(x, v, tile0, mstride, s);
+            else launch_scan16<1>(x, v, tile0, mstride, s);
             break;
-        case 2: launch_scan16<2>(x, tile0, ngroups, mstride, s); break;
-        case 3: launch_scan16<3>(x, tile0, ngroups, mstride, s); break;
-        default: launch_scan16<4>(x, tile0, ngroups, mstride, s); break;
+        case 2: launch_scan16<2>(x, v, tile0, mstride, s); break;
+        case 3: launch_scan16<3>(x, v, tile0, mstride, s); break;
+        default: launch_scan16<4>(x, v, tile0, mstride, s); break;
     }
 }
 
 template <int QT>
-void launch_scan_list(ivr_index *x, const float *qt, int64_t ngroups, int64_t mstride, float *gmax, const int *nlist, const int *list,
+void launch_scan_list(ivr_index *x, const View &v, const float *qt, int64_t mstride, float *gmax, const int *nlist, const int *list,
                       hipStream_t s) {
+    const int64_t ngroups = v.ngroups;
     const size_t lds = (size_t)QT * 16 * x->dp * 4;
     const int threads = 512, nw = threads / 64;
     int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / std::max<size_t>(lds, 1)));
     int64_t grid = std::max<int64_t>(1, std::min<int64_t>(ivr_ceil_div(ngroups, nw), (int64_t)x->ctx->cu_count * per_cu));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(scan_groupmax_list_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
+    (void)hipFuncSetAttribute(v.mask ? reinterpret_cast<const void *>(scan_groupmax_list_kernel<QT, true, RowMask>)
+                                     : reinterpret_cast<const void *>(scan_groupmax_list_kernel<QT, false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     IvrProf prof("scan_groupmax_list", s, 0.0, true);      // normally nothing is listed and every workgroup exits at once
-    hipLaunchKernelGGL(scan_groupmax_list_kernel<QT>, dim3((unsigned)grid), dim3(threads), lds, s, x->data, qt, x->dp4, ngroups, x->ntotal,
-                       gmax, mstride, nlist, list);
+    if (v.mask)
+        hipLaunchKernelGGL((scan_groupmax_list_kernel<QT, true, RowMask>), dim3((unsigned)grid), dim3(threads), lds, s, v.data, qt, x->dp4, ngroups, v.ntotal,
+                           gmax, mstride, nlist, list, *v.mask);
+    else
+        hipLaunchKernelGGL((scan_groupmax_list_kernel<QT, false>), dim3((unsigned)grid), dim3(threads), lds, s, v.data, qt, x->dp4, ngroups, v.ntotal,
+                           gmax, mstride, nlist, list);
+}
+
+// pass 3 of the top-k search: the plain or the masked re-score
+template <bool TILES>
+void launch_rescore(const View &v, unsigned blocks, hipStream_t s, const float *qtiled, int dp4, const uint32_t *sel, int sel_stride, int ksel,
+                    int nq, uint64_t *cand, const int *skip, const ListArgs &la, const PruneArgs &pr = PruneArgs()) {
+    if (v.mask)
+        hipLaunchKernelGGL((rescore_groups_kernel<TILES, true, RowMask>), dim3(blocks), dim3(256), 0, s, v.data, qtiled, dp4, v.ntotal, sel, sel_stride, ksel,
+                           nq, cand, skip, la, pr, *v.mask);
+    else
+        hipLaunchKernelGGL((rescore_groups_kernel<TILES, false>), dim3(blocks), dim3(256), 0, s, v.data, qtiled, dp4, v.ntotal, sel, sel_stride, ksel, nq,
+                           cand, skip, la, pr);
 }
 
 // One chunk (<= kBigChunk queries, already tiled at tile q0 / 16) of a large batch:
@@ -1259,27 +1374,28 @@ void launch_scan_list(ivr_index *x, const float *qt, int64_t ngroups, int64_t ms
 //   best tiles always lie inside the kp+1 best blocks: the argument of DESIGN.md section 4 with tiles for rows) -> exact float32
 //   re-score of kp tiles -> final selection, which also verifies the approximate ranking per query and lists the queries that
 //   fail -> list-driven exact pass (four launches that exit at once when the list is empty; no host round trip).
-int search_big(ivr_index *x, int q0, int nqc, int k, int64_t id_base, float *D, int64_t *I, hipStream_t s) {
+int search_big(ivr_index *x, const View &v, int q0, int nqc, int k, float *D, int64_t *I, hipStream_t s) {
+    const int64_t id_base = v.id_base;
     const int kp = fast_groups(k), ksel2 = kp + 1;
     const int qpad = (int)ivr_round_up(nqc, 256);
     const int64_t cap256 = ivr_round_up(x->cap, 256);
     const int64_t tstride = ivr_round_up(cap256 / 16, 64), bstride = ivr_round_up(cap256 / 128, 64);
-    const int64_t nblk128 = ivr_ceil_div(x->ntotal, 128), ntiles = ivr_ceil_div(x->ntotal, 16);
-    const int64_t ngroups = ivr_ceil_div(x->ntotal, kGroupRows), mstride = ivr_round_up(x->cap / kGroupRows, 64);
+    const int64_t nblk128 = ivr_ceil_div(v.ntotal, 128), ntiles = ivr_ceil_div(v.ntotal, 16);
+    const int64_t mstride = ivr_round_up(x->cap / kGroupRows, 64);
     const float *qtile = x->qtiled + (int64_t)(q0 / 16) * 16 * x->dp;
     int *ok = x->okq, *nfail = x->okq + kBigChunk, *flist = x->okq + kBigChunk + 4;
     ScanQArgs a;
-    a.data16 = x->data16;
+    a.data16 = v.data16;
     a.q16 = x->q16hi + (int64_t)(q0 / 16) * x->pieces * 64;
     a.pieces = x->pieces;
     a.qblocks = qpad / 256;
-    a.ntotal = x->ntotal;
-    a.nblocks = ivr_ceil_div(x->ntotal, 256);
+    a.ntotal = v.ntotal;
+    a.nblocks = ivr_ceil_div(v.ntotal, 256);
     a.tmax = x->tmax;
     a.tstride = tstride;
     a.bmax = x->bmax;
     a.bstride = bstride;
-    int rc = ivr_launch_scanq(x->ctx, a, s);
+    int rc = ivr_launch_scanq(x->ctx, a, s, v.mask);
     if (rc != IVR_OK) return rc;
     {
         SrcGroupMax sb{x->bmax, bstride, nblk128};
@@ -1311,8 +1427,8 @@ int search_big(ivr_index *x, int q0, int nqc, int k, int64_t id_base, float *D, 
             pr.maxdelta_bits = x->maxdelta;
             pr.acc_eps = (float)x->dp * 1.2e-7f;
         }
-        hipLaunchKernelGGL(rescore_groups_kernel<true>, dim3((unsigned)ivr_ceil_div(waves, 4)), dim3(256), 0, s, x->data, qtile, x->dp4, x->ntotal,
-                           x->sel, ksel2, kp, nqc, x->cand, (const int *)nullptr, ListArgs(), pr);
+        launch_rescore<true>(v, (unsigned)ivr_ceil_div(waves, 4), s, qtile, x->dp4, x->sel, ksel2, kp, nqc, x->cand, (const int *)nullptr, ListArgs(),
+                             pr);
         IVR_LAUNCH_CHECK();
     }
     {
@@ -1342,12 +1458,13 @@ int search_big(ivr_index *x, int q0, int nqc, int k, int64_t id_base, float *D, 
     float *gmax = x->tmax;
     const int qt_max = (int)std::max<int64_t>(1, std::min<int64_t>(4, (128 * 1024) / ((int64_t)16 * x->dp * 4)));
     switch (qt_max) {
-        case 1: launch_scan_list<1>(x, qtile, ngroups, mstride, gmax, nfail, flist, s); break;
-        case 2: launch_scan_list<2>(x, qtile, ngroups, mstride, gmax, nfail, flist, s); break;
-        case 3: launch_scan_list<3>(x, qtile, ngroups, mstride, gmax, nfail, flist, s); break;
-        default: launch_scan_list<4>(x, qtile, ngroups, mstride, gmax, nfail, flist, s); break;
+        case 1: launch_scan_list<1>(x, v, qtile, mstride, gmax, nfail, flist, s); break;
+        case 2: launch_scan_list<2>(x, v, qtile, mstride, gmax, nfail, flist, s); break;
+        case 3: launch_scan_list<3>(x, v, qtile, mstride, gmax, nfail, flist, s); break;
+        default: launch_scan_list<4>(x, v, qtile, mstride, gmax, nfail, flist, s); break;
     }
     IVR_LAUNCH_CHECK();
+    const int64_t ngroups = v.ngroups;
     {
         SrcGroupMax sg{gmax, mstride, ngroups};
         IvrProf prof("select_groups", s, 0.0, true);
@@ -1358,8 +1475,7 @@ int search_big(ivr_index *x, int q0, int nqc, int k, int64_t id_base, float *D, 
     {
         const int64_t waves = (int64_t)nqc * k;
         IvrProf prof("rescore_groups", s, 0.0, true);
-        hipLaunchKernelGGL(rescore_groups_kernel<false>, dim3((unsigned)waves), dim3(256), 0, s, x->data, qtile, x->dp4, x->ntotal, x->sel, k, k, nqc,
-                           x->cand, (const int *)nullptr, la);
+        launch_rescore<false>(v, (unsigned)waves, s, qtile, x->dp4, x->sel, k, k, nqc, x->cand, (const int *)nullptr, la);
         IVR_LAUNCH_CHECK();
     }
     {
@@ -1494,9 +1610,13 @@ __device__ __forceinline__ f32x4 range_score_tile(const float4 *__restrict__ a, 
 // The 64 rows of group g against query q of the chunk (qtile = the chunk's first query tile).  In the lanes with (lane & 15) ==
 // (q & 15), acc[t][r] = score of row 64 g + 16 t + 4 (lane >> 4) + r.  Returns the hit mask (bit i: row 64 g + i exists and scores
 // > radius), the same in every lane.
+// MASK: rows that are not allowed are never hits.
+template <bool MASK = false, typename... M>
 __device__ __forceinline__ uint64_t range_group_scores(const float *__restrict__ data, const float *__restrict__ qtile, int dp4,
-                                                       int64_t ntotal, uint32_t g, int q, float radius, f32x4 (&acc)[4]) {
+                                                       int64_t ntotal, uint32_t g, int q, float radius, f32x4 (&acc)[4], const M &...rm) {
     const int lane = threadIdx.x & 63;
+    uint32_t mbyte = 0;
+    if constexpr (MASK) mbyte = row_mask_fetch(rm..., (int64_t)g * kGroupRows);
     const int per_tile = dp4 * 16, kchunks = dp4 >> 2;
     const float4 *b = reinterpret_cast<const float4 *>(qtile) + (int64_t)(q >> 4) * per_tile + lane;
     const bool mine = (lane & 15) == (q & 15);
@@ -1504,11 +1624,23 @@ __device__ __forceinline__ uint64_t range_group_scores(const float *__restrict__
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         acc[t] = range_score_tile(reinterpret_cast<const float4 *>(data) + ((int64_t)g * 4 + t) * per_tile + lane, b, kchunks);
+        if constexpr (!MASK) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int rl = t * 16 + (lane >> 4) * 4 + r;
-            if (mine && (int64_t)g * kGroupRows + rl < ntotal && acc[t][r] > radius) m |= 1ull << rl;
+            for (int r = 0; r < 4; ++r) {
+                const int rl = t * 16 + (lane >> 4) * 4 + r;
+                if (mine && (int64_t)g * kGroupRows + rl < ntotal && acc[t][r] > radius) m |= 1ull << rl;
+            }
         }
+    }
+    if constexpr (MASK) {
+        const uint64_t mw = row_mask_word(rm..., (int64_t)g * kGroupRows, mbyte);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int rl = t * 16 + (lane >> 4) * 4 + r;
+                if (mine && ((mw >> rl) & 1ull) && acc[t][r] > radius) m |= 1ull << rl;
+            }
     }
     // the query's column lives in lanes c, c + 16, c + 32, c + 48 (c = q & 15), each with 16 of the 64 rows
     uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
@@ -1522,10 +1654,11 @@ __device__ __forceinline__ uint64_t range_group_scores(const float *__restrict__
 }
 
 // Pass 3: persistent grid of 4-wave workgroups; wave w of the grid takes the pairs w, w + waves, ... in (query, group) order
+template <bool MASK, typename... M>
 __global__ __launch_bounds__(256) void range_rescore_kernel(const float *__restrict__ data, const float *__restrict__ qtile, int dp4,
                                                             int64_t ntotal, float radius, int nqc, const uint32_t *__restrict__ cand,
                                                             int64_t cstride, const uint32_t *__restrict__ ncand, uint64_t *__restrict__ mask,
-                                                            uint32_t *__restrict__ hits) {
+                                                            uint32_t *__restrict__ hits, M... rm) {
     __shared__ int64_t pre[65];
     range_pair_prefix(ncand, nqc, pre);
     __syncthreads();
@@ -1536,7 +1669,7 @@ __global__ __launch_bounds__(256) void range_rescore_kernel(const float *__restr
         const int q = range_pair_query(pre, nqc, p);
         const int64_t at = (int64_t)q * cstride + (p - pre[q]);
         f32x4 acc[4];
-        const uint64_t m = range_group_scores(data, qtile, dp4, ntotal, cand[at], q, radius, acc);
+        const uint64_t m = range_group_scores<MASK>(data, qtile, dp4, ntotal, cand[at], q, radius, acc, rm...);
         if (lane == 0) {
             mask[at] = m;
             hits[at] = (uint32_t)__popcll(m);
@@ -1563,7 +1696,8 @@ __global__ __launch_bounds__(1024) void range_offsets_kernel(const uint32_t *__r
     if (threadIdx.x == 0) nhits[q] = base;
 }
 
-// Pass 4b, persistent grid like pass 3.  Query i of the chunk starts at output position qb[i] = (running total before the chunk) +
+// Pass 4b, persistent grid like pass 3 (also behind a filtered search: it emits only bits of the hit masks, which the masked pass 3
+// has restricted to the allowed rows).  Query i of the chunk starts at output position qb[i] = (running total before the chunk) +
 // hits of queries 0 .. i-1; workgroup 0 writes lims[q0 .. q0 + nqc] and the new running total.  The total ping-pongs between two
 // slots (read total[parity], write total[parity ^ 1]) so that no workgroup of this launch can read a value written by it; the first
 // chunk starts from 0.  Pairs with hits are re-scored (same function as pass 3: the same scores, the same mask) and each hit is
@@ -1786,17 +1920,16 @@ int ivr_index_reserve_search(ivr_index *x, int max_nq, int max_k) {
     return reserve_search(x, max_nq, max_k);
 }
 
-int ivr_index_search(ivr_index *x, const float *q, int nq, int k, int normalize_q, int64_t id_base, float *D, int64_t *I,
-                     ivr_stream stream) {
-    IVR_REQUIRE(x && q && D && I, "ivr_index_search: NULL argument");
-    IVR_REQUIRE(nq >= 1, "ivr_index_search: nq=%d", nq);
-    IVR_REQUIRE(k >= 1 && k <= IVR_MAX_K, "ivr_index_search: k=%d outside [1,%d]", k, IVR_MAX_K);
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    hipStream_t s = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+
+// ivr_index_search over the rows of view v (the whole index, or the part a filter allows); the caller holds x->mu
+int search_view(ivr_index *x, const View &v, const float *q, int nq, int k, int normalize_q, float *D, int64_t *I, hipStream_t s) {
+    const int64_t id_base = v.id_base;
     int rc = reserve_search(x, nq, k);
     if (rc != IVR_OK) return rc;
-    const int64_t ngroups = ivr_ceil_div(x->ntotal, kGroupRows);
+    const int64_t ngroups = v.ngroups;
     const int64_t mstride = ivr_round_up(x->cap / kGroupRows, 64);
     // queries -> tiled layout (normalised on the way when asked: N2 on the query side, core.py:875)
     {
@@ -1816,7 +1949,7 @@ int ivr_index_search(ivr_index *x, const float *q, int nq, int k, int normalize_
         // large batch: the index is read once per kBigChunk queries instead of once per 64
         for (int q0 = 0; q0 < nq; q0 += kBigChunk) {
             const int nqc = std::min(kBigChunk, nq - q0);
-            rc = search_big(x, q0, nqc, k, id_base, D, I, s);
+            rc = search_big(x, v, q0, nqc, k, D, I, s);
             if (rc != IVR_OK) return rc;
             x->last_nqc = nqc;
         }
@@ -1828,12 +1961,7 @@ int ivr_index_search(ivr_index *x, const float *q, int nq, int k, int normalize_
     int *ok = x->okflag, *tile_flag = x->okflag ? x->okflag + 64 : nullptr;
     auto exact_pass = [&](const float *qtile, int nqc, int qt, int q0, const int *flags, const int *skip) -> int {
         if (ngroups > 0) {
-            switch (qt) {
-                case 1: launch_scan<1>(x, qtile, ngroups, mstride, s, flags); break;
-                case 2: launch_scan<2>(x, qtile, ngroups, mstride, s, flags); break;
-                case 3: launch_scan<3>(x, qtile, ngroups, mstride, s, flags); break;
-                default: launch_scan<4>(x, qtile, ngroups, mstride, s, flags); break;
-            }
+            launch_scan_qt(x, v, qt, qtile, mstride, s, flags);
             IVR_LAUNCH_CHECK();
         }
         SrcGroupMax sg{x->gmax, mstride, ngroups};
@@ -1847,8 +1975,7 @@ int ivr_index_search(ivr_index *x, const float *q, int nq, int k, int normalize_
         // rescore reads query tile (q >> 4) relative to the chunk's first tile
         {
             IvrProf prof("rescore_groups", s, (double)waves * kGroupRows * x->dp * 4, true);
-            hipLaunchKernelGGL(rescore_groups_kernel<false>, dim3((unsigned)waves), dim3(256), 0, s, x->data, qtile, x->dp4,
-                               x->ntotal, x->sel, ksel, ksel, nqc, x->cand, skip, ListArgs());
+            launch_rescore<false>(v, (unsigned)waves, s, qtile, x->dp4, x->sel, ksel, ksel, nqc, x->cand, skip, ListArgs());
         }
         IVR_LAUNCH_CHECK();
         SrcKeys sk{x->cand, (int64_t)ksel * kGroupRows};
@@ -1869,7 +1996,7 @@ int ivr_index_search(ivr_index *x, const float *q, int nq, int k, int normalize_
             continue;
         }
         x->last_nqc = nqc;
-        launch_fast_scan(x, qt, q0 / 16, ngroups, mstride, s);
+        launch_fast_scan(x, v, qt, q0 / 16, mstride, s);
         IVR_LAUNCH_CHECK();
         const int ksel2 = kp + 1;
         SrcGroupMax sg{x->gmax, mstride, ngroups};
@@ -1883,8 +2010,7 @@ int ivr_index_search(ivr_index *x, const float *q, int nq, int k, int normalize_
         const int64_t waves = (int64_t)nqc * kp;
         {
             IvrProf prof("rescore_groups", s, (double)waves * kGroupRows * x->dp * 4, true);
-            hipLaunchKernelGGL(rescore_groups_kernel<false>, dim3((unsigned)waves), dim3(256), 0, s, x->data, qtile, x->dp4,
-                               x->ntotal, x->sel, ksel2, kp, nqc, x->cand, (const int *)nullptr, ListArgs());
+            launch_rescore<false>(v, (unsigned)waves, s, qtile, x->dp4, x->sel, ksel2, kp, nqc, x->cand, (const int *)nullptr, ListArgs());
         }
         IVR_LAUNCH_CHECK();
         {
@@ -1913,34 +2039,11 @@ int ivr_index_search(ivr_index *x, const float *q, int nq, int k, int normalize_
     return IVR_OK;
 }
 
-int ivr_index_scan_stats(ivr_index *x, int *out) {
-    IVR_REQUIRE(x && out, "ivr_index_scan_stats: NULL argument");
-    std::lock_guard<std::mutex> lk(x->mu);
-    out[0] = x->scan16 ? 1 : 0;
-    out[1] = 0;
-    if (!x->scan16) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    IVR_HIP(hipDeviceSynchronize());
-    if (x->last_big) {       // large-batch scan: the length of the failure list of the last chunk
-        IVR_HIP(hipMemcpy(&out[1], x->okq + kBigChunk, sizeof(int), hipMemcpyDeviceToHost));
-        return IVR_OK;
-    }
-    int ok[64];
-    IVR_HIP(hipMemcpy(ok, x->okflag, sizeof(ok), hipMemcpyDeviceToHost));
-    for (int i = 0; i < x->last_nqc; ++i) out[1] += ok[i] == 0;
-    return IVR_OK;
-}
-
-int ivr_index_range_search(ivr_index *x, const float *q, int nq, float radius, int normalize_q, int64_t id_base, int64_t *lims,
-                           float *D, int64_t *I, int64_t cap, ivr_stream stream) {
-    IVR_REQUIRE(x && q && lims && D && I, "ivr_index_range_search: NULL argument");
-    IVR_REQUIRE(nq >= 1, "ivr_index_range_search: nq=%d", nq);
-    IVR_REQUIRE(cap >= 0, "ivr_index_range_search: cap=%lld", (long long)cap);
-    IVR_REQUIRE(!(radius != radius), "ivr_index_range_search: radius is NaN");
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t ngroups = ivr_ceil_div(x->ntotal, kGroupRows);
+// ivr_index_range_search over the rows of view v; the caller holds x->mu
+int range_search_view(ivr_index *x, const View &v, const float *q, int nq, float radius, int normalize_q, int64_t *lims, float *D, int64_t *I,
+                      int64_t cap, hipStream_t s) {
+    const int64_t id_base = v.id_base;
+    const int64_t ngroups = v.ngroups;
     if (ngroups == 0) {
         IVR_HIP(hipMemsetAsync(lims, 0, (size_t)(nq + 1) * sizeof(int64_t), s));
         return IVR_OK;
@@ -1965,16 +2068,8 @@ int ivr_index_range_search(ivr_index *x, const float *q, int nq, float radius, i
         const int nqc = std::min(chunk, nq - q0);
         const int qt = pick_qt(nqc);
         const float *qtile = x->qtiled + (int64_t)(q0 / 16) * 16 * x->dp;
-        if (fast) {
-            launch_fast_scan(x, qt, q0 / 16, ngroups, mstride, s);
-        } else {
-            switch (qt) {
-                case 1: launch_scan<1>(x, qtile, ngroups, mstride, s); break;
-                case 2: launch_scan<2>(x, qtile, ngroups, mstride, s); break;
-                case 3: launch_scan<3>(x, qtile, ngroups, mstride, s); break;
-                default: launch_scan<4>(x, qtile, ngroups, mstride, s); break;
-            }
-        }
+        if (fast) launch_fast_scan(x, v, qt, q0 / 16, mstride, s);
+        else launch_scan_qt(x, v, qt, qtile, mstride, s);
         IVR_LAUNCH_CHECK();
         {
             IvrProf prof("range_candidates", s, (double)nqc * ngroups * 4, true);
@@ -1984,8 +2079,12 @@ int ivr_index_range_search(ivr_index *x, const float *q, int nq, float radius, i
         }
         {
             IvrProf prof("range_rescore", s, 0.0, true);     // the pairs are counted on the device
-            hipLaunchKernelGGL(range_rescore_kernel, dim3(pgrid), dim3(256), 0, s, x->data, qtile, x->dp4, x->ntotal, radius, nqc,
-                               x->rs_cand, cstride, ncand, x->rs_mask, x->rs_off);
+            if (v.mask)
+                hipLaunchKernelGGL((range_rescore_kernel<true, RowMask>), dim3(pgrid), dim3(256), 0, s, v.data, qtile, x->dp4, v.ntotal, radius, nqc,
+                                   x->rs_cand, cstride, ncand, x->rs_mask, x->rs_off, *v.mask);
+            else
+                hipLaunchKernelGGL((range_rescore_kernel<false>), dim3(pgrid), dim3(256), 0, s, v.data, qtile, x->dp4, v.ntotal, radius, nqc,
+                                   x->rs_cand, cstride, ncand, x->rs_mask, x->rs_off);
             IVR_LAUNCH_CHECK();
         }
         {
@@ -1995,13 +2094,77 @@ int ivr_index_range_search(ivr_index *x, const float *q, int nq, float radius, i
         }
         {
             IvrProf prof("range_write", s, 0.0, true);
-            hipLaunchKernelGGL(range_write_kernel, dim3(pgrid), dim3(256), 0, s, x->data, qtile, x->dp4, x->ntotal, radius, nqc, q0,
+            hipLaunchKernelGGL(range_write_kernel, dim3(pgrid), dim3(256), 0, s, v.data, qtile, x->dp4, v.ntotal, radius, nqc, q0,
                                x->rs_cand, cstride, ncand, x->rs_mask, x->rs_off, nhits, total, c == 0 ? 1 : 0, c & 1, lims, D, I, cap,
                                id_base);
             IVR_LAUNCH_CHECK();
         }
     }
     return IVR_OK;
+}
+
+int check_filter(const ivr_id_filter *f, const char *what) {
+    IVR_REQUIRE(!f || f->nbits >= 0, "%s: filter nbits=%lld < 0", what, (long long)(f ? f->nbits : 0));
+    return IVR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ivr_index_search(ivr_index *x, const float *q, int nq, int k, int normalize_q, int64_t id_base, float *D, int64_t *I,
+                     ivr_stream stream) {
+    return ivr_index_search_filtered(x, q, nq, k, normalize_q, id_base, nullptr, D, I, stream);
+}
+
+int ivr_index_search_filtered(ivr_index *x, const float *q, int nq, int k, int normalize_q, int64_t id_base, const ivr_id_filter *filter,
+                              float *D, int64_t *I, ivr_stream stream) {
+    IVR_REQUIRE(x && q && D && I, "ivr_index_search: NULL argument");
+    IVR_REQUIRE(nq >= 1, "ivr_index_search: nq=%d", nq);
+    IVR_REQUIRE(k >= 1 && k <= IVR_MAX_K, "ivr_index_search: k=%d outside [1,%d]", k, IVR_MAX_K);
+    if (check_filter(filter, "ivr_index_search_filtered") != IVR_OK) return IVR_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(x->mu);
+    IVR_HIP(hipSetDevice(x->ctx->device));
+    RowMask m;
+    const View v = filter ? filtered_view(x, id_base, *filter, m) : full_view(x, id_base);
+    return search_view(x, v, q, nq, k, normalize_q, D, I, (hipStream_t)stream);
+}
+
+int ivr_index_scan_stats(ivr_index *x, int *out) {
+    IVR_REQUIRE(x && out, "ivr_index_scan_stats: NULL argument");
+    std::lock_guard<std::mutex> lk(x->mu);
+    out[0] = x->scan16 ? 1 : 0;
+    out[1] = 0;
+    if (!x->scan16) return IVR_OK;
+    IVR_HIP(hipSetDevice(x->ctx->device));
+    IVR_HIP(hipDeviceSynchronize());
+    if (x->last_big) {       // large-batch scan: the length of the failure list of the last chunk
+        IVR_HIP(hipMemcpy(&out[1], x->okq + kBigChunk, sizeof(int), hipMemcpyDeviceToHost));
+        return IVR_OK;
+    }
+    int ok[64];
+    IVR_HIP(hipMemcpy(ok, x->okflag, sizeof(ok), hipMemcpyDeviceToHost));
+    for (int i = 0; i < x->last_nqc; ++i) out[1] += ok[i] == 0;
+    return IVR_OK;
+}
+
+int ivr_index_range_search(ivr_index *x, const float *q, int nq, float radius, int normalize_q, int64_t id_base, int64_t *lims,
+                           float *D, int64_t *I, int64_t cap, ivr_stream stream) {
+    return ivr_index_range_search_filtered(x, q, nq, radius, normalize_q, id_base, nullptr, lims, D, I, cap, stream);
+}
+
+int ivr_index_range_search_filtered(ivr_index *x, const float *q, int nq, float radius, int normalize_q, int64_t id_base,
+                                    const ivr_id_filter *filter, int64_t *lims, float *D, int64_t *I, int64_t cap, ivr_stream stream) {
+    IVR_REQUIRE(x && q && lims && D && I, "ivr_index_range_search: NULL argument");
+    IVR_REQUIRE(nq >= 1, "ivr_index_range_search: nq=%d", nq);
+    IVR_REQUIRE(cap >= 0, "ivr_index_range_search: cap=%lld", (long long)cap);
+    IVR_REQUIRE(!(radius != radius), "ivr_index_range_search: radius is NaN");
+    if (check_filter(filter, "ivr_index_range_search_filtered") != IVR_OK) return IVR_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(x->mu);
+    IVR_HIP(hipSetDevice(x->ctx->device));
+    RowMask m;
+    const View v = filter ? filtered_view(x, id_base, *filter, m) : full_view(x, id_base);
+    return range_search_view(x, v, q, nq, radius, normalize_q, lims, D, I, cap, (hipStream_t)stream);
 }
 
 int ivr_topk_merge(ivr_ctx *ctx, const float *D_parts, const int64_t *I_parts, int parts, int nq, int k, float *D,

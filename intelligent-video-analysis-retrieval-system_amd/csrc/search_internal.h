@@ -3,6 +3,8 @@
 #pragma once
 #include "ivr_common.h"
 
+#include <cfloat>
+
 // One launch of the large-query candidate scan: every stored row against every query of the batch on the bf16 MFMA,
 // reduced on the fly to one maximum per (query, 16-row tile) and one per (query, 128-row block).  The index is streamed
 // from HBM once per launch whatever the number of queries ("large query batches").
@@ -23,4 +25,34 @@ struct ScanQArgs {
     int64_t bstride;
 };
 
-int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s);
+// Filtered search (ivr_index_search_filtered): the rows a launch may rank, in the row numbering of the part of the index it scans.
+// Row r is allowed iff lo <= r < hi and, when bits != NULL, bit (bit0 + r) of bits is set (LSB first within a byte).  The host clips
+// [lo, hi) to the scanned rows and to the bitmap's length, so a bitmap byte is only read for an allowed-range row.
+struct RowMask {
+    int64_t lo = 0, hi = 0;
+    const uint8_t *bits = nullptr;
+    int64_t bit0 = 0;
+};
+
+// The mask of 64 consecutive rows r0 .. r0 + 63 as one wave-uniform word, in two steps so that the bitmap load can be issued early:
+// row_mask_fetch (lane l: the bitmap byte of row r0 + l; one load per lane, no use of it), later row_mask_word (bit l = row r0 + l
+// allowed, by ballot).  Without a bitmap nothing is loaded.
+__device__ __forceinline__ uint32_t row_mask_fetch(const RowMask &m, int64_t r0) {
+    if (!m.bits) return 0u;
+    const int64_t r = r0 + (threadIdx.x & 63);
+    const int64_t b = m.bit0 + (r >= m.lo && r < m.hi ? r : m.lo);     // an in-range byte for every lane: no branch around the load
+    return m.bits[b >> 3];
+}
+__device__ __forceinline__ uint64_t row_mask_word(const RowMask &m, int64_t r0, uint32_t byte) {
+    const int64_t r = r0 + (threadIdx.x & 63);
+    bool ok = r >= m.lo && r < m.hi;
+    if (m.bits) ok = ok && ((byte >> ((m.bit0 + r) & 7)) & 1u);
+    return __ballot(ok);
+}
+// score of a row in a masked maximum: -inf for a row that is not allowed (a maximum of -inf = no allowed row), allowed rows clamped to
+// >= -FLT_MAX so that they stay above that sentinel
+__device__ __forceinline__ float row_mask_score(uint64_t word_shifted, int bit, float s) {
+    return ((word_shifted >> bit) & 1ull) ? fmaxf(s, -FLT_MAX) : -INFINITY;
+}
+
+int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s, const RowMask *mask = nullptr);

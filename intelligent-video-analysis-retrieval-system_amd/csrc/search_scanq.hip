@@ -63,7 +63,50 @@ __device__ __forceinline__ float sq_fold16(float x, float y) {
     return x;
 }
 
-__global__ __launch_bounds__(512, 2) void scanq_kernel(ScanQArgs g) {
+// bit r of nib set: s, else -inf.  Lane-local bit operations: a select would become a v_cmp with a 64-bit lane mask in SGPRs per
+// element, and 32 of those live at once spill in this kernel
+__device__ __forceinline__ float sq_mask_sel(uint32_t nib, int r, float s) {
+    uint32_t m, out;
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(nib), "i"(r));
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(out) : "v"(m), "v"(__float_as_uint(s)), "v"(0xff800000u));
+    return __uint_as_float(out);
+}
+
+// The mask of scanq_kernel<true>.  Row r is allowed iff lo <= r < hi and (words == NULL or bit (shift + r) of the dword stream at words is
+// set).  The host aligns the stream to a dword and clamps reads to dwords [dlo, dhi], the ones that hold a byte of an allowed-range
+// row (such a dword cannot leave the bitmap's pages).
+struct ScanQMask {
+    const uint32_t *words;
+    uint32_t lo, hi, shift, dlo, dhi;
+};
+// bit i of the result: row r0 + i allowed (r0 % 32 == 0), for the 128 rows r0 .. r0 + 127 as four wave-uniform words.  The range
+// test is a ballot; the bitmap comes through five scalar loads (uniform address, constant address space), no vector load: a vector
+// load in this epilogue spills the kernel's VGPRs.
+__device__ __forceinline__ void sq_mask_words(const ScanQMask &m, uint32_t r0, uint32_t (&w)[4]) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t b0 = __ballot(r0 + lane >= m.lo && r0 + lane < m.hi), b1 = __ballot(r0 + 64 + lane >= m.lo && r0 + 64 + lane < m.hi);
+    w[0] = (uint32_t)b0;
+    w[1] = (uint32_t)(b0 >> 32);
+    w[2] = (uint32_t)b1;
+    w[3] = (uint32_t)(b1 >> 32);
+    if (m.words) {
+        typedef __attribute__((address_space(4))) const uint32_t cu32;
+        cu32 *p = (cu32 *)(uintptr_t)m.words;
+        const uint32_t base = r0 >> 5;
+        uint32_t d[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) d[k] = p[min(max(base + k, m.dlo), m.dhi)];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] &= (uint32_t)((((uint64_t)d[j + 1] << 32) | d[j]) >> m.shift);
+    }
+}
+
+// MASK (filtered search, one ScanQMask in the pack): the epilogue of an item scores the rows of the wave that are not allowed as -inf,
+// allowed ones as max(score, -FLT_MAX) (the sentinel of search_internal.h).  The plain kernel uses every VGPR in its K loop and most
+// of them in the epilogue, so the mask state lives only in the epilogue and in SGPRs: a range ballot, five scalar loads of the
+// bitmap, four uniform words; per 16-row tile one 4-bit field and lane-local bit operations.  No spill (profiles/r10a_isa_compare.log).
+template <bool MASK, typename... M>
+__global__ __launch_bounds__(512, 2) void scanq_kernel(ScanQArgs g, M... rm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -94,14 +137,14 @@ __global__ __launch_bounds__(512, 2) void scanq_kernel(ScanQArgs g) {
         }
     };
     Pos px = {slot / QB, slot % QB}, pw = px, pc = px;
-    auto rows_rsrc = [&](const Pos &p) {
-        return __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char *>(reinterpret_cast<const char *>(g.data16)) + (int64_t)(xcd + 8 * (int64_t)p.r) * (int64_t)slab, 0, (int)slab, 0x00020000);
-    };
-    auto query_rsrc = [&](const Pos &p) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(reinterpret_cast<const char *>(g.q16)) + (int64_t)p.qb * (int64_t)slab, 0,
-                                                 (int)slab, 0x00020000);
-    };
+    // macros, not lambdas: a lambda returning the descriptor type inside a kernel TEMPLATE makes hipcc drop the host-side
+    // instantiation silently (see scan16_ring_kernel)
+#define SQ_ROWS_RSRC(P)                                                                                                              \
+    __builtin_amdgcn_make_buffer_rsrc(                                                                                               \
+        const_cast<char *>(reinterpret_cast<const char *>(g.data16)) + (int64_t)(xcd + 8 * (int64_t)(P).r) * (int64_t)slab, 0, (int)slab, 0x00020000)
+#define SQ_QUERY_RSRC(P)                                                                                                             \
+    __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(reinterpret_cast<const char *>(g.q16)) + (int64_t)(P).qb * (int64_t)slab, 0, \
+                                      (int)slab, 0x00020000)
 
     // DMA: 32 pieces of 1 KiB per operand per stage; wave w issues pieces 4w .. 4w+3 of each.  Piece p = tile p >> 1, K half
     // p & 1 of the stage; the LDS image of a slot is the pieces in that order.
@@ -114,8 +157,8 @@ __global__ __launch_bounds__(512, 2) void scanq_kernel(ScanQArgs g) {
     const unsigned voff = (unsigned)lane * 16u;
     // cursors of the two DMA streams: the next stage to issue for the row operand (X) and the query operand (W)
     int xn = 0, xkt = 0, wcn = 0, wkt = 0;
-    auto rsX = rows_rsrc(px);
-    auto rsW = query_rsrc(pw);
+    auto rsX = SQ_ROWS_RSRC(px);
+    auto rsW = SQ_QUERY_RSRC(pw);
     auto pieceX = [&](int xs, int j) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (__attribute__((address_space(3))) void *)(smem + xs * SQ_SLOT + (wave * 4 + j) * 1024), 16,
                                                  voff, pbase[j] + (unsigned)xkt * 2048u, 0, 0);
@@ -128,14 +171,14 @@ __global__ __launch_bounds__(512, 2) void scanq_kernel(ScanQArgs g) {
         if (++xkt == KT) {
             xkt = 0;
             step(px);
-            if (++xn < count) rsX = rows_rsrc(px);
+            if (++xn < count) rsX = SQ_ROWS_RSRC(px);
         }
     };
     auto advanceW = [&]() {
         if (++wkt == KT) {
             wkt = 0;
             step(pw);
-            if (++wcn < count) rsW = query_rsrc(pw);
+            if (++wcn < count) rsW = SQ_QUERY_RSRC(pw);
         }
     };
 
@@ -262,13 +305,22 @@ __global__ __launch_bounds__(512, 2) void scanq_kernel(ScanQArgs g) {
         const int64_t row0 = rb * 256 + wm * 128;                    // first row of this wave's 8 tiles
         const bool partial = row0 + 128 > g.ntotal;                  // wave-uniform: only the last block of the index
         const int c = lane & 15, h = lane >> 4;
+        uint32_t mw[4] = {0u, 0u, 0u, 0u};          // wave-uniform: bit i of mw[j] = row 32 j + i of the wave's 128 allowed
+        if constexpr (MASK) {
+            sq_mask_words(rm..., (uint32_t)row0, mw);
+        }
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
             float m[8];
 #pragma unroll
             for (int mt = 0; mt < 8; ++mt) {
                 f32x4 a = acc[nt][mt];
-                if (partial) {
+                if constexpr (MASK) {
+                    // rows 16 mt + 4 h .. +3 of this lane: one 4-bit field of the uniform words
+                    const uint32_t nib = (mw[mt >> 1] >> ((mt & 1) * 16 + h * 4)) & 15u;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) a[r] = sq_mask_sel(nib, r, sq_max(a[r], -FLT_MAX));
+                } else if (partial) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (row0 + mt * 16 + h * 4 + r >= g.ntotal) a[r] = -FLT_MAX;
@@ -290,20 +342,35 @@ __global__ __launch_bounds__(512, 2) void scanq_kernel(ScanQArgs g) {
 #undef SQ_ROW
 #undef SQ_RD4
 #undef SQ_LGKM
+#undef SQ_ROWS_RSRC
+#undef SQ_QUERY_RSRC
 }
+
 
 }  // namespace
 
-int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s) {
+int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s, const RowMask *mask) {
     IVR_REQUIRE(a.pieces >= 2 && (a.pieces & 1) == 0, "scanq: pieces=%d must be even", a.pieces);
     IVR_REQUIRE(a.qblocks >= 1 && a.nblocks >= 1, "scanq: empty problem");
-    int rc = ivr_func_max_lds(reinterpret_cast<const void *>(scanq_kernel), SQ_LDS);
+    int rc = ivr_func_max_lds(mask ? reinterpret_cast<const void *>(scanq_kernel<true, ScanQMask>) : reinterpret_cast<const void *>(scanq_kernel<false>), SQ_LDS);
     if (rc != IVR_OK) return rc;
     // one workgroup per CU (160 KiB of LDS each); a multiple of 8 so that slot = blockIdx / 8 is the same on every XCD
     const int grid = std::max(8, ctx->cu_count / 8 * 8);
     // algorithmic work of the launch: 2 * rows * padded queries * K flop
     IvrProf prof("scanq", s, 2.0 * (double)a.ntotal * a.qblocks * 256.0 * a.pieces * 32.0);
-    hipLaunchKernelGGL(scanq_kernel, dim3(grid), dim3(512), SQ_LDS, s, a);
+    if (mask) {
+        // rows of a view fit in 32 bits (the index holds fewer than 2^32); the bitmap as a dword stream: row r's bit is bit shift + r
+        ScanQMask sm{nullptr, (uint32_t)mask->lo, (uint32_t)mask->hi, 0u, 0u, 0u};
+        if (mask->bits && mask->lo < mask->hi) {
+            const uintptr_t base = (uintptr_t)mask->bits, p0 = base + (uintptr_t)(mask->bit0 >> 3), aligned = p0 & ~(uintptr_t)3;
+            sm.words = reinterpret_cast<const uint32_t *>(aligned);
+            sm.shift = (uint32_t)((mask->bit0 & 7) + 8 * (int64_t)(p0 & 3));
+            sm.dlo = (uint32_t)((base + (uintptr_t)((mask->bit0 + mask->lo) >> 3) - aligned) >> 2);
+            sm.dhi = (uint32_t)((base + (uintptr_t)((mask->bit0 + mask->hi - 1) >> 3) - aligned) >> 2);
+        }
+        hipLaunchKernelGGL((scanq_kernel<true, ScanQMask>), dim3(grid), dim3(512), SQ_LDS, s, a, sm);
+    }
+    else hipLaunchKernelGGL(scanq_kernel<false>, dim3(grid), dim3(512), SQ_LDS, s, a);
     IVR_LAUNCH_CHECK();
     return IVR_OK;
 }

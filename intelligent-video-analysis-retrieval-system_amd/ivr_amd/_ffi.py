@@ -35,7 +35,12 @@ class GemmDesc(C.Structure):
                 + [(n, C.c_int) for n in ("T", "G2", "skip_mod", "reverse_m")])
 
 
-API_VERSION = 7
+class IdFilter(C.Structure):
+    """ivr_id_filter (include/ivr_api.h): allowed ids [lo, hi), and bits[id >> 3] >> (id & 7) & 1 when bits is set (id < nbits)."""
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64), ("bits", C.c_void_p), ("nbits", C.c_int64)]
+
+
+API_VERSION = 8
 FP8_SITE = {"qkv": 1, "o": 2, "fc1": 4, "fc2": 8}
 
 
@@ -83,6 +88,8 @@ _SIGS = {
     "ivr_index_reserve_search": (_i, [_p, _i, _i]),
     "ivr_index_search": (_i, [_p, _p, _i, _i, _i, _i64, _p, _p, _p]),
     "ivr_index_range_search": (_i, [_p, _p, _i, _f, _i, _i64, _p, _p, _p, _i64, _p]),
+    "ivr_index_search_filtered": (_i, [_p, _p, _i, _i, _i, _i64, C.POINTER(IdFilter), _p, _p, _p]),
+    "ivr_index_range_search_filtered": (_i, [_p, _p, _i, _f, _i, _i64, C.POINTER(IdFilter), _p, _p, _p, _i64, _p]),
     "ivr_topk_merge": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_topk_pack": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "ivr_topk_merge_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),

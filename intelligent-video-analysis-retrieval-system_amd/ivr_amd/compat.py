@@ -31,7 +31,7 @@ import torch
 
 from . import config as C
 from .dedup import DedupState
-from .index import FlatIPIndex, count_nonfinite_and_normalize
+from .index import FlatIPIndex, IDSelectorBitmap, SearchParameters, count_nonfinite_and_normalize
 from .tower import Tower
 from .weights import from_hf_state_dict, make_weights
 
@@ -744,10 +744,17 @@ class UnifiedIndex:
             return self.metadata_list[idx]
         return None
 
-    def search_vectors(self, query_vector, k: int = 50, filter_func: Callable = None) -> List[Dict[str, Any]]:
-        """unified_index.py:480-538: 0-based rank, similarity_score = 1 - inner product."""
+    def search_vectors(self, query_vector, k: int = 50, filter_func: Callable = None, prefilter: bool = False) -> List[Dict[str, Any]]:
+        """unified_index.py:480-538: 0-based rank, similarity_score = 1 - inner product.
+
+        filter_func (metadata -> bool) is applied after the global top k, as the reference does: a selective filter returns few or no
+        rows.  prefilter=True evaluates filter_func once per stored row instead, packs the result into a bitmap (rows without metadata
+        are not allowed) and searches with it: up to k rows that pass, ranks 0..n-1.  Rows are in sorted-path order, so one folder is
+        one id range, and only the rows between the first and the last allowed id are scanned."""
         if not self.is_loaded:
             raise ValueError("Index not loaded. Call load_unified_index() first.")
+        if prefilter and filter_func is not None:
+            return self._search_prefiltered(query_vector, k, filter_func)
         distances, indices = self.faiss_index.search(np.asarray(query_vector, dtype=np.float32).reshape(1, -1), k)
         results = []
         for i, (dist, idx) in enumerate(zip(distances[0], indices[0])):
@@ -759,6 +766,27 @@ class UnifiedIndex:
             if filter_func and not filter_func(md):
                 continue
             results.append({"rank": i, "similarity_score": float(1.0 - dist), "metadata": md, "index": int(idx)})
+        return results
+
+    def _search_prefiltered(self, query_vector, k, filter_func):
+        n = self.faiss_index.ntotal
+        mask = np.zeros(n, dtype=bool)
+        for i in range(n):
+            md = self._get_metadata_cached(i)
+            mask[i] = md is not None and bool(filter_func(md))
+        allowed = np.flatnonzero(mask)
+        if allowed.size == 0:
+            return []
+        # the range of the allowed rows: nothing outside it is scanned
+        sel = IDSelectorBitmap(np.packbits(mask, bitorder="little"), lo=int(allowed[0]), hi=int(allowed[-1]) + 1)
+        distances, indices = self.faiss_index.search(np.asarray(query_vector, dtype=np.float32).reshape(1, -1), k,
+                                                     params=SearchParameters(sel=sel))
+        results = []
+        for dist, idx in zip(distances[0], indices[0]):
+            if idx == -1:
+                break
+            results.append({"rank": len(results), "similarity_score": float(1.0 - dist), "metadata": self._get_metadata_cached(idx),
+                            "index": int(idx)})
         return results
 
     def augmented_search(self, query, top_k=10, clip_processor=None):

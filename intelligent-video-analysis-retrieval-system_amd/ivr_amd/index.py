@@ -53,6 +53,134 @@ def count_nonfinite_and_normalize(t):
     return int(flag.item())
 
 
+# -- faiss ID selectors (SearchParameters(sel=...)) --------------------------------------------------------------------------
+# Each selector reduces to the filter of the C ABI: an id range [lo, hi) and an optional bitmap in faiss IDSelectorBitmap order
+# (bit id & 7 of byte id >> 3).  The bitmap is uploaded once per device and kept.
+class _IDSelector:
+    lo = hi = 0
+    _bits = None            # numpy uint8 bytes from byte _byte0 on (byte index id >> 3), or None: the range alone
+    _byte0 = 0
+    nbits = 0
+
+    def __init__(self):
+        self._dev = {}
+
+    def _filter(self, device):
+        """ivr_id_filter for `device` (the bitmap uploaded on first use)."""
+        ptr = None
+        if self._bits is not None:
+            t = self._dev.get(device.index)
+            if t is None:
+                t = torch.from_numpy(np.ascontiguousarray(self._bits)).to(device) if len(self._bits) else torch.zeros(1, dtype=torch.uint8, device=device)
+                self._dev[device.index] = t
+            # bits[id >> 3] must address byte id >> 3: the upload starts at byte _byte0, and the kernels read bytes of ids in [lo, hi)
+            # only, so lo is kept at or above the upload's first id whatever the attributes say
+            ptr = t.data_ptr() - self._byte0
+            return _ffi.IdFilter(max(int(self.lo), 8 * self._byte0), int(self.hi), ptr, int(self.nbits))
+        return _ffi.IdFilter(int(self.lo), int(self.hi), None, 0)
+
+    def is_member(self, i):
+        i = int(i)
+        if not (self.lo <= i < self.hi):
+            return False
+        if self._bits is None:
+            return True
+        b = (i >> 3) - self._byte0
+        return i < self.nbits and 0 <= b < len(self._bits) and bool((self._bits[b] >> (i & 7)) & 1)
+
+
+class IDSelectorRange(_IDSelector):
+    """faiss.IDSelectorRange(imin, imax): ids imin <= id < imax.  Scanning is restricted to the rows of that range."""
+
+    def __init__(self, imin, imax):
+        super().__init__()
+        self.imin, self.imax = int(imin), int(imax)
+        self.lo, self.hi = self.imin, self.imax
+
+
+class IDSelectorBitmap(_IDSelector):
+    """faiss.IDSelectorBitmap(bitmap): id allowed iff bit (id & 7) of byte (id >> 3) is set; bitmap = numpy.packbits(mask,
+    bitorder="little") as a uint8 numpy array or torch tensor.  IDSelectorBitmap(n, bitmap) (faiss's C++ argument order) is taken too.
+    lo= / hi= (extension): also require lo <= id < hi, i.e. the bitmap intersected with IDSelectorRange(lo, hi); only the rows of that
+    range are scanned, so giving the first and last set id as the range keeps a sparse bitmap from streaming the whole index."""
+
+    def __init__(self, *args, lo=None, hi=None):
+        super().__init__()
+        if len(args) == 2:
+            n, bitmap = args
+        elif len(args) == 1:
+            n, bitmap = None, args[0]
+        else:
+            raise ValueError("IDSelectorBitmap(bitmap) or IDSelectorBitmap(n, bitmap)")
+        if isinstance(bitmap, torch.Tensor):
+            if bitmap.dtype != torch.uint8:
+                raise ValueError(f"IDSelectorBitmap: bitmap must be uint8, got {bitmap.dtype}")
+            bitmap = bitmap.detach().cpu().numpy()
+        if not isinstance(bitmap, np.ndarray) or bitmap.dtype != np.uint8:
+            raise ValueError("IDSelectorBitmap: bitmap must be a uint8 numpy array or torch tensor")
+        bitmap = np.ascontiguousarray(bitmap).reshape(-1)
+        if n is not None:
+            n = int(n)
+            if n < 0 or n > len(bitmap):
+                raise ValueError(f"IDSelectorBitmap: n={n} outside [0, {len(bitmap)}]")
+            bitmap = bitmap[:n]
+        self.bitmap = bitmap.copy()
+        self._bits = self.bitmap
+        self.nbits = 8 * len(self.bitmap)
+        self.lo = 0 if lo is None else max(0, int(lo))
+        self.hi = self.nbits if hi is None else min(self.nbits, int(hi))
+
+
+class IDSelectorBatch(_IDSelector):
+    """faiss.IDSelectorBatch(ids): the listed ids (duplicates are harmless).  Stored as a bitmap over [min(ids), max(ids)] plus that
+    range, so an id list clustered in a few videos only scans the rows between its first and last id.  Negative ids never match.
+    The bitmap takes (max(ids) - min(ids)) / 8 bytes on the host and on each device it is used on: one stray large id (say 10**9 among
+    ids below 10**6) costs about 125 MB.  Drop ids at or above the index size first when that matters."""
+
+    def __init__(self, ids):
+        super().__init__()
+        if isinstance(ids, torch.Tensor):
+            ids = ids.detach().cpu().numpy()
+        ids = np.asarray(ids).reshape(-1)
+        if ids.size and not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f"IDSelectorBatch: ids must be integers, got {ids.dtype}")
+        ids = ids.astype(np.int64)
+        ids = np.unique(ids[ids >= 0])
+        if ids.size == 0:
+            self.lo = self.hi = 0
+            self._bits = np.zeros(0, np.uint8)
+            return
+        lo, hi = int(ids[0]), int(ids[-1]) + 1
+        self._byte0 = lo >> 3
+        bits = np.zeros(((hi - 1) >> 3) - self._byte0 + 1, np.uint8)
+        rel = ids - 8 * self._byte0
+        np.bitwise_or.at(bits, rel >> 3, (1 << (rel & 7)).astype(np.uint8))
+        self._bits = bits
+        self.lo, self.hi, self.nbits = lo, hi, hi
+
+
+class SearchParameters:
+    """faiss.SearchParameters(sel=...): only `sel` is used (None = every id)."""
+
+    def __init__(self, sel=None):
+        if sel is not None and not isinstance(sel, _IDSelector):
+            raise ValueError(f"SearchParameters: sel must be an IDSelectorRange / IDSelectorBatch / IDSelectorBitmap, got {type(sel).__name__}")
+        self.sel = sel
+
+
+def _selector(params=None, sel=None):
+    """The selector of `params` (a SearchParameters) or `sel`; ValueError for anything else."""
+    if params is not None:
+        if not isinstance(params, SearchParameters):
+            raise ValueError(f"params must be a SearchParameters, got {type(params).__name__}")
+        if sel is not None:
+            raise ValueError("give the selector either in params or as sel, not both")
+        sel = params.sel
+    if sel is not None and not isinstance(sel, _IDSelector):
+        raise ValueError(f"sel must be an IDSelectorRange / IDSelectorBatch / IDSelectorBitmap, got {type(sel).__name__}")
+    return sel
+
+
 class FlatIPIndex:
     """Exact inner-product index (FAISS IndexFlatIP contract) on one GPU."""
 
@@ -127,16 +255,19 @@ class FlatIPIndex:
             _ffi.check(self._lib.ivr_index_write_ring(self._h, C.c_void_p(rows.data_ptr()), rows.shape[0], int(bool(normalize)),
                                                       C.c_void_p(cursor.data_ptr()), _ffi.stream_ptr()), "ivr_index_write_ring")
 
-    def search(self, x, k):
-        """(D, I) numpy arrays, exactly like faiss: D float32 [nq,k] descending, I int64 [nq,k], -1 padded."""
+    def search(self, x, k, params=None):
+        """(D, I) numpy arrays, exactly like faiss: D float32 [nq,k] descending, I int64 [nq,k], -1 padded.  params =
+        SearchParameters(sel=IDSelector...): the top k among the ids the selector allows."""
+        sel = _selector(params)
         q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
         if isinstance(q, np.ndarray) and q.ndim == 1:
             q = q.reshape(1, -1)
-        D, I = self.search_device(q, k)
+        D, I = self.search_device(q, k) if sel is None else self.search_device(q, k, sel=sel)
         return D.cpu().numpy(), I.cpu().numpy()
 
-    def search_device(self, x, k, normalize=False, id_base=0, out=None):
-        """Device-resident variant: returns CUDA tensors and does not synchronise."""
+    def search_device(self, x, k, normalize=False, id_base=0, out=None, sel=None):
+        """Device-resident variant: returns CUDA tensors and does not synchronise.  sel: an IDSelector (ids = id_base + row)."""
+        sel = _selector(sel=sel)
         t = _dev_f32(x, self.device)
         if t.dim() != 2 or t.shape[1] != self.d:
             raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({self.d})")
@@ -150,32 +281,40 @@ class FlatIPIndex:
         else:
             D, I = out
         with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_search(self._h, C.c_void_p(t.data_ptr()), nq, k, int(bool(normalize)),
-                                                  int(id_base), C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()),
-                                                  _ffi.stream_ptr()), "ivr_index_search")
+            if sel is None:
+                _ffi.check(self._lib.ivr_index_search(self._h, C.c_void_p(t.data_ptr()), nq, k, int(bool(normalize)),
+                                                      int(id_base), C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()),
+                                                      _ffi.stream_ptr()), "ivr_index_search")
+            else:
+                f = sel._filter(self.device)
+                _ffi.check(self._lib.ivr_index_search_filtered(self._h, C.c_void_p(t.data_ptr()), nq, k, int(bool(normalize)), int(id_base),
+                                                               C.byref(f), C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()),
+                                                               _ffi.stream_ptr()), "ivr_index_search_filtered")
             if t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0):
                 torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
         return D, I
 
-    def range_search(self, x, radius):
+    def range_search(self, x, radius, params=None):
         """faiss range_search: every row with <q, row> > radius.  (lims int64 [nq+1], D float32 [lims[-1]], I int64 [lims[-1]])
         numpy arrays; query i's results are D/I[lims[i]:lims[i+1]], ids ascending.  One host sync to read the total; a second
-        pass only when the first-guess capacity was too small."""
+        pass only when the first-guess capacity was too small.  params = SearchParameters(sel=...): only the allowed ids."""
+        sel = _selector(params)
         q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
         if isinstance(q, np.ndarray) and q.ndim == 1:
             q = q.reshape(1, -1)
         t = _dev_f32(q, self.device)
         cap = max(1024, 64 * t.shape[0])
-        lims, D, I, total = self.range_search_device(t, radius, cap=cap)
+        lims, D, I, total = self.range_search_device(t, radius, cap=cap, sel=sel)
         n = int(total.item())
         if n > cap:
-            lims, D, I, total = self.range_search_device(t, radius, cap=n)
+            lims, D, I, total = self.range_search_device(t, radius, cap=n, sel=sel)
         return lims.cpu().numpy(), D[:n].cpu().numpy(), I[:n].cpu().numpy()
 
-    def range_search_device(self, x, radius, normalize=False, id_base=0, cap=None):
+    def range_search_device(self, x, radius, normalize=False, id_base=0, cap=None, sel=None):
         """Device-resident range search: (lims [nq+1], D [cap], I [cap], total) CUDA tensors, total = lims[nq:] (the number of
         results; entries at positions >= cap are counted but not written).  No host sync when `cap` is given; cap=None sizes
-        D and I exactly (a counting pass, one sync, then the full pass)."""
+        D and I exactly (a counting pass, one sync, then the full pass).  sel: an IDSelector (ids = id_base + row)."""
+        sel = _selector(sel=sel)
         radius = float(radius)
         if radius != radius:
             raise ValueError("range_search: radius is NaN")
@@ -190,9 +329,16 @@ class FlatIPIndex:
         def run(c):
             D = torch.empty(max(c, 1), dtype=torch.float32, device=self.device)   # never a NULL pointer, even for cap 0
             I = torch.empty(max(c, 1), dtype=torch.int64, device=self.device)
-            _ffi.check(self._lib.ivr_index_range_search(self._h, C.c_void_p(t.data_ptr()), nq, C.c_float(radius), int(bool(normalize)),
-                                                        int(id_base), C.c_void_p(lims.data_ptr()), C.c_void_p(D.data_ptr()),
-                                                        C.c_void_p(I.data_ptr()), int(c), _ffi.stream_ptr()), "ivr_index_range_search")
+            if sel is None:
+                _ffi.check(self._lib.ivr_index_range_search(self._h, C.c_void_p(t.data_ptr()), nq, C.c_float(radius), int(bool(normalize)),
+                                                            int(id_base), C.c_void_p(lims.data_ptr()), C.c_void_p(D.data_ptr()),
+                                                            C.c_void_p(I.data_ptr()), int(c), _ffi.stream_ptr()), "ivr_index_range_search")
+            else:
+                f = sel._filter(self.device)
+                _ffi.check(self._lib.ivr_index_range_search_filtered(self._h, C.c_void_p(t.data_ptr()), nq, C.c_float(radius),
+                                                                     int(bool(normalize)), int(id_base), C.byref(f), C.c_void_p(lims.data_ptr()),
+                                                                     C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()), int(c),
+                                                                     _ffi.stream_ptr()), "ivr_index_range_search_filtered")
             return D[:c], I[:c]
 
         with torch.cuda.device(self.device):

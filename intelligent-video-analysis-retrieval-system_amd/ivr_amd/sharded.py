@@ -11,7 +11,8 @@ collective is the right shape; no other exchange exists on this path.
 
 The class is agnostic of how a shard is searched: `local` only needs
 `search_device(q, k, normalize=, id_base=) -> (D, I)` tensors, `add`, `ntotal` (and
-`range_search_device(q, radius, normalize=, id_base=) -> (lims, D, I, total)` for range_search).  On GPUs that
+`range_search_device(q, radius, normalize=, id_base=) -> (lims, D, I, total)` for range_search; both with `sel=` for a filtered
+search).  On GPUs that
 is `ivr_amd.index.FlatIPIndex`; the world_size-2 gloo tests on CPU plug the oracle in.
 """
 import numpy as np
@@ -122,17 +123,28 @@ class ShardedIndex:
         return int(sum(self._counts))
 
     # -- search ------------------------------------------------------------------------------
-    def search(self, q, k, normalize=False):
-        """q [nq,d] replicated on every rank -> (D [nq,k], I [nq,k] global ids), identical on every rank."""
-        D, I = self.local.search_device(q, k, normalize=normalize, id_base=self.id_base)
+    @staticmethod
+    def _sel_kw(params):
+        """params (SearchParameters or None) -> the sel= keyword of the local call.  The selector names GLOBAL ids; each rank's id_base
+        carries its shard offset, so the same selector is valid on every rank and no extra exchange is needed."""
+        if params is None:
+            return {}
+        from .index import _selector
+        sel = _selector(params)
+        return {} if sel is None else {"sel": sel}
+
+    def search(self, q, k, normalize=False, params=None):
+        """q [nq,d] replicated on every rank -> (D [nq,k], I [nq,k] global ids), identical on every rank.  params =
+        SearchParameters(sel=...) over global ids: the top k among the allowed ids of all shards."""
+        D, I = self.local.search_device(q, k, normalize=normalize, id_base=self.id_base, **self._sel_kw(params))
         return self.exchange(D, I)
 
-    def range_search(self, q, radius, normalize=False):
+    def range_search(self, q, radius, normalize=False, params=None):
         """Exact range search over all shards: q [nq,d] replicated on every rank -> (lims [nq+1], D, I global ids), identical on
         every rank and laid out like FlatIPIndex.range_search (ids ascending within a query).  Two collectives: an all-gather of the
         per-query counts, then ONE all-gather of the packed (score, id) results padded to the largest rank's total.  Shards are
         contiguous and ascending, so concatenating each query's parts in rank order keeps its ids ascending: no sort."""
-        lims, D, I, _ = self.local.range_search_device(q, radius, normalize=normalize, id_base=self.id_base)
+        lims, D, I, _ = self.local.range_search_device(q, radius, normalize=normalize, id_base=self.id_base, **self._sel_kw(params))
         if self.world == 1:
             return lims, D, I
         nq = lims.numel() - 1
