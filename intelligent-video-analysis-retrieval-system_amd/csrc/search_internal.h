@@ -1,9 +1,19 @@
-// Internal interface between search.hip (index object, selection, re-score) and search_scanq.hip (the large-query-batch
-// candidate scan).  Not part of the C ABI.
+// The one internal header of the flat index: search_index.hip (the index object and its storage), search.hip (group-maximum scans and
+// the top-k driver), search_range.hip (range search) and search_scanq.hip (the large-query-batch candidate scan).  It holds what more
+// than one of them needs: the index object with the plan of a search, the view a search scans, the row mask of a filtered search, and
+// the launchers that are defined in one file and called from another.  Not part of the C ABI.
 #pragma once
 #include "ivr_common.h"
 
+#include <algorithm>
 #include <cfloat>
+#include <initializer_list>
+#include <type_traits>
+#include <utility>
+
+constexpr int kGroupRows = 64;       // rows per scan group (4 MFMA row tiles)
+constexpr int kBigChunk = 1024;      // queries per launch chain of the large-batch scan
+constexpr int kBigMaxK = 128;        // beyond this k the chunks of 64 queries are used (candidate lists grow with k)
 
 // One launch of the large-query candidate scan: every stored row against every query of the batch on the bf16 MFMA,
 // reduced on the fly to one maximum per (query, 16-row tile) and one per (query, 128-row block).  The index is streamed
@@ -55,4 +65,144 @@ __device__ __forceinline__ float row_mask_score(uint64_t word_shifted, int bit, 
     return ((word_shifted >> bit) & 1ull) ? fmaxf(s, -FLT_MAX) : -INFINITY;
 }
 
+// Plain or masked instantiation of a kernel, chosen once: f(std::false_type) without a mask, f(std::true_type, mask) with one.  A
+// launcher writes  with_mask(v.mask, [&](auto masked, auto... m) { auto *k = kernel<.., decltype(masked)::value, decltype(m)...>;
+// ... launch k with (args..., m...) })  and so names its kernel and its argument list once.
+template <typename M, typename F>
+void with_mask(const M *mask, F &&f) {
+    if (mask) f(std::true_type{}, *mask);
+    else f(std::false_type{});
+}
+
+// One 16-float chunk of a float32 score: lane l holds floats 4 (l >> 4) .. + 3 of the chunk for row / query (l & 15) in a and b.
+// Every float32 score of the index (scan, re-score, range search) is accumulated by this sequence in ascending chunk order, which
+// is what makes them bit-identical to each other.
+__device__ __forceinline__ void mfma_chunk4(f32x4 &acc, const float4 &a, const float4 &b) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+}
+
+// Grow-only device buffer: DevMem owns the block and frees it in its destructor, DevBuf<T> is the same block read as a T *.  Grown
+// by ivr_reserve (search_index.hip).
+struct DevMem {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    DevMem() = default;
+    DevMem(const DevMem &) = delete;
+    DevMem &operator=(const DevMem &) = delete;
+    ~DevMem() {
+        if (ptr) (void)hipFree(ptr);
+    }
+};
+template <typename T>
+struct DevBuf : DevMem {
+    operator T *() const { return static_cast<T *>(ptr); }
+};
+// ivr_reserve({{&buf, bytes}, ...}, zero) grows a group of buffers that are sized together.  Nothing happens while EVERY buffer of
+// the group holds the bytes asked of it.  Otherwise every old block is freed before the first new one is allocated (a workspace
+// never holds two generations), then each is allocated (a size of 0 leaves that buffer empty) and, when asked, zero-filled.  All
+// or nothing: when an allocation fails the whole group is left empty and the error returned, so a repeated call tries again.
+typedef std::initializer_list<std::pair<DevMem *, size_t>> DevSizes;
+int ivr_reserve(DevSizes bufs, bool zero = false);
+
+struct ivr_index {
+    ivr_ctx *ctx = nullptr;
+    int d = 0, dp = 0, dp4 = 0;
+    int64_t cap = 0, ntotal = 0;     // cap is a multiple of kGroupRows
+    float *data = nullptr;
+    std::mutex mu;
+    // search workspace (grow-only)
+    DevBuf<float> qtiled;            // [qtiles][dp4][16][4]
+    DevBuf<float> qnorm;             // [qtiles*16] upper bound of each tiled query's norm (bf16 candidate scan verification)
+    DevBuf<float> gmax;              // [qcols][mstride]
+    DevBuf<uint32_t> sel;            // [nq][ksel]
+    DevBuf<uint64_t> cand;           // [nq][ksel*64]
+    // bf16 candidate scan (scan16_groupmax_kernel): scan copy of the rows, split queries, verification state
+    bool scan16 = false;             // IVR_SCAN_BF16 (default on), fixed at creation
+    int pieces = 0;                  // 1 KiB pieces of a 16-row tile = ceil(dp / 32)
+    uint4 *data16 = nullptr;         // [cap/16][pieces][64]
+    DevBuf<uint4> q16hi, q16lo;      // [qtiles][pieces][64]
+    DevBuf<unsigned int> maxnorm;    // DEV: bits of the largest stored row norm
+    DevBuf<int> okflag;              // DEV [64] per scan chunk + [4] tile flags behind it
+    int last_nqc = 0;                // queries of the last chunk that went through the candidate scan
+    // large-batch candidate scan (search_scanq.hip): more than 64 queries per call
+    DevBuf<unsigned int> maxdelta;   // DEV: bits of the largest |row - bf16(row)| over the stored rows
+    DevBuf<float> qdelta;            // DEV [qtiles*16]: |q - bf16(q)| of each tiled query
+    DevBuf<float> tmax;              // DEV [padded queries of a chunk][tstride]: 16-row tile maxima (also the gmax of its exact pass)
+    DevBuf<float> bmax;              // DEV [padded queries of a chunk][bstride]: 128-row block maxima
+    DevBuf<uint32_t> selb;           // DEV [queries of a chunk][kp + 1]: selected blocks
+    DevBuf<int> okq;                 // DEV [kBigChunk] verification result per query, [4] failure count, [kBigChunk] failed queries
+    bool last_big = false;           // the last search went through the large-batch scan
+    bool bigq = true;                // IVR_SCAN_BIGQ=0 keeps every batch on the 64-query chunks (A/B switch, read at creation)
+    bool prune = true;               // IVR_SCAN_PRUNE=0: the large-batch re-score fetches all kp selected tiles (A/B switch)
+    bool ring = true;                // IVR_SCAN_RING=0: the <= 16-query candidate scan streams the index through registers (A/B switch)
+    // exact range search (ivr_index_range_search), one chunk of <= 64 queries: [64][mstride] entries each, grow-only
+    DevBuf<uint32_t> rs_cand;        // candidate groups of each query, ascending
+    DevBuf<uint64_t> rs_mask;        // hit mask of each (query, candidate group): bit i = row 64 g + i scores > radius
+    DevBuf<uint32_t> rs_off;         // hits of each pair, then (in place) their exclusive prefix sum within the query
+    DevBuf<uint32_t> rs_count;       // DEV [64] candidate groups per query, [64] hits per query, then int64 [2]: running total
+
+    // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
+    // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity
+    int64_t mstride() const { return ivr_round_up(cap / kGroupRows, 64); }
+    int64_t tstride() const { return ivr_round_up(ivr_round_up(cap, 256) / 16, 64); }
+    int64_t bstride() const { return ivr_round_up(ivr_round_up(cap, 256) / 128, 64); }
+    // 16-query tiles per index pass of the streamed scans: as many as fit 128 KiB of LDS, at most 4; a chunk is 16 * qt_max() queries
+    int qt_max() const { return (int)std::max<int64_t>(1, std::min<int64_t>(4, (128 * 1024) / ((int64_t)16 * dp * 4))); }
+    // groups re-scored exactly behind the bf16 candidate scan: k plus slack for what the approximate ranking may displace
+    static int fast_groups(int k) { return k + std::max(22, k); }
+    // bf16 candidate scan first when it can pay: enough groups that kp of them are a small fraction, k within the selector's range
+    bool fast_scan(int64_t ngroups, int k) const {
+        return scan16 && ngroups >= 4 * (int64_t)(fast_groups(k) + 1) && fast_groups(k) + 1 <= IVR_MAX_K;
+    }
+    // more than 64 queries: the tiled large-batch scan (search_scanq.hip) instead of chunks of 64 queries past the streamed index
+    bool use_big(int nq, int k) const { return scan16 && bigq && nq > 64 && k <= kBigMaxK; }
+    // error bound of the bf16 candidate scan relative to |q| max|row|: bf16 keeps 8 significant bits, |row - bf16(row)| <= 2^-8 |row|
+    // per element; the query's hi + lo leaves 2^-16; f32 accumulation
+    float rel_eps() const { return (0.00390625f + 0.0000306f + (float)dp * 1.2e-7f) * 1.01f; }
+    float acc_eps() const { return (float)dp * 1.2e-7f; }        // the accumulation term alone (large-batch scan)
+};
+
+// choose the query tile width of the scan (queries per index pass = 16*QT)
+inline int pick_qt(int nq) { return nq <= 16 ? 1 : nq <= 32 ? 2 : nq <= 48 ? 3 : 4; }
+
+// The rows one search scans: the whole index, or for a filtered search the whole 256-row blocks that cover the allowed rows, treated as
+// an index of their own (the tiled layouts are contiguous per 16-row tile, so data and data16 are offset by whole blocks and the ids
+// shifted by the same rows; whole 256-row blocks keep the large-batch scan's block reads inside the allocation).  mask != NULL: the
+// masked kernels run, with the allowed rows in this view's numbering.
+struct View {
+    const float *data;
+    const uint4 *data16;
+    int64_t ntotal, ngroups, id_base;
+    const RowMask *mask;
+};
+
+// search_index.hip.  The view of a search: the whole index without a filter; with one (id = id_base + row) the part it allows and,
+// in m, the mask of its allowed rows (a view of 0 rows when nothing is allowed)
+View ivr_make_view(const ivr_index *x, int64_t id_base, const ivr_id_filter *f, RowMask &m);
+
+// The shared body of the search entry points once their own arguments are checked: filter check, lock, device, body(view)
+template <typename F>
+int with_view(ivr_index *x, int64_t id_base, const ivr_id_filter *f, const char *what, F &&body) {
+    IVR_REQUIRE(!f || f->nbits >= 0, "%s: filter nbits=%lld < 0", what, (long long)(f ? f->nbits : 0));
+    std::lock_guard<std::mutex> lk(x->mu);
+    IVR_HIP(hipSetDevice(x->ctx->device));
+    RowMask m;
+    return body(ivr_make_view(x, id_base, f, m));
+}
+
+// search_index.hip.  dst == x->data: index rows (bf16 scan copy + max norm alongside); dst == x->qtiled: queries (bf16 hi / lo split
+// alongside)
+int ivr_launch_tile_rows(ivr_index *x, float *dst, const float *src, int64_t start, int64_t n, int normalize, int32_t *nonfinite,
+                         hipStream_t s, const int64_t *start_dev = nullptr, int64_t max_tiles = 0);
+// search.hip.  Tiled query buffers for `qtiles` 16-query tiles, and the group maxima of one scan chunk (grow-only); the float32
+// scan of 16*qt query columns (tile_flag: see scan_groupmax_kernel) and the bf16 candidate scan of the query tiles from tile0 on,
+// both into x->gmax
+int ivr_reserve_queries(ivr_index *x, int qtiles);
+int ivr_reserve_gmax(ivr_index *x);
+void ivr_launch_scan_qt(ivr_index *x, const View &v, int qt, const float *qtile, hipStream_t s, const int *tile_flag = nullptr);
+void ivr_launch_fast_scan(ivr_index *x, const View &v, int qt, int64_t tile0, hipStream_t s);
+// search_scanq.hip
 int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s, const RowMask *mask = nullptr);

@@ -352,15 +352,11 @@ __global__ __launch_bounds__(512, 2) void scanq_kernel(ScanQArgs g, M... rm) {
 int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s, const RowMask *mask) {
     IVR_REQUIRE(a.pieces >= 2 && (a.pieces & 1) == 0, "scanq: pieces=%d must be even", a.pieces);
     IVR_REQUIRE(a.qblocks >= 1 && a.nblocks >= 1, "scanq: empty problem");
-    int rc = ivr_func_max_lds(mask ? reinterpret_cast<const void *>(scanq_kernel<true, ScanQMask>) : reinterpret_cast<const void *>(scanq_kernel<false>), SQ_LDS);
-    if (rc != IVR_OK) return rc;
-    // one workgroup per CU (160 KiB of LDS each); a multiple of 8 so that slot = blockIdx / 8 is the same on every XCD
-    const int grid = std::max(8, ctx->cu_count / 8 * 8);
-    // algorithmic work of the launch: 2 * rows * padded queries * K flop
-    IvrProf prof("scanq", s, 2.0 * (double)a.ntotal * a.qblocks * 256.0 * a.pieces * 32.0);
+    // rows of a view fit in 32 bits (the index holds fewer than 2^32); the bitmap as a dword stream: row r's bit is bit shift + r
+    ScanQMask sm{nullptr, 0u, 0u, 0u, 0u, 0u};
     if (mask) {
-        // rows of a view fit in 32 bits (the index holds fewer than 2^32); the bitmap as a dword stream: row r's bit is bit shift + r
-        ScanQMask sm{nullptr, (uint32_t)mask->lo, (uint32_t)mask->hi, 0u, 0u, 0u};
+        sm.lo = (uint32_t)mask->lo;
+        sm.hi = (uint32_t)mask->hi;
         if (mask->bits && mask->lo < mask->hi) {
             const uintptr_t base = (uintptr_t)mask->bits, p0 = base + (uintptr_t)(mask->bit0 >> 3), aligned = p0 & ~(uintptr_t)3;
             sm.words = reinterpret_cast<const uint32_t *>(aligned);
@@ -368,9 +364,19 @@ int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s, const RowM
             sm.dlo = (uint32_t)((base + (uintptr_t)((mask->bit0 + mask->lo) >> 3) - aligned) >> 2);
             sm.dhi = (uint32_t)((base + (uintptr_t)((mask->bit0 + mask->hi - 1) >> 3) - aligned) >> 2);
         }
-        hipLaunchKernelGGL((scanq_kernel<true, ScanQMask>), dim3(grid), dim3(512), SQ_LDS, s, a, sm);
     }
-    else hipLaunchKernelGGL(scanq_kernel<false>, dim3(grid), dim3(512), SQ_LDS, s, a);
+    int rc = IVR_OK;
+    with_mask(mask ? &sm : nullptr, [&](auto masked, auto... m) {
+        auto *k = scanq_kernel<decltype(masked)::value, decltype(m)...>;
+        rc = ivr_func_max_lds(reinterpret_cast<const void *>(k), SQ_LDS);
+        if (rc != IVR_OK) return;
+        // one workgroup per CU (160 KiB of LDS each); a multiple of 8 so that slot = blockIdx / 8 is the same on every XCD
+        const int grid = std::max(8, ctx->cu_count / 8 * 8);
+        // algorithmic work of the launch: 2 * rows * padded queries * K flop
+        IvrProf prof("scanq", s, 2.0 * (double)a.ntotal * a.qblocks * 256.0 * a.pieces * 32.0);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(512), SQ_LDS, s, a, m...);
+    });
+    if (rc != IVR_OK) return rc;
     IVR_LAUNCH_CHECK();
     return IVR_OK;
 }
