@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IVR_API_VERSION 8
+#define IVR_API_VERSION 9
 #define IVR_MAX_K 2048          /* reference: k=50 default, SearchOptions.limit <= 1000 (system.py:91) */
 
 typedef enum ivr_status {
@@ -290,6 +290,24 @@ int ivr_index_search_filtered(ivr_index *idx, const float *q /*DEV*/, int nq, in
 int ivr_index_range_search_filtered(ivr_index *idx, const float *q /*DEV*/, int nq, float radius, int normalize_q, int64_t id_base,
                                     const ivr_id_filter *filter /*HOST*/, int64_t *lims /*DEV*/, float *D /*DEV*/, int64_t *I /*DEV*/,
                                     int64_t cap, ivr_stream stream);
+
+/* faiss IndexFlat::remove_ids(sel): delete every stored row whose id (id_base + row) the filter allows.  The filter is read exactly as
+ * ivr_index_search_filtered reads it (lo <= id < hi, the optional bitmap in faiss order, ids outside [id_base, id_base + ntotal) match
+ * nothing), but it is required: filter == NULL and nbits < 0 are IVR_ERR_INVALID, there is no "remove everything" default; a filter
+ * that matches no stored row is a no-op that returns IVR_OK with *n_removed = 0.
+ * The surviving rows keep their relative order and move down to rows 0 .. ntotal' - 1 (as in faiss, the ids above a removed row
+ * shift); ntotal becomes ntotal', *n_removed (HOST, may be NULL) receives ntotal - ntotal', the capacity does not change.  Every
+ * surviving row keeps its bits in the float32 tiles and in the bf16 scan copy, so a search after the call reports for a surviving row
+ * the bit-identical score it reported before.  Rows [ntotal', old ntotal) are zero in both layouts afterwards, down to the slots of
+ * a partly filled 16-row tile: the state ivr_index_create and ivr_index_reset establish.  The bounds of the bf16 candidate scan
+ * (largest row norm, largest |row - bf16(row)|) are upper bounds over the rows ever stored; they stay valid and are left alone.
+ * Cost follows the tail: rows below the first removed row are neither read nor written, and the filter is evaluated from the
+ * 256-row block of its first allowed row on.  The extra device memory is a bounce buffer of at most IVR_REMOVE_CHUNK_ROWS rows in
+ * both layouts (environment, read by ivr_index_create; default 65536) plus 12 bytes per 64 rows of the tail.
+ * Synchronises `stream` once (the host needs the count to set ntotal): the call cannot be captured into a hipGraph, and a graph
+ * captured on this index before the call holds the old ntotal.  One stream at a time per handle, as for every call. */
+int ivr_index_remove_ids(ivr_index *idx, int64_t id_base, const ivr_id_filter *filter /*HOST*/, int64_t *n_removed /*HOST, may be NULL*/,
+                         ivr_stream stream);
 
 /* Merge per-shard candidate lists (the reference's concat + sort of peer results, system.py:1744-1746):
  * D_parts/I_parts DEV [parts, nq, k] with global ids, parts ordered by ascending id range. */

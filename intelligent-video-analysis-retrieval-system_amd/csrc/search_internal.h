@@ -143,6 +143,15 @@ struct ivr_index {
     DevBuf<uint64_t> rs_mask;        // hit mask of each (query, candidate group): bit i = row 64 g + i scores > radius
     DevBuf<uint32_t> rs_off;         // hits of each pair, then (in place) their exclusive prefix sum within the query
     DevBuf<uint32_t> rs_count;       // DEV [64] candidate groups per query, [64] hits per query, then int64 [2]: running total
+    // row removal (ivr_index_remove_ids), grow-only: the tail = the rows from the 256-row block of the first allowed row on
+    int64_t remove_chunk = 65536;    // IVR_REMOVE_CHUNK_ROWS: source rows per step through the bounce buffer (a multiple of 64, read at creation)
+    DevBuf<uint64_t> rm_word;        // DEV [groups of the tail + 1]: bit i = row 64 g + i is stored and stays
+    DevBuf<uint32_t> rm_kept;        // DEV [groups of the tail + 1]: kept rows of each group, then their prefix inside a block of 1024 groups
+    DevBuf<uint32_t> rm_top;         // DEV [blocks of 1024 groups]: kept rows of each block, then their exclusive prefix
+    DevBuf<uint32_t> rm_state;       // DEV: first removed row of the tail (0xffffffff: none), kept rows of the tail, then the kept rows in
+                                     // front of every unit of 16 groups: what the host reads back to plan the walk
+    DevBuf<float> rm_bounce;         // DEV [remove_chunk / 16 + 1 tiles]: the survivors of one step, already tiled for their destination
+    DevBuf<uint4> rm_bounce16;       // the same tiles of the bf16 scan copy
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

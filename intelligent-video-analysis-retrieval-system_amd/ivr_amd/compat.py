@@ -16,9 +16,10 @@ meanings, return shapes and error behaviour, and route the arithmetic to libivr_
   faiss.IndexFlatIP / faiss.normalize_L2                   ivr_amd.index.IndexFlatIP / normalize_L2
 
 Out of scope here, as in SURVEY.md section 8: HDF5/LZ4 container, thumbnails, resume, LLM, GUI, network.
-The index container written by `create_unified_index` is a plain .npz (vectors + JSON metadata).
+The index container written by `create_unified_index` is a plain .npz (vectors + JSON metadata + JSON file hashes).
 """
 import csv
+import hashlib
 import json
 import os
 import threading
@@ -31,7 +32,7 @@ import torch
 
 from . import config as C
 from .dedup import DedupState
-from .index import FlatIPIndex, IDSelectorBitmap, SearchParameters, count_nonfinite_and_normalize
+from .index import FlatIPIndex, IDSelectorBatch, IDSelectorBitmap, SearchParameters, count_nonfinite_and_normalize
 from .tower import Tower
 from .weights import from_hf_state_dict, make_weights
 
@@ -624,6 +625,7 @@ class UnifiedIndex:
         self.metadata_cache: Dict[int, Dict[str, Any]] = {}
         self._vectors = None
         self.index_file = None
+        self.file_hashes: Dict[str, str] = {}               # path relative to the keyframes directory -> _calculate_file_hash
 
     def __enter__(self):
         return self
@@ -644,6 +646,25 @@ class UnifiedIndex:
                     found.append(os.path.join(root, n))
         return sorted(found)                                # deterministic row order (hard part 7)
 
+    @staticmethod
+    def _calculate_file_hash(file_path):
+        """unified_index.py:751-757: SHA-256 of the file's bytes, first 16 hex characters."""
+        hasher = hashlib.sha256()
+        with open(file_path, "rb") as f:
+            for chunk in iter(lambda: f.read(8192), b""):
+                hasher.update(chunk)
+        return hasher.hexdigest()[:16]
+
+    @staticmethod
+    def _npz_path(index_file):
+        return index_file if index_file.endswith(".npz") else index_file + ".npz"
+
+    @staticmethod
+    def _save_npz(path, V, metas, csv_mappings, file_hashes):
+        as_bytes = lambda obj: np.frombuffer(json.dumps(obj).encode(), dtype=np.uint8)
+        # file_hashes: what the reference keeps in its container for incremental updates (unified_index.py:1832-1862)
+        np.savez(path, vectors=V, metadata=as_bytes(metas), csv_mappings=as_bytes(csv_mappings or {}), file_hashes=as_bytes(file_hashes))
+
     def create_unified_index(self, keyframes_dir, clip_processor, output_file, csv_mappings=None, progress_callback=None,
                              resume_from_existing=False, chunk_size=1000):
         """unified_index.py:94 with the batch-1 thread pool (:759-812) replaced by whole-chunk GPU batches
@@ -656,7 +677,7 @@ class UnifiedIndex:
         stats["total_files"] = len(files)
         # rows go straight into one preallocated array (the reference's 2.2M-file build, logs/system_20250821.log:4, is 6.9 GB of
         # 768-d rows: no per-row Python objects, no final np.stack copy)
-        V, nrows, metas = None, 0, []
+        V, nrows, metas, hashes = None, 0, [], {}
         for c0 in range(0, len(files), chunk_size):
             chunk = files[c0:c0 + chunk_size]
             try:
@@ -686,6 +707,7 @@ class UnifiedIndex:
                 nrows += len(kept)
             for p in kept:
                 rel = os.path.relpath(p, keyframes_dir)
+                hashes[rel] = self._calculate_file_hash(p)
                 folder = os.path.dirname(rel) or os.path.basename(os.path.normpath(keyframes_dir))
                 metas.append({"folder_name": folder, "image_name": os.path.basename(p), "frame_id": _frame_id_of(p),
                               "file_path": p, "vector_index": len(metas)})
@@ -694,20 +716,19 @@ class UnifiedIndex:
             if progress_callback:
                 progress_callback(stats["processed_files"], len(files))
         V = V[:nrows] if V is not None else np.zeros((0, 1), np.float32)
-        np.savez(output_file if output_file.endswith(".npz") else output_file + ".npz", vectors=V,
-                 metadata=np.frombuffer(json.dumps(metas).encode(), dtype=np.uint8),
-                 csv_mappings=np.frombuffer(json.dumps(csv_mappings or {}).encode(), dtype=np.uint8))
-        out = output_file if output_file.endswith(".npz") else output_file + ".npz"
+        out = self._npz_path(output_file)
+        self._save_npz(out, V, metas, csv_mappings, hashes)
         stats["vectors_count"] = len(V)
         stats["file_size_mb"] = os.path.getsize(out) / 1e6
         stats["build_time"] = time.time() - t0
-        self._install(V, metas, out)
+        self._install(V, metas, out, hashes)
         return stats
 
     build_index = create_unified_index                      # README.md:124-136 alias
 
-    def _install(self, V, metas, path):
+    def _install(self, V, metas, path, file_hashes=None):
         with self.lock:
+            self.file_hashes = dict(file_hashes or {})
             # no second host copy of the rows: `.vectors` (a reference attribute) is rebuilt from the device index on first access
             # (host copy + fp32 tiles + bf16 copy were 2.5x the rows, 17 GB at the reference's 2.2M x 768)
             self._vectors = None
@@ -732,11 +753,97 @@ class UnifiedIndex:
         return self._vectors
 
     def load_unified_index(self, index_file):
-        path = index_file if index_file.endswith(".npz") else index_file + ".npz"
+        path = self._npz_path(index_file)
         z = np.load(path, allow_pickle=False)
         metas = json.loads(bytes(z["metadata"]).decode())
-        self._install(z["vectors"], metas, path)
+        # a file written before the hashes were stored: none, as the reference's _get_stored_file_hashes returns {} (:1475-1481)
+        hashes = json.loads(bytes(z["file_hashes"]).decode()) if "file_hashes" in z.files else {}
+        self._install(z["vectors"], metas, path, hashes)
         return {"vectors_count": self._nvectors, "metadata_count": len(metas), "index_file": path}
+
+    def incremental_update(self, keyframes_dir, clip_processor, index_file):
+        """unified_index.py:415-478: bring the loaded index up to date with `keyframes_dir` without re-encoding what did not change.
+        Files are compared by hash (_calculate_file_hash) with the hashes stored at build time.  Returns the reference's stats keys.
+        When (new + modified) / files exceeds incremental_threshold (config.incremental_threshold, else the reference's 0.1) the
+        index is left alone and rebuild_required is True; an index without stored hashes therefore always asks for a rebuild.
+        Otherwise the changes are applied - the reference's _perform_incremental_update (:1505) only logs: new and modified files are
+        encoded in ONE encode_images call, modified rows rewritten in place, deleted rows removed with one remove_ids (the rows above
+        them move down, metadata_list and vector_index with them), new rows appended in sorted-path order.  Deletions are applied even
+        when nothing is new or modified.  A non-empty index_file is rewritten afterwards; "" updates in memory only."""
+        t0 = time.time()
+        stats = {"scanned_files": 0, "new_files": 0, "modified_files": 0, "deleted_files": 0, "update_time": 0.0,
+                 "rebuild_required": False}
+        if not self.is_loaded:
+            self.load_unified_index(index_file)
+        files = self._scan_files(keyframes_dir)
+        if not files:
+            raise ValueError(f"incremental_update: no .jpg files under {keyframes_dir!r} (an empty directory would delete every row; "
+                             "build a new index instead)")
+        with self.lock:
+            current = {os.path.relpath(p, keyframes_dir): self._calculate_file_hash(p) for p in files}
+            stored = self.file_hashes
+            row_of = {os.path.relpath(m["file_path"], keyframes_dir): i for i, m in enumerate(self.metadata_list) if m.get("file_path")}
+            new = [r for r in current if r not in stored]                                       # sorted-path order, as `files`
+            modified = [r for r in current if r in stored and stored[r] != current[r]]
+            deleted = [r for r in stored if r not in current]
+            stats.update(scanned_files=len(files), new_files=len(new), modified_files=len(modified), deleted_files=len(deleted))
+            threshold = getattr(self.config, "incremental_threshold", 0.1) if self.config is not None else 0.1
+            if (len(new) + len(modified)) / len(current) > threshold:
+                stats["rebuild_required"] = True
+                return stats
+            if not (new or modified or deleted):
+                stats["update_time"] = time.time() - t0
+                return stats
+            # a modified file whose row is missing is appended like a new one; a deleted one without a row only loses its hash
+            new = sorted(new + [r for r in modified if r not in row_of])
+            rewrite = [r for r in modified if r in row_of]
+            paths = [os.path.join(keyframes_dir, r) for r in rewrite + new]
+            feats = np.zeros((0, self.faiss_index.d), np.float32)
+            if paths:
+                feats = np.asarray(clip_processor.encode_images(paths, validate_files=False, show_progress=False), dtype=np.float32)
+                if feats.ndim != 2 or len(feats) != len(paths):
+                    raise RuntimeError(f"incremental_update: {len(paths)} changed files gave {len(feats)} embeddings")
+            # the rows as the .npz holds them (not normalised), edited alongside, so that a reload adds what a rebuild would add
+            path = self._npz_path(index_file) if index_file else None
+            raw, csv_mappings = None, {}
+            if path and os.path.exists(path):
+                z = np.load(path, allow_pickle=False)
+                csv_mappings = json.loads(bytes(z["csv_mappings"]).decode()) if "csv_mappings" in z.files else {}
+                if len(z["vectors"]) == self.faiss_index.ntotal:
+                    raw = np.array(z["vectors"], dtype=np.float32)
+            for j, r in enumerate(rewrite):
+                self.faiss_index.write(row_of[r], feats[j:j + 1], normalize=True)
+                if raw is not None:
+                    raw[row_of[r]] = feats[j]
+            gone = sorted(row_of[r] for r in deleted if r in row_of)
+            if gone:
+                removed = self.faiss_index.remove_ids(IDSelectorBatch(np.asarray(gone, np.int64)))
+                if removed != len(gone):
+                    raise RuntimeError(f"incremental_update: removed {removed} rows, expected {len(gone)}")
+                dropped = set(gone)
+                self.metadata_list = [m for i, m in enumerate(self.metadata_list) if i not in dropped]
+                if raw is not None:
+                    raw = np.delete(raw, gone, axis=0)
+            if new:
+                self.faiss_index.add(feats[len(rewrite):], normalize=True)
+                if raw is not None:
+                    raw = np.concatenate([raw, feats[len(rewrite):]])
+                for r in new:
+                    p = os.path.join(keyframes_dir, r)
+                    folder = os.path.dirname(r) or os.path.basename(os.path.normpath(keyframes_dir))
+                    self.metadata_list.append({"folder_name": folder, "image_name": os.path.basename(p), "frame_id": _frame_id_of(p),
+                                               "file_path": p, "vector_index": 0})
+            for i, m in enumerate(self.metadata_list):
+                m["vector_index"] = i
+            self.file_hashes = current
+            self.metadata_cache = {}
+            self._vectors = None
+            self._nvectors = int(self.faiss_index.ntotal)
+            if path:
+                self._save_npz(path, raw if raw is not None else self.vectors, self.metadata_list, csv_mappings, self.file_hashes)
+                self.index_file = path
+        stats["update_time"] = time.time() - t0
+        return stats
 
     def _get_metadata_cached(self, idx):
         idx = int(idx)
@@ -827,6 +934,12 @@ class UnifiedBuilderIntegration:
     def load_unified_index_fast(self, index_file):
         self.unified_index = load_optimized_index(index_file)
         return True
+
+    def incremental_update_fast(self, keyframes_dir):
+        """unified_builder.py:293-339: the loaded index brought up to date in memory ("" as the index file, :320-324)."""
+        if not self.unified_index:
+            raise ValueError("Unified index not loaded. Call load_unified_index_fast() first.")
+        return self.unified_index.incremental_update(keyframes_dir, self.system.clip_processor, "")
 
     def search_unified_fast(self, query_vector, k: int = 50, similarity_threshold: float = 0.0):
         if not self.unified_index:

@@ -362,6 +362,27 @@ class FlatIPIndex:
                                                        _ffi.stream_ptr()), "ivr_index_reconstruct")
         return out.cpu().numpy()
 
+    def reconstruct(self, i):
+        """faiss reconstruct(i): the stored row i as a float32 [d] numpy array."""
+        return self.reconstruct_n(int(i), 1)[0]
+
+    def remove_ids(self, sel, id_base=0):
+        """faiss remove_ids(sel): delete every stored row whose id (id_base + row) the selector names and return how many were removed.
+        sel: an IDSelectorRange / IDSelectorBatch / IDSelectorBitmap, or an integer numpy array / torch tensor of ids (wrapped in an
+        IDSelectorBatch, as faiss's Python wrapper does).  The surviving rows keep their order and their bits and move down, so the
+        ids above a removed row shift; the capacity stays.  Synchronises the current stream once (not graph-capturable)."""
+        if isinstance(sel, (np.ndarray, torch.Tensor)):
+            sel = IDSelectorBatch(sel)
+        if not isinstance(sel, _IDSelector):
+            raise ValueError(f"remove_ids: sel must be an IDSelectorRange / IDSelectorBatch / IDSelectorBitmap or an integer array, "
+                             f"got {type(sel).__name__}")
+        n = C.c_int64(0)
+        with torch.cuda.device(self.device):
+            f = sel._filter(self.device)
+            _ffi.check(self._lib.ivr_index_remove_ids(self._h, int(id_base), C.byref(f), C.byref(n), _ffi.stream_ptr()),
+                       "ivr_index_remove_ids")
+        return int(n.value)
+
     def reset(self):
         with torch.cuda.device(self.device):
             _ffi.check(self._lib.ivr_index_reset(self._h), "ivr_index_reset")

@@ -12,7 +12,7 @@ collective is the right shape; no other exchange exists on this path.
 The class is agnostic of how a shard is searched: `local` only needs
 `search_device(q, k, normalize=, id_base=) -> (D, I)` tensors, `add`, `ntotal` (and
 `range_search_device(q, radius, normalize=, id_base=) -> (lims, D, I, total)` for range_search; both with `sel=` for a filtered
-search).  On GPUs that
+search; `remove_ids(sel, id_base=) -> int` for remove_ids).  On GPUs that
 is `ivr_amd.index.FlatIPIndex`; the world_size-2 gloo tests on CPU plug the oracle in.
 """
 import numpy as np
@@ -121,6 +121,16 @@ class ShardedIndex:
     @property
     def ntotal(self):
         return int(sum(self._counts))
+
+    def remove_ids(self, sel):
+        """faiss remove_ids(sel) over all shards: sel names GLOBAL ids (a selector, or an integer array as FlatIPIndex.remove_ids takes
+        it).  Every rank removes its own rows, then the counts are agreed on again (sync_counts: the one collective, as after
+        add_local), so each shard's id_base follows the rows that left the shards below it.  Returns the global number of removed
+        rows, identical on every rank: the difference of the summed counts.  Shards are not re-balanced."""
+        before = self.ntotal
+        self.local.remove_ids(sel, id_base=self.id_base)
+        self.sync_counts()
+        return before - self.ntotal
 
     # -- search ------------------------------------------------------------------------------
     @staticmethod

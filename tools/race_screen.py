@@ -104,6 +104,32 @@ for (rows, d, nq, k) in ((300_001, 512, 300, 10), (120_000, 768, 1000, 5), (70_0
     torch.cuda.synchronize()
     print(f"{'large-batch' if nq > 64 else 'ring-scan'} search {rows} x {d}, {nq} queries: {it + 1} launches reproduced")
     idx.close()
+# row removal (search_index.hip: a step's place launch, or its direct gather, must not overwrite rows another workgroup still has to read):
+# every repeat must leave exactly the surviving rows, with the walk in many small steps and in the default ones
+import numpy as np  # noqa: E402
+for (rows, d, chunk) in ((120_001, 256, "4096"), (200_003, 128, None)):
+    g = torch.Generator(device="cuda").manual_seed(rows)
+    master = torch.randn((rows, d), generator=g, device="cuda")
+    if chunk:
+        os.environ["IVR_REMOVE_CHUNK_ROWS"] = chunk
+    idx = FlatIPIndex(d, capacity=rows)
+    os.environ.pop("IVR_REMOVE_CHUNK_ROWS", None)
+    rng = np.random.default_rng(rows)
+    for it in range(max(10, iters // 10)):
+        gone = np.flatnonzero(rng.random(rows) < (0.02, 0.3, 0.6)[it % 3])
+        idx.reset()
+        idx.add(master)
+        with torch.cuda.stream(side):
+            junk_b.copy_(junk_a, non_blocking=True)
+        removed = idx.remove_ids(gone)
+        keep = np.ones(rows, bool)
+        keep[gone] = False
+        if removed != len(gone) or not np.array_equal(idx.reconstruct_n(0, idx.ntotal), master.cpu().numpy()[keep]):
+            bad += 1
+            print(f"MISMATCH remove_ids rows={rows} d={d} chunk={chunk} iteration {it}")
+    torch.cuda.synchronize()
+    print(f"remove_ids {rows} x {d}, chunk rows {chunk or 'default'}: {it + 1} removals left exactly the surviving rows")
+    idx.close()
 for name, batch in (("l14", 24), ("dino", 64), ("b32", 256)):
     cfg = {"b32": C.CLIP_VIT_B32, "l14": C.CLIP_VIT_L14, "dino": C.DINO_VIT_S16}[name]
     tw = Tower(cfg, make_weights(cfg, 3), max_batch=batch)
