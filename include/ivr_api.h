@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IVR_API_VERSION 9
+#define IVR_API_VERSION 10
 #define IVR_MAX_K 2048          /* reference: k=50 default, SearchOptions.limit <= 1000 (system.py:91) */
 
 typedef enum ivr_status {
@@ -238,7 +238,7 @@ int ivr_l2_normalize(ivr_ctx *ctx, float *x /*DEV*/, int64_t n, int d, int32_t *
  */
 int ivr_index_create(ivr_ctx *ctx, int d, int64_t capacity_rows, ivr_index **out);
 int ivr_index_destroy(ivr_index *idx);
-int ivr_index_reset(ivr_index *idx);                        /* ntotal = 0 */
+int ivr_index_reset(ivr_index *idx);                        /* ntotal = 0; plain or id-mapped is undecided again */
 int64_t ivr_index_ntotal(ivr_index *idx);
 int ivr_index_dim(ivr_index *idx);
 int64_t ivr_index_capacity(ivr_index *idx);
@@ -308,6 +308,36 @@ int ivr_index_range_search_filtered(ivr_index *idx, const float *q /*DEV*/, int 
  * captured on this index before the call holds the old ntotal.  One stream at a time per handle, as for every call. */
 int ivr_index_remove_ids(ivr_index *idx, int64_t id_base, const ivr_id_filter *filter /*HOST*/, int64_t *n_removed /*HOST, may be NULL*/,
                          ivr_stream stream);
+
+/* ---- stable external ids (faiss IndexIDMap2 / add_with_ids) --------------------------------------
+ * The reference keys its metadata by FAISS id (core.py:722-723: id_to_metadata / metadata_to_id) and looks rows up by it
+ * (search_by_id, core.py:932-958).  With row positions as ids every key above a removed row goes stale; an id-mapped index
+ * carries caller-chosen int64 labels with its rows instead: a device table ids[capacity], ids[r] = the label of stored row r.
+ *
+ * An index becomes id-mapped by ivr_index_add_with_ids while it is empty and stays so until ivr_index_reset; a plain index (the
+ * one ivr_index_add makes) is not touched by any of this.  ivr_index_add_with_ids on a non-empty plain index and ivr_index_add
+ * on an id-mapped index (faiss IndexIDMap::add throws too) return IVR_ERR_STATE; n == 0 on an empty index only decides the mode.
+ * ids: DEV int64 [n], every id >= 0 (-1 labels an unused result slot and the filters never match a negative id; the caller
+ * checks, the ids are not read on the host).  Duplicate ids are allowed, as in faiss: every row is treated on its own.  The
+ * table grows with the rows and keeps its contents; ivr_index_write and ivr_index_write_ring replace vectors and leave ids alone.
+ *
+ * On an id-mapped index every entry point above keeps its signature, and
+ *  - id_base is ignored;
+ *  - labels written to I are ids[row], unused slots stay -1; order and ties follow the storage order as before (equal scores:
+ *    the lower row first whatever its label; range-search results of a query in ascending row order);
+ *  - a filter names stored ids.  One pass over the table (8 bytes read per stored row, one bit written) turns it into a row
+ *    bitmap, then the masked kernels run over the WHOLE index: unlike on a plain index a narrow id range does not narrow the
+ *    scan.  A byte of filter->bits is read only for a stored id inside [max(lo, 0), min(hi, nbits)).  Still enqueue-only: no
+ *    host synchronisation, and after ivr_index_reserve_search no allocation until the index grows;
+ *  - ivr_index_remove_ids compacts the table with the rows; ids at or above the new ntotal are never read. */
+int ivr_index_add_with_ids(ivr_index *idx, const float *rows /*DEV*/, const int64_t *ids /*DEV*/, int64_t n, int normalize,
+                           ivr_stream stream);
+int ivr_index_has_ids(ivr_index *idx);                      /* 1: id-mapped, 0: plain (or NULL) */
+/* ids[start .. start + n) -> out (faiss id_map[start:start+n]); start + n <= ntotal; IVR_ERR_STATE on a plain index. */
+int ivr_index_get_ids(ivr_index *idx, int64_t start, int64_t n, int64_t *out /*DEV*/, ivr_stream stream);
+/* rows[i] = the lowest row that holds id keys[i], or -1 (what IndexIDMap2::reconstruct and the reference's search_by_id,
+ * core.py:932-958, need).  A scan of the whole table per call, O(n x ntotal) compares: meant for a handful of keys. */
+int ivr_index_find_ids(ivr_index *idx, const int64_t *keys /*DEV*/, int64_t n, int64_t *rows /*DEV*/, ivr_stream stream);
 
 /* Merge per-shard candidate lists (the reference's concat + sort of peer results, system.py:1744-1746):
  * D_parts/I_parts DEV [parts, nq, k] with global ids, parts ordered by ascending id range. */

@@ -572,10 +572,10 @@ int exact_tail(ivr_index *x, const View &v, const float *gmax, const float *qtil
         IVR_LAUNCH_CHECK();
     }
     IvrProf prof("select_final", s, counted ? (double)waves * kGroupRows * 8 : 0.0, true);
-    SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base);
+    SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base, v.ids);
     o.skip = skip;
     o.la = la;
-    launch_select<OUT_DI>(SrcKeys{x->cand, (int64_t)k * kGroupRows}, nqc, k, o, s);
+    launch_select_rows(SrcKeys{x->cand, (int64_t)k * kGroupRows}, nqc, k, o, s);
     IVR_LAUNCH_CHECK();
     return IVR_OK;
 }
@@ -617,9 +617,9 @@ int search_big(ivr_index *x, const View &v, int q0, int nqc, int k, float *D, in
     }
     {
         IvrProf prof("select_final", s, (double)nqc * kp * 16 * 8, true);
-        SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base);
+        SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base, v.ids);
         o.vf = vf;
-        launch_select<OUT_DI>(SrcKeys{x->cand, (int64_t)kp * 16}, nqc, k, o, s);
+        launch_select_rows(SrcKeys{x->cand, (int64_t)kp * 16}, nqc, k, o, s);
         IVR_LAUNCH_CHECK();
     }
     // exact pass over the listed queries; its group maxima reuse the tile-maxima buffer (read for the last time just above)
@@ -699,9 +699,9 @@ int search_view(ivr_index *x, const View &v, const float *q, int nq, int k, int 
             }
             {
                 IvrProf prof("select_final", s, (double)waves * kGroupRows * 8, true);
-                SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base);
+                SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base, v.ids);
                 o.vf = vf;
-                launch_select<OUT_DI>(SrcKeys{x->cand, (int64_t)kp * kGroupRows}, nqc, k, o, s);
+                launch_select_rows(SrcKeys{x->cand, (int64_t)kp * kGroupRows}, nqc, k, o, s);
                 IVR_LAUNCH_CHECK();
             }
             // the exact pass below redoes the queries whose check failed: every kernel of it exits at once when nothing is flagged
@@ -775,7 +775,7 @@ int ivr_index_search_filtered(ivr_index *x, const float *q, int nq, int k, int n
     IVR_REQUIRE(x && q && D && I, "ivr_index_search: NULL argument");
     IVR_REQUIRE(nq >= 1, "ivr_index_search: nq=%d", nq);
     IVR_REQUIRE(k >= 1 && k <= IVR_MAX_K, "ivr_index_search: k=%d outside [1,%d]", k, IVR_MAX_K);
-    return with_view(x, id_base, filter, "ivr_index_search_filtered",
+    return with_view(x, id_base, filter, (hipStream_t)stream, "ivr_index_search_filtered",
                      [&](const View &v) { return search_view(x, v, q, nq, k, normalize_q, D, I, (hipStream_t)stream); });
 }
 

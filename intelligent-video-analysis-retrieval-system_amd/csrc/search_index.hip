@@ -1,6 +1,6 @@
 // The flat index object (ivr_index) and its storage: rows are kept in tiles of 16 rows, inside a tile in the order
 // [d/4][16 rows][4 floats] (the MFMA operand layout that search.hip scans, see there), with a bf16 scan copy alongside.  Create /
-// destroy / reset / add / write / reconstruct / remove_ids, the tiling kernels (also used for the queries of a search) and the grow-only
+// destroy / reset / add / add_with_ids / write / reconstruct / remove_ids, the tiling kernels (also used for the queries of a search) and the grow-only
 // workspace buffers.
 #include "ivr_common.h"
 #include "search_internal.h"
@@ -425,6 +425,21 @@ __global__ __launch_bounds__(256) void remove_place_kernel(RemoveMove mv) {
     if (mv.data16) copy_lane(mv.bounce16 + j * mv.pstride * 64 + lane, mv.data16 + tile * mv.pstride * 64 + lane, mv.pieces);
 }
 
+// Id table of an id-mapped index: the ids of the kept rows from the first removed row on, in row order, out of place into `moved`
+// (kept row number q >= first goes to moved[q - first]; an in-place pass would overwrite ids that other workgroups have yet to
+// read).  One thread per row from the group of the first removed row on; the host copies moved back to ids[first ..).
+__global__ __launch_bounds__(256) void remove_ids_gather_kernel(RemovePlan p, const int64_t *__restrict__ ids, int64_t *__restrict__ moved,
+                                                                uint32_t first) {
+    const int64_t r = (int64_t)(first / kGroupRows) * kGroupRows + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= p.nrows) return;
+    const int64_t g = r / kGroupRows;
+    const int i = (int)(r % kGroupRows);
+    const uint64_t w = p.word[g];
+    if (!((w >> i) & 1ull)) return;
+    const uint32_t dst = kept_before(p, g) + (uint32_t)__popcll(w & ((1ull << i) - 1));
+    if (dst >= first) moved[dst - first] = ids[r];
+}
+
 // the slots slot0 .. 15 of one tile zero in both layouts: one wave
 __global__ __launch_bounds__(64) void zero_slots_kernel(float4 *tile, uint4 *tile16, int slot0, int kchunks, int pstride) {
     const int lane = threadIdx.x;
@@ -449,6 +464,13 @@ int index_alloc(ivr_index *x, int64_t rows) {
         IVR_HIP(hipMalloc(&nd16, (size_t)tile16_bytes(x, ivr_round_up(rows, 256))));
         IVR_HIP(hipMemset(nd16, 0, (size_t)tile16_bytes(x, ivr_round_up(rows, 256))));
     }
+    int64_t *nids = nullptr;
+    if (x->has_ids) {
+        IVR_HIP(hipMalloc(&nids, (size_t)rows * sizeof(int64_t)));
+        if (x->ids && x->ntotal > 0) IVR_HIP(hipMemcpy(nids, x->ids, (size_t)x->ntotal * sizeof(int64_t), hipMemcpyDeviceToDevice));
+    }
+    if (x->ids) IVR_HIP(hipFree(x->ids));
+    x->ids = nids;
     if (x->data) {
         if (x->ntotal > 0) {
             IVR_HIP(hipMemcpy(nd, x->data, (size_t)tile_bytes(x, ivr_round_up(x->ntotal, 16)), hipMemcpyDeviceToDevice));
@@ -487,6 +509,42 @@ int allocate_all(DevSizes bufs, bool zero) {
     return IVR_OK;
 }
 
+// ivr_index_add (ids == NULL) and ivr_index_add_with_ids: the mode check, growth, the tiling launch and, with ids, one device-to-device
+// copy of the labels behind the table's stored part
+int index_append(ivr_index *x, const float *rows, const int64_t *ids, int64_t n, int normalize, hipStream_t s, const char *what) {
+    IVR_REQUIRE(x && (rows || n == 0), "%s: NULL argument", what);
+    IVR_REQUIRE(n >= 0, "%s: n=%lld", what, (long long)n);
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (ids && !x->has_ids && x->ntotal > 0)
+        return ivr_fail(IVR_ERR_STATE, "%s: the index holds %lld rows without ids (ids are chosen while it is empty, or after ivr_index_reset)",
+                        what, (long long)x->ntotal);
+    if (!ids && x->has_ids)
+        return ivr_fail(IVR_ERR_STATE, "%s: the index is id-mapped: add rows with ivr_index_add_with_ids (or ivr_index_reset first)", what);
+    IVR_HIP(hipSetDevice(x->ctx->device));
+    const bool first_ids = ids && !x->has_ids;
+    if (x->ntotal + n > x->cap || first_ids) {
+        IVR_REQUIRE(x->ntotal + n < (1ll << 32) - 64, "%s: index would exceed 2^32 rows", what);
+        // growing re-allocates: wait for work that may still read the old buffer
+        IVR_HIP(hipDeviceSynchronize());
+        if (x->ntotal + n > x->cap) {
+            x->has_ids = ids != nullptr;
+            int rc = index_alloc(x, std::max<int64_t>(x->ntotal + n, x->cap + x->cap / 2));
+            if (rc != IVR_OK) {
+                if (first_ids) x->has_ids = false;
+                return rc;
+            }
+        } else {                                 // an empty index becomes id-mapped inside its capacity: the table alone
+            IVR_HIP(hipMalloc(&x->ids, (size_t)x->cap * sizeof(int64_t)));
+            x->has_ids = true;
+        }
+    }
+    int rc = ivr_launch_tile_rows(x, x->data, rows, x->ntotal, n, normalize, nullptr, s);
+    if (rc != IVR_OK) return rc;
+    if (ids && n > 0) IVR_HIP(hipMemcpyAsync(x->ids + x->ntotal, ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    x->ntotal += n;
+    return IVR_OK;
+}
+
 }  // namespace
 
 int ivr_reserve(DevSizes bufs, bool zero) {
@@ -502,21 +560,21 @@ int ivr_reserve(DevSizes bufs, bool zero) {
 }
 
 View ivr_make_view(const ivr_index *x, int64_t id_base, const ivr_id_filter *f, RowMask &m) {
-    if (!f) return View{x->data, x->data16, x->ntotal, ivr_ceil_div(x->ntotal, kGroupRows), id_base, nullptr};
+    if (!f) return View{x->data, x->data16, x->ntotal, ivr_ceil_div(x->ntotal, kGroupRows), id_base, nullptr, nullptr};
     __int128 lo = f->lo, hi = f->hi;
     if (f->bits) {                              // ids the bitmap covers: [0, nbits)
         lo = std::max<__int128>(lo, 0);
         hi = std::min<__int128>(hi, f->nbits);
     }
     const __int128 rlo = std::max<__int128>(lo - id_base, 0), rhi = std::min<__int128>(hi - id_base, x->ntotal);
-    if (rlo >= rhi) return View{x->data, x->data16, 0, 0, id_base, &m};
+    if (rlo >= rhi) return View{x->data, x->data16, 0, 0, id_base, &m, nullptr};
     const int64_t b0 = (int64_t)rlo / 256 * 256, n = (int64_t)rhi - b0;
     m.lo = (int64_t)rlo - b0;
     m.hi = n;
     m.bits = f->bits;
     m.bit0 = id_base + b0;
     return View{x->data + b0 * x->dp, x->data16 ? x->data16 + (b0 / 16) * x->pieces * 64 : nullptr, n, ivr_ceil_div(n, kGroupRows),
-                id_base + b0, &m};
+                id_base + b0, &m, nullptr};
 }
 
 int ivr_launch_tile_rows(ivr_index *x, float *dst, const float *src, int64_t start, int64_t n, int normalize, int32_t *nonfinite,
@@ -581,6 +639,7 @@ int ivr_index_destroy(ivr_index *x) {
     if (!x) return IVR_OK;
     if (x->data) (void)hipFree(x->data);
     if (x->data16) (void)hipFree(x->data16);
+    if (x->ids) (void)hipFree(x->ids);
     delete x;                        // the workspace buffers free themselves
     return IVR_OK;
 }
@@ -596,6 +655,14 @@ int ivr_index_reset(ivr_index *x) {
         IVR_HIP(hipMemset(x->maxdelta, 0, 4));
     }
     x->ntotal = 0;
+    // the mode is undecided again: the next ivr_index_add makes a plain index, the next ivr_index_add_with_ids an id-mapped one
+    x->has_ids = false;
+    if (x->ids) {
+        int64_t *old = x->ids;
+        x->ids = nullptr;
+        IVR_HIP(hipDeviceSynchronize());         // work that may still read the table
+        IVR_HIP(hipFree(old));
+    }
     return IVR_OK;
 }
 
@@ -604,21 +671,13 @@ int ivr_index_dim(ivr_index *x) { return x ? x->d : 0; }
 int64_t ivr_index_capacity(ivr_index *x) { return x ? x->cap : 0; }
 
 int ivr_index_add(ivr_index *x, const float *rows, int64_t n, int normalize, ivr_stream stream) {
-    IVR_REQUIRE(x && (rows || n == 0), "ivr_index_add: NULL argument");
-    IVR_REQUIRE(n >= 0, "ivr_index_add: n=%lld", (long long)n);
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    if (x->ntotal + n > x->cap) {
-        IVR_REQUIRE(x->ntotal + n < (1ll << 32) - 64, "ivr_index_add: index would exceed 2^32 rows");
-        // growing re-allocates: wait for work that may still read the old buffer
-        IVR_HIP(hipDeviceSynchronize());
-        int rc = index_alloc(x, std::max<int64_t>(x->ntotal + n, x->cap + x->cap / 2));
-        if (rc != IVR_OK) return rc;
-    }
-    int rc = ivr_launch_tile_rows(x, x->data, rows, x->ntotal, n, normalize, nullptr, (hipStream_t)stream);
-    if (rc != IVR_OK) return rc;
-    x->ntotal += n;
-    return IVR_OK;
+    return index_append(x, rows, nullptr, n, normalize, (hipStream_t)stream, "ivr_index_add");
+}
+
+int ivr_index_add_with_ids(ivr_index *x, const float *rows, const int64_t *ids, int64_t n, int normalize, ivr_stream stream) {
+    IVR_REQUIRE(ids || n == 0, "ivr_index_add_with_ids: NULL ids");
+    static const int64_t none = 0;               // n == 0 still decides the mode of an empty index
+    return index_append(x, rows, ids ? ids : &none, n, normalize, (hipStream_t)stream, "ivr_index_add_with_ids");
 }
 
 int ivr_index_write(ivr_index *x, int64_t start, const float *rows, int64_t n, int normalize, ivr_stream stream) {
@@ -664,10 +723,11 @@ int ivr_index_remove_ids(ivr_index *x, int64_t id_base, const ivr_id_filter *fil
     IVR_REQUIRE(x, "ivr_index_remove_ids: NULL index");
     IVR_REQUIRE(filter, "ivr_index_remove_ids: NULL filter (there is no \"remove everything\" default)");
     if (n_removed) *n_removed = 0;
-    return with_view(x, id_base, filter, "ivr_index_remove_ids", [&](const View &v) -> int {
+    return with_view(x, id_base, filter, (hipStream_t)stream, "ivr_index_remove_ids", [&](const View &v) -> int {
         if (v.ntotal == 0) return IVR_OK;                       // no stored row has an allowed id
         hipStream_t s = (hipStream_t)stream;
-        const int64_t row0 = v.id_base - id_base;               // first row of the tail: the 256-row block of the first allowed row
+        // first row of the tail: the 256-row block of the first allowed row; an id-mapped index is filtered as a whole (row 0)
+        const int64_t row0 = x->has_ids ? 0 : v.id_base - id_base;
         RemovePlan p;
         p.nrows = x->ntotal - row0;
         p.ngroups = ivr_ceil_div(p.nrows, kGroupRows);
@@ -698,6 +758,19 @@ int ivr_index_remove_ids(ivr_index *x, int64_t id_base, const ivr_id_filter *fil
         rc = ivr_reserve({{&x->rm_bounce, (size_t)tile_bytes(x, (chunk_units * unit * 4 + 1) * 16)},   // + 1: destinations start inside a tile
                           {&x->rm_bounce16, x->scan16 ? (size_t)tile16_bytes(x, (chunk_units * unit * 4 + 1) * 16) : 0}});
         if (rc != IVR_OK) return rc;
+        if (x->has_ids && (int64_t)state[1] > (int64_t)first) {
+            // the id table follows the rows: the surviving ids from the first removed row on, gathered out of place and copied back
+            const int64_t from = (int64_t)(first / kGroupRows) * kGroupRows, moved = (int64_t)state[1] - first;
+            rc = ivr_reserve({{&x->ids_moved, (size_t)moved * sizeof(int64_t)}});
+            if (rc != IVR_OK) return rc;
+            {
+                IvrProf prof("remove_ids_gather", s, (double)(p.nrows - from) * 8 + (double)moved * 8, true);
+                hipLaunchKernelGGL(remove_ids_gather_kernel, dim3((unsigned)ivr_ceil_div(p.nrows - from, 256)), dim3(256), 0, s, p,
+                                   x->ids + row0, (int64_t *)x->ids_moved, first);
+                IVR_LAUNCH_CHECK();
+            }
+            IVR_HIP(hipMemcpyAsync(x->ids + row0 + first, (int64_t *)x->ids_moved, (size_t)moved * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        }
         RemoveMove mv;
         mv.data = reinterpret_cast<float4 *>(x->data + row0 * x->dp);
         mv.data16 = x->scan16 ? x->data16 + (row0 / 16) * x->pieces * 64 : nullptr;

@@ -1,5 +1,6 @@
 // The one internal header of the flat index: search_index.hip (the index object and its storage), search.hip (group-maximum scans and
-// the top-k driver), search_range.hip (range search) and search_scanq.hip (the large-query-batch candidate scan).  It holds what more
+// the top-k driver), search_range.hip (range search), search_scanq.hip (the large-query-batch candidate scan) and search_ids.hip (the
+// id table of an id-mapped index).  It holds what more
 // than one of them needs: the index object with the plan of a search, the view a search scans, the row mask of a filtered search, and
 // the launchers that are defined in one file and called from another.  Not part of the C ABI.
 #pragma once
@@ -152,6 +153,11 @@ struct ivr_index {
                                      // front of every unit of 16 groups: what the host reads back to plan the walk
     DevBuf<float> rm_bounce;         // DEV [remove_chunk / 16 + 1 tiles]: the survivors of one step, already tiled for their destination
     DevBuf<uint4> rm_bounce16;       // the same tiles of the bf16 scan copy
+    // stable external ids (ivr_index_add_with_ids, search_ids.hip): an id-mapped index labels row r ids[r] instead of id_base + r
+    bool has_ids = false;            // set by the first ivr_index_add_with_ids on an empty index, cleared by ivr_index_reset
+    int64_t *ids = nullptr;          // DEV [cap] while has_ids: grows with the rows (index_alloc), entries >= ntotal are never read
+    DevBuf<uint64_t> ids_rows;       // DEV [cap / 64] row bitmap of a filter over stored ids: bit i of word g = row 64 g + i is allowed
+    DevBuf<int64_t> ids_moved;       // DEV [rows from the first removed one on]: their surviving ids in order (ivr_index_remove_ids)
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity
@@ -186,20 +192,30 @@ struct View {
     const uint4 *data16;
     int64_t ntotal, ngroups, id_base;
     const RowMask *mask;
+    const int64_t *ids;      // id-mapped index: the label of row r is ids[r] (id_base is 0 and unused); NULL: id_base + r
 };
 
 // search_index.hip.  The view of a search: the whole index without a filter; with one (id = id_base + row) the part it allows and,
 // in m, the mask of its allowed rows (a view of 0 rows when nothing is allowed)
 View ivr_make_view(const ivr_index *x, int64_t id_base, const ivr_id_filter *f, RowMask &m);
 
-// The shared body of the search entry points once their own arguments are checked: filter check, lock, device, body(view)
+// search_ids.hip.  The view of a search on an id-mapped index: always the whole index, labelled from the id table.  A filter names
+// stored ids: one pass over the table on stream s turns it into the row bitmap x->ids_rows, which m then points at (no host
+// synchronisation; a view of 0 rows when the filter's range is empty)
+int ivr_make_ids_view(ivr_index *x, const ivr_id_filter *f, RowMask &m, hipStream_t s, View &out);
+
+// The shared body of the search entry points once their own arguments are checked: filter check, lock, device, body(view).  s: the
+// stream the body launches on
 template <typename F>
-int with_view(ivr_index *x, int64_t id_base, const ivr_id_filter *f, const char *what, F &&body) {
+int with_view(ivr_index *x, int64_t id_base, const ivr_id_filter *f, hipStream_t s, const char *what, F &&body) {
     IVR_REQUIRE(!f || f->nbits >= 0, "%s: filter nbits=%lld < 0", what, (long long)(f ? f->nbits : 0));
     std::lock_guard<std::mutex> lk(x->mu);
     IVR_HIP(hipSetDevice(x->ctx->device));
     RowMask m;
-    return body(ivr_make_view(x, id_base, f, m));
+    if (!x->has_ids) return body(ivr_make_view(x, id_base, f, m));
+    View v;
+    const int rc = ivr_make_ids_view(x, f, m, s, v);
+    return rc != IVR_OK ? rc : body(v);
 }
 
 // search_index.hip.  dst == x->data: index rows (bf16 scan copy + max norm alongside); dst == x->qtiled: queries (bf16 hi / lo split

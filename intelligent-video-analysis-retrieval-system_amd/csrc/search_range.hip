@@ -204,12 +204,14 @@ __global__ __launch_bounds__(1024) void range_offsets_kernel(const uint32_t *__r
 // slots (read total[parity], write total[parity ^ 1]) so that no workgroup of this launch can read a value written by it; the first
 // chunk starts from 0.  Pairs with hits are re-scored (same function as pass 3: the same scores, the same mask) and each hit is
 // written at its position when that is < cap.  -0.0 is written as +0.0, as the top-k search reports it.
+template <bool IDS>
 __global__ __launch_bounds__(256) void range_write_kernel(const float *__restrict__ data, const float *__restrict__ qtile, int dp4,
                                                           int64_t ntotal, float radius, int nqc, int q0, const uint32_t *__restrict__ cand,
                                                           int64_t cstride, const uint32_t *__restrict__ ncand, const uint64_t *__restrict__ mask,
                                                           const uint32_t *__restrict__ off, const uint32_t *__restrict__ nhits,
                                                           int64_t *__restrict__ total, int first, int parity, int64_t *__restrict__ lims,
-                                                          float *__restrict__ D, int64_t *__restrict__ I, int64_t cap, int64_t id_base) {
+                                                          float *__restrict__ D, int64_t *__restrict__ I, int64_t cap, int64_t id_base,
+                                                          const int64_t *__restrict__ ids) {
     __shared__ int64_t pre[65], qb[65];
     if (threadIdx.x == 0) {
         int64_t s = 0, h = first ? 0 : total[parity];
@@ -249,7 +251,8 @@ __global__ __launch_bounds__(256) void range_write_kernel(const float *__restric
                         const int64_t pos = o + __popcll(m & ((1ull << rl) - 1));
                         if (pos < cap) {
                             D[pos] = acc[t][r] + 0.f;
-                            I[pos] = id_base + (int64_t)g * kGroupRows + rl;
+                            const int64_t row = (int64_t)g * kGroupRows + rl;
+                            I[pos] = IDS ? ids[row] : id_base + row;
                         }
                     }
                 }
@@ -315,9 +318,9 @@ int range_search_view(ivr_index *x, const View &v, const float *q, int nq, float
         }
         {
             IvrProf prof("range_write", s, 0.0, true);
-            hipLaunchKernelGGL(range_write_kernel, dim3(pgrid), dim3(256), 0, s, v.data, qtile, x->dp4, v.ntotal, radius, nqc, q0,
+            hipLaunchKernelGGL(v.ids ? range_write_kernel<true> : range_write_kernel<false>, dim3(pgrid), dim3(256), 0, s, v.data, qtile, x->dp4, v.ntotal, radius, nqc, q0,
                                x->rs_cand, cstride, ncand, x->rs_mask, x->rs_off, nhits, total, c == 0 ? 1 : 0, c & 1, lims, D, I, cap,
-                               id_base);
+                               id_base, v.ids);
             IVR_LAUNCH_CHECK();
         }
     }
@@ -339,7 +342,7 @@ int ivr_index_range_search_filtered(ivr_index *x, const float *q, int nq, float 
     IVR_REQUIRE(nq >= 1, "ivr_index_range_search: nq=%d", nq);
     IVR_REQUIRE(cap >= 0, "ivr_index_range_search: cap=%lld", (long long)cap);
     IVR_REQUIRE(!(radius != radius), "ivr_index_range_search: radius is NaN");
-    return with_view(x, id_base, filter, "ivr_index_range_search_filtered", [&](const View &v) {
+    return with_view(x, id_base, filter, (hipStream_t)stream, "ivr_index_range_search_filtered", [&](const View &v) {
         return range_search_view(x, v, q, nq, radius, normalize_q, lims, D, I, cap, (hipStream_t)stream);
     });
 }

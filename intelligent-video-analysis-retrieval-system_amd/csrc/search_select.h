@@ -99,7 +99,9 @@ struct SrcPacked {     // shard merge straight from the all-gather buffer: candi
     }
 };
 
-enum { OUT_GROUPS = 0, OUT_DI = 1, OUT_DI_PARTS = 2, OUT_DI_PACKED = 3 };
+// OUT_DI_IDS: OUT_DI on an id-mapped index, the label of row r is ids[r] (the table travels in the I_parts argument); an
+// instantiation of its own, so that the kernels a plain index launches stay as they are
+enum { OUT_GROUPS = 0, OUT_DI = 1, OUT_DI_PARTS = 2, OUT_DI_PACKED = 3, OUT_DI_IDS = 4 };
 
 constexpr int kRegKeys = 16;   // keys cached per thread: n <= 16 * 1024 is selected without re-reading global memory
 
@@ -315,6 +317,8 @@ __global__ __launch_bounds__(kSelThreads) void select_topk_kernel(Src src, int q
                 } else if (OUT == OUT_DI_PACKED) {
                     const int32_t *c = ((const SrcPacked *)&src)->at(q, low);
                     id = ((int64_t)c[2] << 32) | (uint32_t)c[1];
+                } else if (OUT == OUT_DI_IDS) {
+                    id = I_parts[low];
                 } else {
                     id = id_base + (int64_t)low;
                 }
@@ -322,7 +326,7 @@ __global__ __launch_bounds__(kSelThreads) void select_topk_kernel(Src src, int q
             I[qo * k + j] = id;
         }
     }
-    if (OUT == OUT_DI && vf.ok && tid == 0) {
+    if ((OUT == OUT_DI || OUT == OUT_DI_IDS) && vf.ok && tid == 0) {
         const uint32_t g = vf.sel[(int64_t)q * vf.ksel2 + vf.kp];
         int good = 1;
         if (g != 0xFFFFFFFFu) {                       // there IS an excluded group
@@ -354,6 +358,7 @@ struct SelectOut {
     float *D = nullptr;                   // OUT_DI*: [nq][k] scores and ids; id = id_base + row, or taken from the source's parts
     int64_t *I = nullptr;
     int64_t id_base = 0;
+    const int64_t *ids = nullptr;         // OUT_DI_IDS: id = ids[row] (launch_select_rows picks the instantiation)
     const int64_t *I_parts = nullptr;     // OUT_DI_PARTS
     const int *skip = nullptr;            // queries with skip[q] != 0 keep what they have
     VerifyArgs vf;
@@ -364,11 +369,12 @@ struct SelectOut {
         o.groups = groups;
         return o;
     }
-    static SelectOut to_rows(float *D, int64_t *I, int64_t id_base = 0) {
+    static SelectOut to_rows(float *D, int64_t *I, int64_t id_base = 0, const int64_t *ids = nullptr) {
         SelectOut o;
         o.D = D;
         o.I = I;
         o.id_base = id_base;
+        o.ids = ids;
         return o;
     }
 };
@@ -377,7 +383,14 @@ struct SelectOut {
 template <int OUT, typename Src>
 void launch_select(const Src &src, int nq, int k, const SelectOut &o, hipStream_t s) {
     hipLaunchKernelGGL((select_topk_kernel<Src, OUT>), dim3(nq), dim3(sel_threads(src.n)), 0, s, src, 0, k, o.id_base, o.groups, o.D, o.I,
-                       o.I_parts, o.skip, o.vf, o.reset_flags, o.la);
+                       OUT == OUT_DI_IDS ? o.ids : o.I_parts, o.skip, o.vf, o.reset_flags, o.la);
+}
+
+// the final selection of a search (scores and labels of index rows): labels from the id table when the index has one
+template <typename Src>
+void launch_select_rows(const Src &src, int nq, int k, const SelectOut &o, hipStream_t s) {
+    if (o.ids) launch_select<OUT_DI_IDS>(src, nq, k, o, s);
+    else launch_select<OUT_DI>(src, nq, k, o, s);
 }
 
 }  // namespace

@@ -6,6 +6,9 @@ Stands in for the `faiss.IndexFlatIP` objects the reference creates at
 float32 scores descending, int64 labels, -1 labels for unused slots - so the
 call sites `index.add(x)`, `index.search(q, k)`, `index.ntotal`, `index.d`,
 `index.is_trained`, `index.train(x)` run unchanged on this object.
+`add_with_ids` / `IndexIDMap2` give the rows caller-chosen int64 labels that
+survive `remove_ids` (what the reference's `id_to_metadata`, `core.py:722-723`,
+and `search_by_id`, `core.py:932-958`, key on).
 All arithmetic happens in libivr_hip.so; numpy arrays are staged through
 torch CUDA tensors, torch CUDA tensors are used in place.
 """
@@ -15,6 +18,21 @@ import numpy as np
 import torch
 
 from . import _ffi
+
+
+def _ids_i64(ids, n, what):
+    """ids (numpy / torch, any integer dtype) -> numpy int64 [n]; ValueError for a wrong length, a non-integer dtype or a negative id."""
+    if isinstance(ids, torch.Tensor):
+        if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+            raise ValueError(f"{what}: ids must be integers, got {ids.dtype}")
+        ids = ids.detach().cpu().numpy()
+    ids = np.asarray(ids)
+    if not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError(f"{what}: ids must be integers, got {ids.dtype}")
+    ids = ids.reshape(-1).astype(np.int64)
+    if n is not None and len(ids) != n:
+        raise ValueError(f"{what}: {len(ids)} ids for {n} rows")
+    return ids
 
 
 def _dev_f32(x, device):
@@ -160,7 +178,8 @@ class IDSelectorBatch(_IDSelector):
 
 
 class SearchParameters:
-    """faiss.SearchParameters(sel=...): only `sel` is used (None = every id)."""
+    """faiss.SearchParameters(sel=...): only `sel` is used (None = every id).  The ids a selector names are row positions (id_base + row)
+    on a plain index and the stored ids on an id-mapped one (add_with_ids)."""
 
     def __init__(self, sel=None):
         if sel is not None and not isinstance(sel, _IDSelector):
@@ -222,13 +241,60 @@ class FlatIPIndex:
             return
         self._add_device(_dev_f32(x, self.device), normalize)
 
-    def _add_device(self, t, normalize):
+    def _add_device(self, t, normalize, ids=None):
         if t.dim() != 2 or t.shape[1] != self.d:
             raise ValueError(f"add expects [n,{self.d}], got {tuple(t.shape)}")
         with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_add(self._h, C.c_void_p(t.data_ptr()), t.shape[0], int(bool(normalize)),
-                                               _ffi.stream_ptr()), "ivr_index_add")
+            if ids is None:
+                _ffi.check(self._lib.ivr_index_add(self._h, C.c_void_p(t.data_ptr()), t.shape[0], int(bool(normalize)),
+                                                   _ffi.stream_ptr()), "ivr_index_add")
+            else:
+                i = torch.from_numpy(ids).to(self.device)
+                _ffi.check(self._lib.ivr_index_add_with_ids(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(i.data_ptr()), t.shape[0],
+                                                            int(bool(normalize)), _ffi.stream_ptr()), "ivr_index_add_with_ids")
             torch.cuda.current_stream().synchronize()  # `t` may be a temporary staging copy
+
+    def add_with_ids(self, x, ids, normalize=False, chunk_rows=1 << 20):
+        """faiss add_with_ids(x, ids): append rows under caller-chosen int64 labels (numpy or torch, one per row, every id >= 0: -1 is
+        the empty-slot label and the selectors never match a negative id; duplicates are allowed).  The first call on an empty index
+        makes it id-mapped until reset(): search / range_search return the stored ids, selectors and remove_ids name stored ids, and
+        add() is refused.  ValueError for a wrong length, a non-integer dtype or a negative id; refused on an index that already holds
+        rows without ids."""
+        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"add_with_ids expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        n = len(x)
+        ids = _ids_i64(ids, n, "add_with_ids")
+        if n and int(ids.min()) < 0:
+            raise ValueError(f"add_with_ids: negative id {int(ids.min())} (-1 labels an unused result slot)")
+        if n == 0:
+            self._add_device(torch.empty((0, self.d), dtype=torch.float32, device=self.device), normalize, ids)
+        for i in range(0, n, chunk_rows):
+            self._add_device(_dev_f32(x[i:i + chunk_rows], self.device), normalize, np.ascontiguousarray(ids[i:i + chunk_rows]))
+
+    @property
+    def has_ids(self):
+        """True once add_with_ids (or IndexIDMap / IndexIDMap2) has made the index id-mapped; False again after reset()."""
+        return bool(self._lib.ivr_index_has_ids(self._h))
+
+    @property
+    def id_map(self):
+        """The stored ids in row order as a numpy int64 copy: faiss.vector_to_array(index.id_map)."""
+        n = self.ntotal
+        out = torch.empty(n, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self._lib.ivr_index_get_ids(self._h, 0, n, C.c_void_p(out.data_ptr()), _ffi.stream_ptr()), "ivr_index_get_ids")
+        return out.cpu().numpy()
+
+    def find(self, ids):
+        """rows[i] = the lowest row stored under ids[i], or -1 (numpy int64).  Every call scans the whole id table once per key: for a
+        handful of keys, such as the reference's search_by_id (core.py:932-958)."""
+        keys = _ids_i64(np.atleast_1d(ids) if not isinstance(ids, torch.Tensor) else ids, None, "find")
+        k = torch.from_numpy(np.ascontiguousarray(keys)).to(self.device)
+        rows = torch.empty(len(keys), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self._lib.ivr_index_find_ids(self._h, C.c_void_p(k.data_ptr()), len(keys), C.c_void_p(rows.data_ptr()),
+                                                    _ffi.stream_ptr()), "ivr_index_find_ids")
+        return rows.cpu().numpy()
 
     def write(self, start, x, normalize=False):
         """Overwrite rows [start, start+n): ring-buffer maintenance for rolling indexes."""
@@ -257,7 +323,8 @@ class FlatIPIndex:
 
     def search(self, x, k, params=None):
         """(D, I) numpy arrays, exactly like faiss: D float32 [nq,k] descending, I int64 [nq,k], -1 padded.  params =
-        SearchParameters(sel=IDSelector...): the top k among the ids the selector allows."""
+        SearchParameters(sel=IDSelector...): the top k among the ids the selector allows.  On an id-mapped index (add_with_ids) the
+        labels are the stored ids and the selector names stored ids; equal scores still rank the lower ROW first."""
         sel = _selector(params)
         q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
         if isinstance(q, np.ndarray) and q.ndim == 1:
@@ -266,7 +333,9 @@ class FlatIPIndex:
         return D.cpu().numpy(), I.cpu().numpy()
 
     def search_device(self, x, k, normalize=False, id_base=0, out=None, sel=None):
-        """Device-resident variant: returns CUDA tensors and does not synchronise.  sel: an IDSelector (ids = id_base + row)."""
+        """Device-resident variant: returns CUDA tensors and does not synchronise.  sel: an IDSelector (ids = id_base + row).  On an
+        id-mapped index id_base is ignored: labels and selectors are stored ids (one extra pass over the id table per filtered call,
+        still without a host synchronisation, and the whole index is scanned whatever the selector's range)."""
         sel = _selector(sel=sel)
         t = _dev_f32(x, self.device)
         if t.dim() != 2 or t.shape[1] != self.d:
@@ -297,7 +366,8 @@ class FlatIPIndex:
     def range_search(self, x, radius, params=None):
         """faiss range_search: every row with <q, row> > radius.  (lims int64 [nq+1], D float32 [lims[-1]], I int64 [lims[-1]])
         numpy arrays; query i's results are D/I[lims[i]:lims[i+1]], ids ascending.  One host sync to read the total; a second
-        pass only when the first-guess capacity was too small.  params = SearchParameters(sel=...): only the allowed ids."""
+        pass only when the first-guess capacity was too small.  params = SearchParameters(sel=...): only the allowed ids.  On an
+        id-mapped index I holds stored ids (in ascending ROW order within a query) and the selector names stored ids."""
         sel = _selector(params)
         q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
         if isinstance(q, np.ndarray) and q.ndim == 1:
@@ -313,7 +383,8 @@ class FlatIPIndex:
     def range_search_device(self, x, radius, normalize=False, id_base=0, cap=None, sel=None):
         """Device-resident range search: (lims [nq+1], D [cap], I [cap], total) CUDA tensors, total = lims[nq:] (the number of
         results; entries at positions >= cap are counted but not written).  No host sync when `cap` is given; cap=None sizes
-        D and I exactly (a counting pass, one sync, then the full pass).  sel: an IDSelector (ids = id_base + row)."""
+        D and I exactly (a counting pass, one sync, then the full pass).  sel: an IDSelector (ids = id_base + row; stored ids on an
+        id-mapped index, where id_base is ignored)."""
         sel = _selector(sel=sel)
         radius = float(radius)
         if radius != radius:
@@ -363,14 +434,22 @@ class FlatIPIndex:
         return out.cpu().numpy()
 
     def reconstruct(self, i):
-        """faiss reconstruct(i): the stored row i as a float32 [d] numpy array."""
+        """faiss reconstruct(i): the stored row i as a float32 [d] numpy array.  On an id-mapped index i is a stored id
+        (IndexIDMap2::reconstruct): the lowest row stored under it, RuntimeError when no row is.  reconstruct_n stays positional."""
+        if self.has_ids:
+            row = int(self.find([int(i)])[0])
+            if row < 0:
+                raise RuntimeError(f"reconstruct: id {int(i)} is not in the index")
+            return self.reconstruct_n(row, 1)[0]
         return self.reconstruct_n(int(i), 1)[0]
 
     def remove_ids(self, sel, id_base=0):
         """faiss remove_ids(sel): delete every stored row whose id (id_base + row) the selector names and return how many were removed.
         sel: an IDSelectorRange / IDSelectorBatch / IDSelectorBitmap, or an integer numpy array / torch tensor of ids (wrapped in an
         IDSelectorBatch, as faiss's Python wrapper does).  The surviving rows keep their order and their bits and move down, so the
-        ids above a removed row shift; the capacity stays.  Synchronises the current stream once (not graph-capturable)."""
+        ids above a removed row shift; the capacity stays.  Synchronises the current stream once (not graph-capturable).
+        On an id-mapped index the selector (or the integer array) names STORED ids, id_base is ignored, every row stored under a named
+        id goes (duplicates each counted), and the surviving rows keep their ids: nothing shifts."""
         if isinstance(sel, (np.ndarray, torch.Tensor)):
             sel = IDSelectorBatch(sel)
         if not isinstance(sel, _IDSelector):
@@ -402,6 +481,20 @@ class FlatIPIndex:
 def IndexFlatIP(d):
     """faiss.IndexFlatIP(d) drop-in constructor."""
     return FlatIPIndex(d)
+
+
+def IndexIDMap2(index):
+    """faiss.IndexIDMap2(faiss.IndexFlatIP(d)) drop-in: the given EMPTY FlatIPIndex (ValueError otherwise, as faiss requires), made
+    id-mapped: add_with_ids / search / remove_ids / reconstruct(id) work on stored ids and add() raises until the index is reset."""
+    if not isinstance(index, FlatIPIndex):
+        raise ValueError(f"IndexIDMap2 wraps a FlatIPIndex, got {type(index).__name__}")
+    if index.ntotal != 0:
+        raise ValueError(f"IndexIDMap2: the index must be empty, it holds {index.ntotal} rows")
+    index.add_with_ids(np.zeros((0, index.d), np.float32), np.zeros(0, np.int64))
+    return index
+
+
+IndexIDMap = IndexIDMap2      # faiss.IndexIDMap differs only in lacking reconstruct(), which costs nothing to keep here
 
 
 def topk_merge(D_parts, I_parts, k=None):

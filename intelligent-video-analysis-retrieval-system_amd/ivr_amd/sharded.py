@@ -91,6 +91,12 @@ def merge_range(counts, packed):
 
 
 class ShardedIndex:
+    """Shards built with add_local label their rows id_base + row, and id_base follows the counts of the lower ranks.  Shards built
+    with add_local_with_ids (id-mapped, FlatIPIndex.add_with_ids) carry the global ids themselves: id_base is still kept up to date
+    and passed down but unused, the ids a search returns and the ids a selector or remove_ids names are the stored ones on every
+    rank, and a removal on one rank changes no id on another.  Candidates still merge in rank order, so equal scores rank the
+    lower rank's row first."""
+
     def __init__(self, local, d, group=None, merge="device"):
         self.local = local
         self.d = int(d)
@@ -106,6 +112,11 @@ class ShardedIndex:
         """Append this rank's rows, then agree on every shard's global id offset (one tiny all-gather of counts;
         build-time only, never on the search path)."""
         self.local.add(rows, normalize=normalize) if normalize else self.local.add(rows)
+        self.sync_counts()
+
+    def add_local_with_ids(self, rows, ids, normalize=False):
+        """Append this rank's rows under global ids of the caller's choosing (local.add_with_ids), then agree on the counts."""
+        self.local.add_with_ids(rows, ids, normalize=normalize) if normalize else self.local.add_with_ids(rows, ids)
         self.sync_counts()
 
     def sync_counts(self):
@@ -126,7 +137,8 @@ class ShardedIndex:
         """faiss remove_ids(sel) over all shards: sel names GLOBAL ids (a selector, or an integer array as FlatIPIndex.remove_ids takes
         it).  Every rank removes its own rows, then the counts are agreed on again (sync_counts: the one collective, as after
         add_local), so each shard's id_base follows the rows that left the shards below it.  Returns the global number of removed
-        rows, identical on every rank: the difference of the summed counts.  Shards are not re-balanced."""
+        rows, identical on every rank: the difference of the summed counts.  Shards are not re-balanced.  On id-mapped shards sel names
+        stored ids and the ids of the surviving rows stay as they are on every rank."""
         before = self.ntotal
         self.local.remove_ids(sel, id_base=self.id_base)
         self.sync_counts()
