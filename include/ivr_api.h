@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IVR_API_VERSION 10
+#define IVR_API_VERSION 11
 #define IVR_MAX_K 2048          /* reference: k=50 default, SearchOptions.limit <= 1000 (system.py:91) */
 
 typedef enum ivr_status {
@@ -336,8 +336,47 @@ int ivr_index_has_ids(ivr_index *idx);                      /* 1: id-mapped, 0: 
 /* ids[start .. start + n) -> out (faiss id_map[start:start+n]); start + n <= ntotal; IVR_ERR_STATE on a plain index. */
 int ivr_index_get_ids(ivr_index *idx, int64_t start, int64_t n, int64_t *out /*DEV*/, ivr_stream stream);
 /* rows[i] = the lowest row that holds id keys[i], or -1 (what IndexIDMap2::reconstruct and the reference's search_by_id,
- * core.py:932-958, need).  A scan of the whole table per call, O(n x ntotal) compares: meant for a handful of keys. */
+ * core.py:932-958, need); a negative key and any key on an empty index give -1.  Two paths with the same results:
+ *  - n < IVR_FIND_TABLE_MIN_KEYS: one scan of the whole id table per call, O(n x ntotal) compares, nothing allocated;
+ *  - otherwise a device hash table from stored id to lowest row: open addressing with linear probing, a power-of-two number of
+ *    slots >= 2 ntotal (load factor <= 1/2, 16 bytes per slot: at most 64 bytes per stored row), the id bits mixed before masking,
+ *    empty key -1.  Nothing is allocated until the first lookup that takes this path.  The table is built by one pass over
+ *    ids[0 .. ntotal) (a 64-bit compare-and-swap claims a key's slot, an atomic minimum lowers its row, so duplicates resolve to
+ *    the lowest row as the scan does); ivr_index_add_with_ids, ivr_index_remove_ids and ivr_index_reset mark it stale, the next
+ *    lookup rebuilds it, ivr_index_reset and ivr_index_destroy free it.
+ * A lookup that builds or rebuilds the table allocates and so cannot be captured into a hipGraph; one that finds the table built,
+ * and the scan path, only enqueue.  IVR_FIND_TABLE_MIN_KEYS (environment, read by ivr_index_create; 0 = always the table, a huge
+ * value = always the scan) defaults to 512: the smallest measured key count at which a table lookup including one
+ * rebuild beats the scan on 1M rows (0.161 ms against 0.171 ms; a built table answers any number of keys up to 65,536 in 0.025 ms). */
 int ivr_index_find_ids(ivr_index *idx, const int64_t *keys /*DEV*/, int64_t n, int64_t *rows /*DEV*/, ivr_stream stream);
+
+/* ---- row access by position: gather, scatter, search + reconstruct ---------------------------------
+ * Random access to the stored rows over both layouts (the float32 tiles and the bf16 scan copy).  One row of d floats is d / 4
+ * pieces of 16 bytes spaced 256 bytes apart inside its 16-row tile, so a random row touches every cache line of its tile: 16 times
+ * the row's bytes move on the index side ("row access").  The row-major side of both calls is fully coalesced.
+ * Both are positional on plain and id-mapped indexes alike (ivr_index_find_ids turns stored ids into rows), enqueue-only, and
+ * n == 0 is a no-op.
+ *
+ * ivr_index_gather: faiss reconstruct_batch(n, keys, out).  out[i] = stored row rows[i] as row-major float32 with the exact bits
+ * ivr_index_reconstruct returns; an entry outside [0, ntotal) (-1, the empty result slot, included) gives a row of d NaNs, what
+ * faiss::Index::search_and_reconstruct writes for a -1 label.  Repeats are allowed.  rows: DEV int64 [n], out: DEV [n,d]. */
+int ivr_index_gather(ivr_index *idx, const int64_t *rows /*DEV*/, int64_t n, float *out /*DEV*/, ivr_stream stream);
+/* ivr_index_scatter: faiss IndexIVF::update_vectors applied to the flat index, and the n calls ivr_index_write(rows[i], x + i d, 1,
+ * normalize) of unified_index.py's modified-file loop in one launch.  Stored row rows[i] becomes x[i] in the float32 tiles and in
+ * the bf16 scan copy, bit-identical to those n calls (same lane mapping and summation order of the norm, the two scan bounds raised
+ * the same way); the other 15 slots of a touched tile keep their bits, entries outside [0, ntotal) are skipped, ids are left alone.
+ * When one row is named twice in a call, which of the two vectors it ends up holding is unspecified (lanes of different waves
+ * write it unordered); every other row is unaffected.  rows: DEV int64 [n], x: DEV float32 [n,d]. */
+int ivr_index_scatter(ivr_index *idx, const int64_t *rows /*DEV*/, const float *x /*DEV*/, int64_t n, int normalize,
+                      ivr_stream stream);
+/* faiss search_and_reconstruct(x, k): ivr_index_search_filtered (D and I bit-identical to it for the same arguments; filter NULL =
+ * unfiltered) plus R: DEV float32 [nq,k,d], R[q,j] = the stored row that produced slot j, NaN rows for unused slots.  The row
+ * positions come out of the final selection itself, so on an id-mapped index with duplicate labels R is the row that scored, not
+ * the lowest row under its label.  Allocates nothing after ivr_index_reserve_search(max_nq, max_k), which also holds the nq x k
+ * positions (8 bytes each). */
+int ivr_index_search_reconstruct(ivr_index *idx, const float *q /*DEV*/, int nq, int k, int normalize_q, int64_t id_base,
+                                 const ivr_id_filter *filter /*HOST, may be NULL*/, float *D /*DEV*/, int64_t *I /*DEV*/,
+                                 float *R /*DEV*/, ivr_stream stream);
 
 /* Merge per-shard candidate lists (the reference's concat + sort of peer results, system.py:1744-1746):
  * D_parts/I_parts DEV [parts, nq, k] with global ids, parts ordered by ascending id range. */

@@ -551,11 +551,20 @@ VerifyArgs verify_args(const ivr_index *x, int q0, int k, bool big, PruneArgs *p
     return vf;
 }
 
+// ivr_index_search_reconstruct: where the final selections of a search leave the row behind every result slot, as its number in the
+// scanned view (pos: DEV [nq][k], NULL for every other search)
+struct RowPos {
+    int64_t *pos = nullptr;
+    void set(SelectOut &o, int q0, int k) const {
+        if (pos) o.pos = pos + (int64_t)q0 * k;
+    }
+};
+
 // Passes 2 to 4 of the exact search for one chunk whose float32 group maxima are in gmax: for the queries without skip[q] (the
 // 64-query chunks), or for the listed ones (la: behind the large-batch scan, where the amount of work is known on the device only).
 // qtile = the chunk's first query tile: the re-score reads query tile (q >> 4) relative to it.
 int exact_tail(ivr_index *x, const View &v, const float *gmax, const float *qtile, int q0, int nqc, int k, const int *skip,
-               const ListArgs &la, float *D, int64_t *I, hipStream_t s) {
+               const ListArgs &la, float *D, int64_t *I, const RowPos &rp, hipStream_t s) {
     const bool counted = la.count == nullptr;
     const int64_t waves = (int64_t)nqc * k;
     {
@@ -575,6 +584,7 @@ int exact_tail(ivr_index *x, const View &v, const float *gmax, const float *qtil
     SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base, v.ids);
     o.skip = skip;
     o.la = la;
+    rp.set(o, q0, k);
     launch_select_rows(SrcKeys{x->cand, (int64_t)k * kGroupRows}, nqc, k, o, s);
     IVR_LAUNCH_CHECK();
     return IVR_OK;
@@ -585,7 +595,7 @@ int exact_tail(ivr_index *x, const View &v, const float *gmax, const float *qtil
 //   best tiles always lie inside the kp+1 best blocks: the argument of DESIGN.md section 4 with tiles for rows) -> exact float32
 //   re-score of kp tiles -> final selection, which also verifies the approximate ranking per query and lists the queries that
 //   fail -> list-driven exact pass (four launches that exit at once when the list is empty; no host round trip).
-int search_big(ivr_index *x, const View &v, int q0, int nqc, int k, float *D, int64_t *I, hipStream_t s) {
+int search_big(ivr_index *x, const View &v, int q0, int nqc, int k, float *D, int64_t *I, const RowPos &rp, hipStream_t s) {
     const int kp = ivr_index::fast_groups(k), ksel2 = kp + 1;
     const int64_t tstride = x->tstride(), bstride = x->bstride();
     const int64_t nblk128 = ivr_ceil_div(v.ntotal, 128), ntiles = ivr_ceil_div(v.ntotal, 16);
@@ -619,6 +629,7 @@ int search_big(ivr_index *x, const View &v, int q0, int nqc, int k, float *D, in
         IvrProf prof("select_final", s, (double)nqc * kp * 16 * 8, true);
         SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base, v.ids);
         o.vf = vf;
+        rp.set(o, q0, k);
         launch_select_rows(SrcKeys{x->cand, (int64_t)kp * 16}, nqc, k, o, s);
         IVR_LAUNCH_CHECK();
     }
@@ -631,7 +642,7 @@ int search_big(ivr_index *x, const View &v, int q0, int nqc, int k, float *D, in
         default: launch_scan_list<4>(x, v, qtile, x->tmax, la, s); break;
     }
     IVR_LAUNCH_CHECK();
-    return exact_tail(x, v, x->tmax, qtile, q0, nqc, k, nullptr, la, D, I, s);
+    return exact_tail(x, v, x->tmax, qtile, q0, nqc, k, nullptr, la, D, I, rp, s);
 }
 
 int reserve_search(ivr_index *x, int nq, int k) {
@@ -642,6 +653,7 @@ int reserve_search(ivr_index *x, int nq, int k) {
     const size_t chunk_q = std::min(nq, big ? kBigChunk : 64), ksel2 = ivr_index::fast_groups(k) + 1;
     const size_t need_sel = chunk_q * (x->scan16 ? ksel2 : k);   // per scan chunk
     if (rc == IVR_OK) rc = ivr_reserve({{&x->sel, need_sel * 4}, {&x->cand, need_sel * kGroupRows * 8}});
+    if (rc == IVR_OK) rc = ivr_reserve({{&x->rpos, (size_t)nq * k * sizeof(int64_t)}});     // ivr_index_search_reconstruct
     if (rc != IVR_OK || !big) return rc;
     const size_t qpad = ivr_round_up(chunk_q, 256);
     rc = ivr_reserve({{&x->tmax, qpad * x->tstride() * 4}});
@@ -652,9 +664,12 @@ int reserve_search(ivr_index *x, int nq, int k) {
 }
 
 // ivr_index_search over the rows of view v (the whole index, or the part a filter allows); the caller holds x->mu
-int search_view(ivr_index *x, const View &v, const float *q, int nq, int k, int normalize_q, float *D, int64_t *I, hipStream_t s) {
+// want_pos: the row of the view behind every result slot goes to x->rpos
+int search_view(ivr_index *x, const View &v, const float *q, int nq, int k, int normalize_q, float *D, int64_t *I, bool want_pos,
+                hipStream_t s) {
     int rc = reserve_search(x, nq, k);
     if (rc != IVR_OK) return rc;
+    const RowPos rp{want_pos ? (int64_t *)x->rpos : nullptr};
     // queries -> tiled layout (normalised on the way when asked: N2 on the query side, core.py:875)
     rc = ivr_launch_tile_rows(x, x->qtiled, q, 0, nq, normalize_q, nullptr, s);
     if (rc != IVR_OK) return rc;
@@ -666,7 +681,7 @@ int search_view(ivr_index *x, const View &v, const float *q, int nq, int k, int 
         // large batch: the index is read once per kBigChunk queries instead of once per 64
         for (int q0 = 0; q0 < nq; q0 += kBigChunk) {
             const int nqc = std::min(kBigChunk, nq - q0);
-            rc = search_big(x, v, q0, nqc, k, D, I, s);
+            rc = search_big(x, v, q0, nqc, k, D, I, rp, s);
             if (rc != IVR_OK) return rc;
             x->last_nqc = nqc;
         }
@@ -701,6 +716,7 @@ int search_view(ivr_index *x, const View &v, const float *q, int nq, int k, int 
                 IvrProf prof("select_final", s, (double)waves * kGroupRows * 8, true);
                 SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, v.id_base, v.ids);
                 o.vf = vf;
+                rp.set(o, q0, k);
                 launch_select_rows(SrcKeys{x->cand, (int64_t)kp * kGroupRows}, nqc, k, o, s);
                 IVR_LAUNCH_CHECK();
             }
@@ -712,13 +728,17 @@ int search_view(ivr_index *x, const View &v, const float *q, int nq, int k, int 
             ivr_launch_scan_qt(x, v, qt, qtile, s, tile_flag);
             IVR_LAUNCH_CHECK();
         }
-        rc = exact_tail(x, v, x->gmax, qtile, q0, nqc, k, skip, ListArgs(), D, I, s);
+        rc = exact_tail(x, v, x->gmax, qtile, q0, nqc, k, skip, ListArgs(), D, I, rp, s);
         if (rc != IVR_OK) return rc;
     }
     return IVR_OK;
 }
 
 }  // namespace
+
+int ivr_search_view_pos(ivr_index *x, const View &v, const float *q, int nq, int k, int normalize_q, float *D, int64_t *I, hipStream_t s) {
+    return search_view(x, v, q, nq, k, normalize_q, D, I, true, s);
+}
 
 // tiled query buffers (float32, norms, bf16 hi / lo, rounding residuals) for `qtiles` 16-query tiles, zero-filled
 int ivr_reserve_queries(ivr_index *x, int qtiles) {
@@ -776,7 +796,7 @@ int ivr_index_search_filtered(ivr_index *x, const float *q, int nq, int k, int n
     IVR_REQUIRE(nq >= 1, "ivr_index_search: nq=%d", nq);
     IVR_REQUIRE(k >= 1 && k <= IVR_MAX_K, "ivr_index_search: k=%d outside [1,%d]", k, IVR_MAX_K);
     return with_view(x, id_base, filter, (hipStream_t)stream, "ivr_index_search_filtered",
-                     [&](const View &v) { return search_view(x, v, q, nq, k, normalize_q, D, I, (hipStream_t)stream); });
+                     [&](const View &v) { return search_view(x, v, q, nq, k, normalize_q, D, I, false, (hipStream_t)stream); });
 }
 
 int ivr_index_scan_stats(ivr_index *x, int *out) {

@@ -2,7 +2,8 @@
 // table itself (ivr_index::ids, one int64 label per stored row) is allocated, grown, appended to and compacted with the rows in
 // search_index.hip; the label of a result is read from it by the final write of each search path (select_topk_kernel<.., OUT_DI_IDS>,
 // range_write_kernel<true>).  Here: the pass that turns a filter over stored ids into a row bitmap, so that every masked kernel runs
-// as it is, the lookup of rows by id, and the two entry points that read the table back.
+// as it is, the lookup of rows by id (a scan of the table for a few keys, a hash table from id to lowest row for many), and the two
+// entry points that read the table back.
 #include "ivr_common.h"
 #include "search_internal.h"
 
@@ -32,7 +33,8 @@ __global__ __launch_bounds__(256) void ids_row_mask_kernel(const int64_t *__rest
 
 // rows[i] = the lowest row whose id is keys[i], or -1: a grid-stride scan of the table, every thread compares its id with every key
 // (the keys are read at wave-uniform addresses) and a match lowers the key's slot by an atomic minimum.  The slots start as -1 =
-// the largest unsigned value, so "none" needs no second pass.  O(keys x ntotal) compares: meant for a handful of keys.
+// the largest unsigned value, so "none" needs no second pass.  O(keys x ntotal) compares: the path of lookups below
+// IVR_FIND_TABLE_MIN_KEYS keys, which need no table built.
 __global__ __launch_bounds__(256) void ids_find_kernel(const int64_t *__restrict__ ids, int64_t ntotal, const int64_t *__restrict__ keys,
                                                        int64_t nkeys, unsigned long long *__restrict__ rows) {
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < ntotal; r += (int64_t)gridDim.x * 256) {
@@ -40,6 +42,78 @@ __global__ __launch_bounds__(256) void ids_find_kernel(const int64_t *__restrict
         for (int64_t i = 0; i < nkeys; ++i)
             if (keys[i] == id) atomicMin(&rows[i], (unsigned long long)r);
     }
+}
+
+// Hash table from stored id to the lowest row that holds it: open addressing with linear probing over a power-of-two number of slots
+// >= 2 ntotal (load factor <= 1/2, so every probe sequence ends at an empty slot), empty key -1 (stored ids are >= 0).  The slot of an
+// id comes from all of its bits (the 64-bit finaliser of MurmurHash3): sequential ids, and ids that share a large base, spread.
+__device__ __forceinline__ uint64_t ids_slot(int64_t id, uint64_t mask) {
+    uint64_t h = (uint64_t)id;
+    h ^= h >> 33;
+    h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 33;
+    h *= 0xc4ceb9fe1a85ec53ull;
+    h ^= h >> 33;
+    return h & mask;
+}
+
+// One thread per stored row: a 64-bit compare-and-swap claims the first slot of the probe sequence that is empty or already holds the
+// id, an atomic minimum lowers that slot's row.  Rows under one id all end in the same slot (a claimed key never changes), so the slot
+// holds the lowest of them whatever the order of the threads: what the scan path returns.  keys / rows start as all ones (-1).
+__global__ __launch_bounds__(256) void ids_table_build_kernel(const int64_t *__restrict__ ids, int64_t ntotal, unsigned long long *__restrict__ keys,
+                                                              unsigned long long *__restrict__ rows, uint64_t mask) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= ntotal) return;
+    const unsigned long long id = (unsigned long long)ids[r];
+    for (uint64_t h = ids_slot((int64_t)id, mask);; h = (h + 1) & mask) {
+        const unsigned long long prev = atomicCAS(&keys[h], ~0ull, id);
+        if (prev == ~0ull || prev == id) {
+            atomicMin(&rows[h], (unsigned long long)r);
+            return;
+        }
+    }
+}
+
+// One thread per key: walk the probe sequence to the key or to the first empty slot.  A negative key is no stored id (and -1 is the
+// empty marker): -1 without a probe.
+__global__ __launch_bounds__(256) void ids_table_find_kernel(const int64_t *__restrict__ tkeys, const unsigned long long *__restrict__ trows,
+                                                             uint64_t mask, const int64_t *__restrict__ keys, int64_t nkeys,
+                                                             int64_t *__restrict__ rows) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nkeys) return;
+    const int64_t key = keys[i];
+    int64_t row = -1;
+    if (key >= 0) {
+        for (uint64_t h = ids_slot(key, mask);; h = (h + 1) & mask) {
+            const int64_t k = tkeys[h];
+            if (k == key) row = (int64_t)trows[h];
+            if (k == key || k == -1) break;
+        }
+    }
+    rows[i] = row;
+}
+
+// the table of x brought up to date with ids[0 .. ntotal) on stream s (ntotal > 0): allocates when the slot count changes
+int ids_table_build(ivr_index *x, hipStream_t s) {
+    if (x->tab_ok) return IVR_OK;
+    int64_t slots = 2;
+    while (slots < 2 * x->ntotal) slots <<= 1;
+    const size_t bytes = (size_t)slots * 8;
+    if (x->tab_keys.bytes != bytes) {
+        // exactly the slots of this build, so that the table never holds more than 64 bytes per stored row
+        int rc = ivr_release({{&x->tab_keys, 0}, {&x->tab_rows, 0}});
+        if (rc == IVR_OK) rc = ivr_reserve({{&x->tab_keys, bytes}, {&x->tab_rows, bytes}});
+        if (rc != IVR_OK) return rc;
+    }
+    x->tab_slots = slots;
+    IVR_HIP(hipMemsetAsync(x->tab_keys, 0xff, bytes, s));
+    IVR_HIP(hipMemsetAsync(x->tab_rows, 0xff, bytes, s));
+    IvrProf prof("ids_table_build", s, (double)x->ntotal * 8 + 4.0 * bytes, true);
+    hipLaunchKernelGGL(ids_table_build_kernel, dim3((unsigned)ivr_ceil_div(x->ntotal, 256)), dim3(256), 0, s, x->ids, x->ntotal,
+                       reinterpret_cast<unsigned long long *>((int64_t *)x->tab_keys), (unsigned long long *)x->tab_rows, (uint64_t)slots - 1);
+    IVR_LAUNCH_CHECK();
+    x->tab_ok = true;
+    return IVR_OK;
 }
 
 }  // namespace
@@ -95,6 +169,16 @@ int ivr_index_find_ids(ivr_index *x, const int64_t *keys, int64_t n, int64_t *ro
     if (n == 0) return IVR_OK;
     IVR_HIP(hipSetDevice(x->ctx->device));
     hipStream_t s = (hipStream_t)stream;
+    if (x->ntotal > 0 && n >= x->find_table_min) {
+        // many keys: the hash table, (re)built first when rows or ids changed since its last build
+        const int rc = ids_table_build(x, s);
+        if (rc != IVR_OK) return rc;
+        IvrProf prof("ids_table_find", s, (double)n * 32, true);
+        hipLaunchKernelGGL(ids_table_find_kernel, dim3((unsigned)ivr_ceil_div(n, 256)), dim3(256), 0, s, (const int64_t *)x->tab_keys,
+                           (const unsigned long long *)x->tab_rows, (uint64_t)x->tab_slots - 1, keys, n, rows);
+        IVR_LAUNCH_CHECK();
+        return IVR_OK;
+    }
     IVR_HIP(hipMemsetAsync(rows, 0xff, (size_t)n * sizeof(int64_t), s));         // -1: no row holds the key
     if (x->ntotal == 0) return IVR_OK;
     const int64_t blocks = std::min<int64_t>(ivr_ceil_div(x->ntotal, 256), (int64_t)x->ctx->cu_count * 8);

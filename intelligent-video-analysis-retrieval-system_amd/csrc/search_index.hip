@@ -10,16 +10,6 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // tiling: row-major [n,d] -> tiled, with optional L2 normalisation (N2/N3) and non-finite count
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float4 load_quad(const float *__restrict__ row, int k0, int d, bool vec) {
-    if (vec) return *reinterpret_cast<const float4 *>(row + k0);   // k0 + 3 < d guaranteed by caller when vec
-    float4 v;
-    v.x = k0 + 0 < d ? row[k0 + 0] : 0.f;
-    v.y = k0 + 1 < d ? row[k0 + 1] : 0.f;
-    v.z = k0 + 2 < d ? row[k0 + 2] : 0.f;
-    v.w = k0 + 3 < d ? row[k0 + 3] : 0.f;
-    return v;
-}
-
 // one wave per 16-row tile; lane l owns row (l & 15) and quad (l >> 4) of every 16-float chunk.
 // Optionally also writes the bf16 scan copy of the tile (dst16; and the rounding remainder dst16lo for query tiles):
 // per 32 floats of K one 1 KiB piece, lane l -> 16 bytes = the two quads this lane owns in the pair of 16-float chunks, i.e.
@@ -55,7 +45,7 @@ __global__ __launch_bounds__(256) void tile_rows_kernel(const float *__restrict_
             for (int u = 0; u < 8; ++u) {
                 const int k0 = (kc0 + u) * 16 + qd * 4;
                 v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (valid && kc0 + u < kchunks && k0 < d) v[u] = load_quad(srow, k0, d, vec && k0 + 3 < d);
+                if (valid && kc0 + u < kchunks && k0 < d) v[u] = ivr_load_quad(srow, k0, d, vec && k0 + 3 < d);
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -101,7 +91,7 @@ __global__ __launch_bounds__(256) void tile_rows_kernel(const float *__restrict_
         for (int u = 0; u < 2; ++u) {
             const int kc = 2 * (kb0 + b4) + u, k0 = kc * 16 + qd * 4;
             vv[b4][u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (valid && kc < kchunks && k0 < d) vv[b4][u] = load_quad(srow, k0, d, vec && k0 + 3 < d);
+            if (valid && kc < kchunks && k0 < d) vv[b4][u] = ivr_load_quad(srow, k0, d, vec && k0 + 3 < d);
         }
 #pragma unroll
       for (int b4 = 0; b4 < 4; ++b4) {
@@ -486,19 +476,6 @@ int index_alloc(ivr_index *x, int64_t rows) {
     return IVR_OK;
 }
 
-// every buffer of the group empty again; the first error, if any
-int release_all(DevSizes bufs) {
-    hipError_t first = hipSuccess;
-    for (const auto &b : bufs) {
-        const hipError_t e = b.first->ptr ? hipFree(b.first->ptr) : hipSuccess;
-        if (first == hipSuccess) first = e;
-        b.first->ptr = nullptr;
-        b.first->bytes = 0;
-    }
-    IVR_HIP(first);
-    return IVR_OK;
-}
-
 int allocate_all(DevSizes bufs, bool zero) {
     for (const auto &b : bufs) {
         if (b.second == 0) continue;
@@ -541,21 +518,34 @@ int index_append(ivr_index *x, const float *rows, const int64_t *ids, int64_t n,
     int rc = ivr_launch_tile_rows(x, x->data, rows, x->ntotal, n, normalize, nullptr, s);
     if (rc != IVR_OK) return rc;
     if (ids && n > 0) IVR_HIP(hipMemcpyAsync(x->ids + x->ntotal, ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (ids) x->tab_ok = false;                  // the lookup table of ivr_index_find_ids is rebuilt by its next lookup
     x->ntotal += n;
     return IVR_OK;
 }
 
 }  // namespace
 
+int ivr_release(DevSizes bufs) {
+    hipError_t first = hipSuccess;
+    for (const auto &b : bufs) {
+        const hipError_t e = b.first->ptr ? hipFree(b.first->ptr) : hipSuccess;
+        if (first == hipSuccess) first = e;
+        b.first->ptr = nullptr;
+        b.first->bytes = 0;
+    }
+    IVR_HIP(first);
+    return IVR_OK;
+}
+
 int ivr_reserve(DevSizes bufs, bool zero) {
     bool enough = true;
     for (const auto &b : bufs) enough = enough && b.second <= b.first->bytes;
     if (enough) return IVR_OK;
-    int rc = release_all(bufs);
+    int rc = ivr_release(bufs);
     if (rc == IVR_OK) rc = allocate_all(bufs, zero);
     // all or nothing: after a failed allocation no buffer of the group is left behind, so the next call starts over and reports the
     // error again instead of finding some buffers present and launching on the missing ones
-    if (rc != IVR_OK) (void)release_all(bufs);
+    if (rc != IVR_OK) (void)ivr_release(bufs);
     return rc;
 }
 
@@ -621,6 +611,9 @@ int ivr_index_create(ivr_ctx *ctx, int d, int64_t capacity_rows, ivr_index **out
         const char *rc = getenv("IVR_REMOVE_CHUNK_ROWS");
         const long long rows = rc ? atoll(rc) : 0;
         if (rows > 0) x->remove_chunk = ivr_round_up(std::min<long long>(rows, 1ll << 22), kGroupRows);
+        // ivr_index_find_ids: lookups of at least this many keys go through the hash table (0: always, a huge value: never)
+        const char *ft = getenv("IVR_FIND_TABLE_MIN_KEYS");
+        x->find_table_min = ft && ft[0] ? std::max<long long>(0, atoll(ft)) : kFindTableMinKeys;
     }
     // an even number of pieces per tile: the large-batch scan steps K by two pieces; an odd tail piece stays all zero on both sides
     x->pieces = (int)ivr_round_up(x->pieces, 2);
@@ -657,11 +650,14 @@ int ivr_index_reset(ivr_index *x) {
     x->ntotal = 0;
     // the mode is undecided again: the next ivr_index_add makes a plain index, the next ivr_index_add_with_ids an id-mapped one
     x->has_ids = false;
+    x->tab_ok = false;
+    x->tab_slots = 0;
     if (x->ids) {
         int64_t *old = x->ids;
         x->ids = nullptr;
         IVR_HIP(hipDeviceSynchronize());         // work that may still read the table
         IVR_HIP(hipFree(old));
+        return ivr_release({{&x->tab_keys, 0}, {&x->tab_rows, 0}});      // the lookup table goes with the ids
     }
     return IVR_OK;
 }
@@ -821,6 +817,7 @@ int ivr_index_remove_ids(ivr_index *x, int64_t id_base, const ivr_id_filter *fil
             if (x->scan16) IVR_HIP(hipMemsetAsync(x->data16 + t0 * x->pieces * 64, 0, (size_t)tile16_bytes(x, (t1 - t0) * 16), s));
         }
         x->ntotal = keep;
+        x->tab_ok = false;                       // rows moved: the lookup table of ivr_index_find_ids is stale
         if (n_removed) *n_removed = removed;
         return IVR_OK;
     });

@@ -2,7 +2,8 @@
 // the top-k driver), search_range.hip (range search), search_scanq.hip (the large-query-batch candidate scan) and search_ids.hip (the
 // id table of an id-mapped index).  It holds what more
 // than one of them needs: the index object with the plan of a search, the view a search scans, the row mask of a filtered search, and
-// the launchers that are defined in one file and called from another.  Not part of the C ABI.
+// the launchers that are defined in one file and called from another.  search_rows.hip (gather / scatter of rows by position) uses it
+// too.  Not part of the C ABI.
 #pragma once
 #include "ivr_common.h"
 
@@ -14,6 +15,9 @@
 
 constexpr int kGroupRows = 64;       // rows per scan group (4 MFMA row tiles)
 constexpr int kBigChunk = 1024;      // queries per launch chain of the large-batch scan
+// default of IVR_FIND_TABLE_MIN_KEYS (ivr_index_find_ids): the smallest measured key count at which a table lookup INCLUDING one rebuild
+// beats the scan on 1M rows (0.161 ms against 0.171 ms; at 256 keys the scan's 0.097 ms wins; profiles/r14a_bench_row_access.log)
+constexpr long long kFindTableMinKeys = 512;
 constexpr int kBigMaxK = 128;        // beyond this k the chunks of 64 queries are used (candidate lists grow with k)
 
 // One launch of the large-query candidate scan: every stored row against every query of the batch on the bf16 MFMA,
@@ -85,6 +89,18 @@ __device__ __forceinline__ void mfma_chunk4(f32x4 &acc, const float4 &a, const f
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
 }
 
+// One quad of a row-major float32 row for the tiled layouts: floats k0 .. k0 + 3 of `row`, zero past d.  vec: one 16-byte load (the
+// caller guarantees k0 + 3 < d and the alignment)
+__device__ __forceinline__ float4 ivr_load_quad(const float *__restrict__ row, int k0, int d, bool vec) {
+    if (vec) return *reinterpret_cast<const float4 *>(row + k0);
+    float4 v;
+    v.x = k0 + 0 < d ? row[k0 + 0] : 0.f;
+    v.y = k0 + 1 < d ? row[k0 + 1] : 0.f;
+    v.z = k0 + 2 < d ? row[k0 + 2] : 0.f;
+    v.w = k0 + 3 < d ? row[k0 + 3] : 0.f;
+    return v;
+}
+
 // Grow-only device buffer: DevMem owns the block and frees it in its destructor, DevBuf<T> is the same block read as a T *.  Grown
 // by ivr_reserve (search_index.hip).
 struct DevMem {
@@ -107,6 +123,8 @@ struct DevBuf : DevMem {
 // or nothing: when an allocation fails the whole group is left empty and the error returned, so a repeated call tries again.
 typedef std::initializer_list<std::pair<DevMem *, size_t>> DevSizes;
 int ivr_reserve(DevSizes bufs, bool zero = false);
+// every buffer of the group empty again (the sizes are not read); the first error, if any
+int ivr_release(DevSizes bufs);
 
 struct ivr_index {
     ivr_ctx *ctx = nullptr;
@@ -158,6 +176,14 @@ struct ivr_index {
     int64_t *ids = nullptr;          // DEV [cap] while has_ids: grows with the rows (index_alloc), entries >= ntotal are never read
     DevBuf<uint64_t> ids_rows;       // DEV [cap / 64] row bitmap of a filter over stored ids: bit i of word g = row 64 g + i is allowed
     DevBuf<int64_t> ids_moved;       // DEV [rows from the first removed one on]: their surviving ids in order (ivr_index_remove_ids)
+    // hash table from stored id to lowest row (ivr_index_find_ids, search_ids.hip): open addressing, linear probing, empty key -1
+    int64_t find_table_min = 0;      // IVR_FIND_TABLE_MIN_KEYS: lookups of at least this many keys use the table (read at creation)
+    DevBuf<int64_t> tab_keys;        // DEV [tab_slots]: nothing until the first table lookup; freed by ivr_index_reset
+    DevBuf<unsigned long long> tab_rows;     // DEV [tab_slots]: the lowest row that holds the slot's key
+    int64_t tab_slots = 0;           // power of two >= 2 ntotal of the build
+    bool tab_ok = false;             // the table matches ids[0 .. ntotal): cleared by add_with_ids, remove_ids and reset
+    // ivr_index_search_reconstruct (search_rows.hip): the row position behind every result slot of a search
+    DevBuf<int64_t> rpos;            // DEV [nq][k], sized by ivr_index_reserve_search
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity
@@ -222,6 +248,12 @@ int with_view(ivr_index *x, int64_t id_base, const ivr_id_filter *f, hipStream_t
 // alongside)
 int ivr_launch_tile_rows(ivr_index *x, float *dst, const float *src, int64_t start, int64_t n, int normalize, int32_t *nonfinite,
                          hipStream_t s, const int64_t *start_dev = nullptr, int64_t max_tiles = 0);
+// search_rows.hip.  out[i] = stored row row_base + rows[i] (row-major float32); NaN rows for negative entries and for rows outside
+// [0, ntotal); the caller holds x->mu
+int ivr_launch_gather(ivr_index *x, const int64_t *rows, int64_t row_base, int64_t n, float *out, hipStream_t s);
+// search.hip.  The search of ivr_index_search_filtered over view v that also leaves the row behind every result slot in x->rpos (DEV
+// [nq][k]: its number in the view, -1 for an unused slot); the caller holds x->mu
+int ivr_search_view_pos(ivr_index *x, const View &v, const float *q, int nq, int k, int normalize_q, float *D, int64_t *I, hipStream_t s);
 // search.hip.  Tiled query buffers for `qtiles` 16-query tiles, and the group maxima of one scan chunk (grow-only); the float32
 // scan of 16*qt query columns (tile_flag: see scan_groupmax_kernel) and the bf16 candidate scan of the query tiles from tile0 on,
 // both into x->gmax

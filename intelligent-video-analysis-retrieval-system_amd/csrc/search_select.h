@@ -101,7 +101,10 @@ struct SrcPacked {     // shard merge straight from the all-gather buffer: candi
 
 // OUT_DI_IDS: OUT_DI on an id-mapped index, the label of row r is ids[r] (the table travels in the I_parts argument); an
 // instantiation of its own, so that the kernels a plain index launches stay as they are
-enum { OUT_GROUPS = 0, OUT_DI = 1, OUT_DI_PARTS = 2, OUT_DI_PACKED = 3, OUT_DI_IDS = 4 };
+// OUT_DI_POS / OUT_DI_IDS_POS (ivr_index_search_reconstruct): OUT_DI / OUT_DI_IDS that also report the row behind every result slot,
+// as its number in the scanned view (-1 for an unused slot), into an int64 [nq][k] buffer that travels in the out_groups argument
+// (unused by every OUT_DI* otherwise).  Instantiations of their own again: the kernels of every other search keep their code.
+enum { OUT_GROUPS = 0, OUT_DI = 1, OUT_DI_PARTS = 2, OUT_DI_PACKED = 3, OUT_DI_IDS = 4, OUT_DI_POS = 5, OUT_DI_IDS_POS = 6 };
 
 constexpr int kRegKeys = 16;   // keys cached per thread: n <= 16 * 1024 is selected without re-reading global memory
 
@@ -317,16 +320,17 @@ __global__ __launch_bounds__(kSelThreads) void select_topk_kernel(Src src, int q
                 } else if (OUT == OUT_DI_PACKED) {
                     const int32_t *c = ((const SrcPacked *)&src)->at(q, low);
                     id = ((int64_t)c[2] << 32) | (uint32_t)c[1];
-                } else if (OUT == OUT_DI_IDS) {
+                } else if (OUT == OUT_DI_IDS || OUT == OUT_DI_IDS_POS) {
                     id = I_parts[low];
                 } else {
                     id = id_base + (int64_t)low;
                 }
             }
             I[qo * k + j] = id;
+            if (OUT == OUT_DI_POS || OUT == OUT_DI_IDS_POS) reinterpret_cast<int64_t *>(out_groups)[qo * k + j] = key ? (int64_t)low : -1;
         }
     }
-    if ((OUT == OUT_DI || OUT == OUT_DI_IDS) && vf.ok && tid == 0) {
+    if ((OUT == OUT_DI || OUT == OUT_DI_IDS || OUT == OUT_DI_POS || OUT == OUT_DI_IDS_POS) && vf.ok && tid == 0) {
         const uint32_t g = vf.sel[(int64_t)q * vf.ksel2 + vf.kp];
         int good = 1;
         if (g != 0xFFFFFFFFu) {                       // there IS an excluded group
@@ -364,6 +368,7 @@ struct SelectOut {
     VerifyArgs vf;
     int *reset_flags = nullptr;           // tile flags [4] zeroed by this launch
     ListArgs la;
+    int64_t *pos = nullptr;               // final selection of a search: [nq][k] rows of the view behind the slots (OUT_DI*_POS), or NULL
     static SelectOut to_groups(uint32_t *groups) {
         SelectOut o;
         o.groups = groups;
@@ -382,14 +387,19 @@ struct SelectOut {
 // one workgroup per query; the block size follows the number of keys
 template <int OUT, typename Src>
 void launch_select(const Src &src, int nq, int k, const SelectOut &o, hipStream_t s) {
-    hipLaunchKernelGGL((select_topk_kernel<Src, OUT>), dim3(nq), dim3(sel_threads(src.n)), 0, s, src, 0, k, o.id_base, o.groups, o.D, o.I,
-                       OUT == OUT_DI_IDS ? o.ids : o.I_parts, o.skip, o.vf, o.reset_flags, o.la);
+    constexpr bool kPos = OUT == OUT_DI_POS || OUT == OUT_DI_IDS_POS, kIds = OUT == OUT_DI_IDS || OUT == OUT_DI_IDS_POS;
+    hipLaunchKernelGGL((select_topk_kernel<Src, OUT>), dim3(nq), dim3(sel_threads(src.n)), 0, s, src, 0, k, o.id_base,
+                       kPos ? reinterpret_cast<uint32_t *>(o.pos) : o.groups, o.D, o.I, kIds ? o.ids : o.I_parts, o.skip, o.vf, o.reset_flags,
+                       o.la);
 }
 
 // the final selection of a search (scores and labels of index rows): labels from the id table when the index has one
 template <typename Src>
 void launch_select_rows(const Src &src, int nq, int k, const SelectOut &o, hipStream_t s) {
-    if (o.ids) launch_select<OUT_DI_IDS>(src, nq, k, o, s);
+    if (o.pos) {
+        if (o.ids) launch_select<OUT_DI_IDS_POS>(src, nq, k, o, s);
+        else launch_select<OUT_DI_POS>(src, nq, k, o, s);
+    } else if (o.ids) launch_select<OUT_DI_IDS>(src, nq, k, o, s);
     else launch_select<OUT_DI>(src, nq, k, o, s);
 }
 

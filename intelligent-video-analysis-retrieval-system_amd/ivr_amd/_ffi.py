@@ -40,7 +40,7 @@ class IdFilter(C.Structure):
     _fields_ = [("lo", C.c_int64), ("hi", C.c_int64), ("bits", C.c_void_p), ("nbits", C.c_int64)]
 
 
-API_VERSION = 10
+API_VERSION = 11
 FP8_SITE = {"qkv": 1, "o": 2, "fc1": 4, "fc2": 8}
 
 
@@ -95,6 +95,9 @@ _SIGS = {
     "ivr_index_has_ids": (_i, [_p]),
     "ivr_index_get_ids": (_i, [_p, _i64, _i64, _p, _p]),
     "ivr_index_find_ids": (_i, [_p, _p, _i64, _p, _p]),
+    "ivr_index_gather": (_i, [_p, _p, _i64, _p, _p]),
+    "ivr_index_scatter": (_i, [_p, _p, _p, _i64, _i, _p]),
+    "ivr_index_search_reconstruct": (_i, [_p, _p, _i, _i, _i, _i64, C.POINTER(IdFilter), _p, _p, _p, _p]),
     "ivr_topk_merge": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_topk_pack": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "ivr_topk_merge_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),

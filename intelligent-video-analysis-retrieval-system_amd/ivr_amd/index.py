@@ -286,15 +286,91 @@ class FlatIPIndex:
         return out.cpu().numpy()
 
     def find(self, ids):
-        """rows[i] = the lowest row stored under ids[i], or -1 (numpy int64).  Every call scans the whole id table once per key: for a
-        handful of keys, such as the reference's search_by_id (core.py:932-958)."""
+        """rows[i] = the lowest row stored under ids[i], or -1 (numpy int64): the reference's search_by_id (core.py:932-958) for one
+        key, a result list or a batch of labels for many.  Few keys scan the id table; IVR_FIND_TABLE_MIN_KEYS keys or more go through
+        a device hash table that is rebuilt after add_with_ids / remove_ids / reset."""
         keys = _ids_i64(np.atleast_1d(ids) if not isinstance(ids, torch.Tensor) else ids, None, "find")
-        k = torch.from_numpy(np.ascontiguousarray(keys)).to(self.device)
+        return self._find_device(torch.from_numpy(np.ascontiguousarray(keys)).to(self.device)).cpu().numpy()
+
+    def _find_device(self, keys):
+        """keys: int64 CUDA tensor [n] of stored ids -> int64 CUDA tensor of their lowest rows (-1: not stored); no host sync."""
         rows = torch.empty(len(keys), dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_find_ids(self._h, C.c_void_p(k.data_ptr()), len(keys), C.c_void_p(rows.data_ptr()),
+            _ffi.check(self._lib.ivr_index_find_ids(self._h, C.c_void_p(keys.data_ptr()), len(keys), C.c_void_p(rows.data_ptr()),
                                                     _ffi.stream_ptr()), "ivr_index_find_ids")
-        return rows.cpu().numpy()
+        return rows
+
+    # -- row access by position / by key ---------------------------------------------------------
+    def _rows_i64(self, rows, what):
+        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.device == self.device and rows.dtype == torch.int64
+                and rows.dim() == 1 and rows.is_contiguous()):
+            raise ValueError(f"{what} expects a contiguous int64 CUDA tensor [n] on {self.device}")
+        return rows
+
+    def gather_device(self, rows):
+        """Stored rows by POSITION (plain and id-mapped index alike): rows int64 CUDA tensor [n] -> float32 CUDA tensor [n,d] with the
+        bits reconstruct_n returns; an entry outside [0, ntotal), -1 included, gives a NaN row.  Repeats are allowed.  No host sync."""
+        rows = self._rows_i64(rows, "gather_device")
+        out = torch.empty((len(rows), self.d), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self._lib.ivr_index_gather(self._h, C.c_void_p(rows.data_ptr()), len(rows), C.c_void_p(out.data_ptr()),
+                                                  _ffi.stream_ptr()), "ivr_index_gather")
+        return out
+
+    def scatter_device(self, rows, x, normalize=False):
+        """Replace the vectors at POSITIONS rows (int64 CUDA tensor [n]) by x (contiguous float32 CUDA tensor [n,d]) in one launch:
+        the index ends up bit-identical to n single-row write() calls.  Entries outside [0, ntotal) are skipped, ids stay; with a row
+        named twice, which vector it keeps is unspecified.  No host sync: rows and x must stay alive until the stream has run."""
+        rows = self._rows_i64(rows, "scatter_device")
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
+                and x.dim() == 2 and x.shape == (len(rows), self.d)):
+            raise ValueError(f"scatter_device expects a contiguous float32 CUDA tensor [{len(rows)},{self.d}]")
+        with torch.cuda.device(self.device):
+            _ffi.check(self._lib.ivr_index_scatter(self._h, C.c_void_p(rows.data_ptr()), C.c_void_p(x.data_ptr()), len(rows),
+                                                   int(bool(normalize)), _ffi.stream_ptr()), "ivr_index_scatter")
+
+    def _keys_device(self, keys, what):
+        """keys (row numbers on a plain index, stored ids on an id-mapped one) -> (numpy int64 keys, int64 CUDA tensor of their rows,
+        -1 where a key names no row)."""
+        keys = _ids_i64(np.atleast_1d(keys) if not isinstance(keys, torch.Tensor) else keys, None, what)
+        k = torch.from_numpy(np.ascontiguousarray(keys)).to(self.device)
+        if self.has_ids:
+            return keys, self._find_device(k)
+        return keys, torch.where((k >= 0) & (k < self.ntotal), k, torch.full_like(k, -1))
+
+    def reconstruct_batch_device(self, keys):
+        """(rows, R) CUDA tensors without a host sync: rows int64 [n] = the position of each key (a row number on a plain index, the
+        lowest row stored under the id on an id-mapped one; -1 when it names no row), R float32 [n,d] = those rows, NaN where -1."""
+        _, rows = self._keys_device(keys, "reconstruct_batch")
+        return rows, self.gather_device(rows)
+
+    def reconstruct_batch(self, keys):
+        """faiss reconstruct_batch(keys): numpy float32 [n,d].  Keys are row numbers on a plain index and stored ids on an id-mapped
+        one (IndexIDMap2::reconstruct: the lowest row under the id).  RuntimeError for a key that names no row, as reconstruct."""
+        keys, rows = self._keys_device(keys, "reconstruct_batch")
+        R = self.gather_device(rows)
+        missing = np.flatnonzero(rows.cpu().numpy() < 0)
+        if len(missing):
+            raise RuntimeError(f"reconstruct_batch: key {int(keys[missing[0]])} is not in the index ({len(missing)} of {len(keys)} missing)")
+        return R.cpu().numpy()
+
+    def update_vectors(self, keys, x, normalize=False):
+        """faiss IndexIVF::update_vectors on the flat index: the vectors stored under keys (as for reconstruct_batch) become x [n,d];
+        ids and every other row stay.  ValueError for duplicate keys or a wrong shape; RuntimeError when a key names no row, and then
+        nothing has been written."""
+        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"update_vectors expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        keys = _ids_i64(np.atleast_1d(keys) if not isinstance(keys, torch.Tensor) else keys, len(x), "update_vectors")
+        if len(np.unique(keys)) != len(keys):
+            raise ValueError("update_vectors: duplicate keys")
+        keys, rows = self._keys_device(keys, "update_vectors")
+        missing = np.flatnonzero(rows.cpu().numpy() < 0)
+        if len(missing):
+            raise RuntimeError(f"update_vectors: key {int(keys[missing[0]])} is not in the index ({len(missing)} of {len(keys)} missing)")
+        t = _dev_f32(x, self.device)
+        self.scatter_device(rows, t, normalize)
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()  # `t` and `rows` are temporaries
 
     def write(self, start, x, normalize=False):
         """Overwrite rows [start, start+n): ring-buffer maintenance for rolling indexes."""
@@ -362,6 +438,40 @@ class FlatIPIndex:
             if t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0):
                 torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
         return D, I
+
+    def search_and_reconstruct(self, x, k, params=None):
+        """faiss search_and_reconstruct(x, k): (D, I, R) numpy arrays, D and I exactly what search() returns and R float32 [nq,k,d]
+        the stored row behind each slot (the row that scored, also where an id-mapped index stores a label twice), NaN rows for the
+        -1 slots.  params = SearchParameters(sel=...) as for search."""
+        sel = _selector(params)
+        q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
+        if isinstance(q, np.ndarray) and q.ndim == 1:
+            q = q.reshape(1, -1)
+        D, I, R = self.search_and_reconstruct_device(q, k, sel=sel)
+        return D.cpu().numpy(), I.cpu().numpy(), R.cpu().numpy()
+
+    def search_and_reconstruct_device(self, x, k, normalize=False, id_base=0, sel=None):
+        """Device-resident search_and_reconstruct: (D, I, R) CUDA tensors, arguments as for search_device."""
+        sel = _selector(sel=sel)
+        t = _dev_f32(x, self.device)
+        if t.dim() != 2 or t.shape[1] != self.d:
+            raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({self.d})")
+        k = int(k)
+        if k < 1 or k > _ffi.IVR_MAX_K:
+            raise ValueError(f"k={k} outside [1,{_ffi.IVR_MAX_K}]")
+        nq = t.shape[0]
+        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        R = torch.empty((nq, k, self.d), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            f = None if sel is None else sel._filter(self.device)
+            _ffi.check(self._lib.ivr_index_search_reconstruct(self._h, C.c_void_p(t.data_ptr()), nq, k, int(bool(normalize)), int(id_base),
+                                                              None if f is None else C.byref(f), C.c_void_p(D.data_ptr()),
+                                                              C.c_void_p(I.data_ptr()), C.c_void_p(R.data_ptr()), _ffi.stream_ptr()),
+                       "ivr_index_search_reconstruct")
+            if t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0):
+                torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
+        return D, I, R
 
     def range_search(self, x, radius, params=None):
         """faiss range_search: every row with <q, row> > radius.  (lims int64 [nq+1], D float32 [lims[-1]], I int64 [lims[-1]])

@@ -12,7 +12,8 @@ collective is the right shape; no other exchange exists on this path.
 The class is agnostic of how a shard is searched: `local` only needs
 `search_device(q, k, normalize=, id_base=) -> (D, I)` tensors, `add`, `ntotal` (and
 `range_search_device(q, radius, normalize=, id_base=) -> (lims, D, I, total)` for range_search; both with `sel=` for a filtered
-search; `remove_ids(sel, id_base=) -> int` for remove_ids).  On GPUs that
+search; `remove_ids(sel, id_base=) -> int` for remove_ids; `reconstruct_batch_device(keys) -> (rows, R)` and `has_ids` for
+reconstruct_batch).  On GPUs that
 is `ivr_amd.index.FlatIPIndex`; the world_size-2 gloo tests on CPU plug the oracle in.
 """
 import numpy as np
@@ -143,6 +144,35 @@ class ShardedIndex:
         self.local.remove_ids(sel, id_base=self.id_base)
         self.sync_counts()
         return before - self.ntotal
+
+    def reconstruct_batch(self, ids):
+        """faiss reconstruct_batch over all shards: ids [n] GLOBAL ids, replicated on every rank -> numpy float32 [n,d], identical on
+        every rank.  Plain shards: an id is a global row and belongs to the shard whose synced bounds hold it.  Id-mapped shards: the
+        lowest rank that stores the id answers, with its lowest row under it: the lowest global storage position.  Two collectives:
+        an all-gather of the found flags (n int64 per rank), then ONE all-gather of every rank's rows, n * d * world floats in all:
+        meant for result-list sizes, not for bulk export.  RuntimeError on every rank, after both collectives (no rank is left
+        waiting), when an id names no row."""
+        keys = torch.from_numpy(np.ascontiguousarray(np.asarray(ids).reshape(-1).astype(np.int64)))
+        # plain shards: global row -> this shard's row; the rows of other shards fall outside [0, ntotal) and come back as -1
+        local_keys = keys if getattr(self.local, "has_ids", False) else keys - self.id_base
+        rows, R = self.local.reconstruct_batch_device(local_keys)
+        n = keys.numel()
+        found = (rows >= 0).to(torch.int64).contiguous()
+        R = R.contiguous()
+        if self.world > 1:
+            found_all = torch.empty(self.world * n, dtype=torch.int64, device=found.device)
+            dist.all_gather_into_tensor(found_all, found, group=self.group)
+            R_all = torch.empty((self.world * n, self.d), dtype=torch.float32, device=R.device)
+            dist.all_gather_into_tensor(R_all, R, group=self.group)
+            found_all, R_all = found_all.view(self.world, n), R_all.view(self.world, n, self.d)
+        else:
+            found_all, R_all = found.view(1, n), R.view(1, n, self.d)
+        ranks = torch.arange(self.world, device=found_all.device).unsqueeze(1)
+        owner = torch.where(found_all > 0, ranks, torch.full_like(ranks, self.world)).min(0).values      # the lowest rank that holds the id
+        missing = torch.nonzero(owner == self.world).reshape(-1).cpu()
+        if missing.numel():
+            raise RuntimeError(f"reconstruct_batch: id {int(keys[missing[0]])} is not in the index ({missing.numel()} of {n} missing)")
+        return R_all[owner, torch.arange(n, device=owner.device)].cpu().numpy()
 
     # -- search ------------------------------------------------------------------------------
     @staticmethod
