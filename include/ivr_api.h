@@ -378,6 +378,31 @@ int ivr_index_search_reconstruct(ivr_index *idx, const float *q /*DEV*/, int nq,
                                  const ivr_id_filter *filter /*HOST, may be NULL*/, float *D /*DEV*/, int64_t *I /*DEV*/,
                                  float *R /*DEV*/, ivr_stream stream);
 
+/* ---- inverted lists (faiss IndexIVFFlat) -------------------------------------------------------------
+ * An inverted-file index is an ivr_index whose rows are ordered by list: list l is the run of rows [list_off[l], list_off[l + 1])
+ * (list_off ascending, list_off[nlist] <= ntotal; the caller keeps the rows in that order, ivr_amd/ivf.py does it with gather +
+ * add_with_ids).  ivr_index_search_lists is faiss search_preassigned: query i is scored against the rows of the lists
+ * assign[i][0 .. p) only, and D / I are the top k of those rows under the contract of ivr_index_search (labels from the id table on
+ * an id-mapped index, else the row number; unused slots -FLT_MAX / -1).  A score is the float32 inner product ivr_index_search
+ * computes, to the bit; equal scores rank the lower row first, i.e. the lower list and inside a list the row stored first, whatever
+ * the order of a row of assign.
+ *   assign          DEV int64 [nq][p], EVERY ROW ASCENDING.  Entries outside [0, nlist) (-1, the empty slot of a coarse search,
+ *                   included) are skipped; a list named twice in a row is scanned once (the two entries are adjacent).
+ *   max_probe_rows  an upper bound of the rows any one query probes (the sum of its lists' sizes), e.g. the sum of the p longest
+ *                   lists; clipped to ntotal.  It sizes the scratch: 8 bytes per probed row and query.  A query that probes more rows
+ *                   than this bound returns no result at all (never a write outside the scratch).
+ * The queries are worked off in chunks so that the scratch stays at 2^25 keys (256 MiB) or one query's max_probe_rows keys, whichever
+ * is larger, plus 20 bytes per (query, list) pair of a chunk (at most 2^22 pairs).  Within a chunk a list is read once per 16 of the
+ * queries that probe it.  Enqueue-only once the scratch has grown (a call that grows it allocates); not graph-capturable then. */
+int ivr_index_search_lists(ivr_index *idx, const int64_t *list_off /*DEV [nlist+1]*/, int nlist, const float *q /*DEV [nq,d]*/, int nq,
+                           const int64_t *assign /*DEV [nq][p]*/, int p, int64_t max_probe_rows, int k, int normalize_q,
+                           float *D /*DEV [nq,k]*/, int64_t *I /*DEV [nq,k]*/, ivr_stream stream);
+/* The centroid update of k-means: out[s] = the mean of rows[seg_off[s] .. seg_off[s + 1]) (row-major float32 [n,d]; seg_off ascending,
+ * clipped to [0, n]), divided by its L2 norm when normalize (a zero mean stays zero).  Every column is summed in ascending row order
+ * in double precision without atomics, so the result has the same bits on every run.  An empty segment gives a row of NaNs. */
+int ivr_segment_mean(ivr_ctx *ctx, const float *rows /*DEV [n,d]*/, int64_t n, const int64_t *seg_off /*DEV [nseg+1]*/, int nseg, int d,
+                     int normalize, float *out /*DEV [nseg,d]*/, ivr_stream stream);
+
 /* Merge per-shard candidate lists (the reference's concat + sort of peer results, system.py:1744-1746):
  * D_parts/I_parts DEV [parts, nq, k] with global ids, parts ordered by ascending id range. */
 int ivr_topk_merge(ivr_ctx *ctx, const float *D_parts /*DEV*/, const int64_t *I_parts /*DEV*/, int parts,

@@ -184,6 +184,14 @@ struct ivr_index {
     bool tab_ok = false;             // the table matches ids[0 .. ntotal): cleared by add_with_ids, remove_ids and reset
     // ivr_index_search_reconstruct (search_rows.hip): the row position behind every result slot of a search
     DevBuf<int64_t> rpos;            // DEV [nq][k], sized by ivr_index_reserve_search
+    // inverted-list search (ivr_index_search_lists, search_ivf.hip), one chunk of queries; grow-only
+    DevBuf<uint64_t> ivf_keys;       // DEV [queries of a chunk][rows one query may probe]: (ordered score, ~row) of every probed row
+    DevBuf<int64_t> ivf_slot;        // DEV [queries of a chunk][p]: first key slot of each probed list, -1 for a skipped entry
+    DevBuf<int64_t> ivf_qtotal;      // DEV [queries of a chunk]: rows each query probes
+    DevBuf<int> ivf_count;           // DEV [nlist]: queries per list, then the fill cursors
+    DevBuf<int64_t> ivf_off;         // DEV [nlist + 1] pairs in front of each list, then [nlist + 1] 16-query pair tiles in front of it
+    DevBuf<int> ivf_pair_q;          // DEV [pairs of a chunk]: the (query, list) pairs grouped by list: the query of the chunk ...
+    DevBuf<int64_t> ivf_pair_slot;   // ... and its first key slot for that list
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

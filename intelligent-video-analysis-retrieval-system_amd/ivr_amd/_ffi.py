@@ -98,6 +98,8 @@ _SIGS = {
     "ivr_index_gather": (_i, [_p, _p, _i64, _p, _p]),
     "ivr_index_scatter": (_i, [_p, _p, _p, _i64, _i, _p]),
     "ivr_index_search_reconstruct": (_i, [_p, _p, _i, _i, _i, _i64, C.POINTER(IdFilter), _p, _p, _p, _p]),
+    "ivr_index_search_lists": (_i, [_p, _p, _i, _p, _i, _p, _i, _i64, _i, _i, _p, _p, _p]),
+    "ivr_segment_mean": (_i, [_p, _p, _i64, _p, _i, _i, _i, _p, _p]),
     "ivr_topk_merge": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_topk_pack": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "ivr_topk_merge_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
