@@ -403,6 +403,42 @@ int ivr_index_search_lists(ivr_index *idx, const int64_t *list_off /*DEV [nlist+
 int ivr_segment_mean(ivr_ctx *ctx, const float *rows /*DEV [n,d]*/, int64_t n, const int64_t *seg_off /*DEV [nseg+1]*/, int nseg, int d,
                      int normalize, float *out /*DEV [nseg,d]*/, ivr_stream stream);
 
+/* ---- binary codes (faiss IndexBinaryFlat, and the sign-bit encoder of IndexLSH) --------------------------
+ * Stands in for faiss.IndexLSH(dimension, 256), one of the index types of _create_index (core.py:1198-1230): a row is stored as
+ * nbits sign bits (32 bytes at 256 bits, where the flat index stores 2-4.6 KB) and ranked by Hamming distance.
+ * A code is code_size = (nbits + 7) / 8 caller-facing bytes in faiss order: bit j of a code is bit j & 7 of byte j >> 3
+ * (numpy.packbits(..., bitorder="little")).  The bits of the last byte at or above nbits are pad bits: they are ignored in stored
+ * codes and in query codes alike, and ivr_bin_index_get_codes returns them as 0.  On the device a code is padded with zeros to whole
+ * 16-byte words and the rows are interleaved per 64, so that one lane reads one row with 16-byte loads and a wave reads 1 KiB
+ * contiguous per load ("binary codes").  The allocation grows like ivr_index's; capacity below 2^31 rows. */
+typedef struct ivr_bin_index ivr_bin_index;
+#define IVR_BIN_MAX_BITS 2048
+int ivr_bin_index_create(ivr_ctx *ctx, int nbits, int64_t capacity_rows, ivr_bin_index **out);   /* 1 <= nbits <= IVR_BIN_MAX_BITS */
+int ivr_bin_index_destroy(ivr_bin_index *idx);
+int ivr_bin_index_reset(ivr_bin_index *idx);                /* ntotal = 0 */
+int64_t ivr_bin_index_ntotal(ivr_bin_index *idx);
+int ivr_bin_index_block_rows(void);     /* rows per workgroup block of the search passes: tests size their cases from it */
+/* append n codes; grows the allocation when the capacity is exceeded (a call that grows synchronises the device) */
+int ivr_bin_index_add(ivr_bin_index *idx, const uint8_t *codes /*DEV [n][code_size]*/, int64_t n, ivr_stream stream);
+/* codes of rows [start, start + n) as they were added (pad bits 0); start + n <= ntotal */
+int ivr_bin_index_get_codes(ivr_bin_index *idx, int64_t start, int64_t n, uint8_t *out /*DEV [n][code_size]*/, ivr_stream stream);
+/* Exact top k by Hamming distance: D ascending, equal distances rank the lower row first, unused slots (k > ntotal, empty index)
+ * hold INT32_MAX in D and -1 in I, as faiss's integer heap leaves them.  1 <= k <= IVR_MAX_K, nq >= 1.  The top k is selected by
+ * counting (histogram of distances per query, threshold distance, ranks by prefix sums: no float compares, no cursor atomics, the
+ * same rows on every run).  Scratch: 16-byte-padded queries, and per chunk of at most 64 queries 4 (nbits + 1) + 8 ntotal / 64 + 8 k
+ * bytes per query; nothing is written per (query, row) pair.  Enqueue-only once the scratch has grown (a call that grows it
+ * allocates and cannot be captured into a hipGraph). */
+int ivr_bin_index_search(ivr_bin_index *idx, const uint8_t *qcodes /*DEV [nq][code_size]*/, int nq, int k, int32_t *D /*DEV [nq][k]*/,
+                         int64_t *I /*DEV [nq][k]*/, ivr_stream stream);
+/* faiss IndexLSH's encoder: proj[i][j] = <x[i], rot[j]> accumulated in float32 on the float32 MFMA in a fixed order (no atomics:
+ * the same input gives the same bits on every run); rot == NULL: proj[i][j] = x[i][j], which needs nbits <= d (faiss's "first nbits
+ * coordinates").  Bit j of code i is set iff proj[i][j] - thr[j] >= 0.0f (thr == NULL: 0; faiss fvecs2bitvecs after the threshold
+ * subtraction); pad bits are written as 0.  proj != NULL also receives the float32 projections, before the threshold (threshold
+ * training reads them).  x: DEV float32 [n][d], 1 <= d <= 65536; n == 0 is a no-op. */
+int ivr_sign_encode(ivr_ctx *ctx, const float *x /*DEV [n][d]*/, int64_t n, int d, const float *rot /*DEV [nbits][d] or NULL*/,
+                    const float *thr /*DEV [nbits] or NULL*/, int nbits, uint8_t *codes /*DEV [n][code_size]*/,
+                    float *proj /*DEV [n][nbits] or NULL*/, ivr_stream stream);
+
 /* Merge per-shard candidate lists (the reference's concat + sort of peer results, system.py:1744-1746):
  * D_parts/I_parts DEV [parts, nq, k] with global ids, parts ordered by ascending id range. */
 int ivr_topk_merge(ivr_ctx *ctx, const float *D_parts /*DEV*/, const int64_t *I_parts /*DEV*/, int parts,

@@ -100,6 +100,15 @@ _SIGS = {
     "ivr_index_search_reconstruct": (_i, [_p, _p, _i, _i, _i, _i64, C.POINTER(IdFilter), _p, _p, _p, _p]),
     "ivr_index_search_lists": (_i, [_p, _p, _i, _p, _i, _p, _i, _i64, _i, _i, _p, _p, _p]),
     "ivr_segment_mean": (_i, [_p, _p, _i64, _p, _i, _i, _i, _p, _p]),
+    "ivr_bin_index_create": (_i, [_p, _i, _i64, C.POINTER(_p)]),
+    "ivr_bin_index_destroy": (_i, [_p]),
+    "ivr_bin_index_reset": (_i, [_p]),
+    "ivr_bin_index_ntotal": (_i64, [_p]),
+    "ivr_bin_index_block_rows": (_i, []),
+    "ivr_bin_index_add": (_i, [_p, _p, _i64, _p]),
+    "ivr_bin_index_get_codes": (_i, [_p, _i64, _i64, _p, _p]),
+    "ivr_bin_index_search": (_i, [_p, _p, _i, _i, _p, _p, _p]),
+    "ivr_sign_encode": (_i, [_p, _p, _i64, _i, _p, _p, _i, _p, _p, _p]),
     "ivr_topk_merge": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_topk_pack": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "ivr_topk_merge_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),

@@ -1,0 +1,329 @@
+"""FAISS-shaped binary indexes resident in MI355X HBM: IndexBinaryFlat (exact Hamming top-k) and IndexLSH (sign bits of a random
+rotation, ranked by Hamming distance).
+
+Stands in for the `faiss.IndexLSH(dimension, 256)` the reference accepts in `_create_index` (`core.py:1198-1230`).  A row is stored
+as `nbits` sign bits (32 bytes at 256 bits), the search is popcount(xor) over the dense code array, and the top k is found by
+counting, exactly: distances ascending, equal distances rank the LOWER ROW first, unused slots hold the largest int32 and -1 as
+faiss's integer heap leaves them.  The encoder (float32 MFMA projection + sign packing) and every search pass are HIP kernels of
+libivr_hip.so (csrc/search_binary.hip); torch stages arrays and sorts the training projections.
+
+Codes are uint8 [n, code_size] in faiss order: bit j of a code is bit j & 7 of byte j >> 3, i.e.
+numpy.packbits(bits, axis=1, bitorder="little").
+
+faiss's own random stream cannot be reproduced here, so the default rotation is defined by `lsh_rotation` (numpy, seeded); a matrix
+exported from a real faiss index can be assigned to `IndexLSH.rrot` while the index is empty and then reproduces that index's codes.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _ffi
+from .index import _dev_f32
+
+METRIC_L2 = 1                 # faiss.METRIC_L2: what faiss.IndexLSH reports as its metric_type
+_ENCODE_CHUNK = 1 << 18       # rows of a host array staged per encoder launch
+
+
+def lsh_rotation(d, nbits, seed=5):
+    """The default rotation of IndexLSH, float32 [nbits, d], pure numpy: with m = max(d, nbits), A = RandomState(seed)
+    .standard_normal((m, m)) in float64, Q R = A and the sign fixed so that diag(R) > 0, it is Q[:nbits, :d].  Its rows are
+    orthonormal when nbits <= d and its columns when nbits > d (the shape of faiss's RandomRotationMatrix)."""
+    d, nbits = int(d), int(nbits)
+    if d < 1 or nbits < 1:
+        raise ValueError(f"lsh_rotation: d={d} nbits={nbits}")
+    m = max(d, nbits)
+    a = np.random.RandomState(int(seed)).standard_normal((m, m))
+    q, r = np.linalg.qr(a)
+    q *= np.sign(np.diag(r))
+    return np.ascontiguousarray(q[:nbits, :d], dtype=np.float32)
+
+
+def _dev_u8(x, width, device, what):
+    """numpy / torch uint8 [n, width] -> contiguous uint8 CUDA tensor on `device` (a view when already there)."""
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.uint8:
+            raise ValueError(f"{what}: codes must be uint8, got {x.dtype}")
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise ValueError(f"{what}: codes must be a uint8 numpy array or torch tensor")
+    if x.dim() == 1 and width and x.shape[0] == width:
+        x = x.reshape(1, -1)
+    if x.dim() != 2 or x.shape[1] != width:
+        raise ValueError(f"{what} expects uint8 [n,{width}], got {tuple(x.shape)}")
+    return x.to(device=device).contiguous()
+
+
+class BinaryFlatIndex:
+    """Exact Hamming-distance index over binary codes (FAISS IndexBinaryFlat contract) on one GPU.  d_bits is the code length in
+    bits and must be a multiple of 8, as in faiss; a code is d_bits / 8 bytes."""
+
+    def __init__(self, d_bits, device=None):
+        d_bits = int(d_bits)
+        if d_bits < 8 or d_bits % 8 != 0:
+            raise ValueError(f"BinaryFlatIndex: d={d_bits} must be a positive multiple of 8")
+        self._lib = _ffi.load()
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+        self.d = d_bits
+        self.code_size = d_bits // 8
+        self.is_trained = True
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _ffi.check(self._lib.ivr_bin_index_create(_ffi.context(self.device.index), self.d, 0, C.byref(h)), "ivr_bin_index_create")
+        self._h = h
+
+    @property
+    def ntotal(self):
+        return int(self._lib.ivr_bin_index_ntotal(self._h))
+
+    def train(self, x):
+        return None
+
+    def add(self, codes):
+        """Append codes: uint8 [n, d/8], a numpy array or a torch tensor."""
+        self._add_device(_dev_u8(codes, self.code_size, self.device, "add"))
+
+    def _add_device(self, t):
+        with torch.cuda.device(self.device):
+            _ffi.check(self._lib.ivr_bin_index_add(self._h, C.c_void_p(t.data_ptr()), t.shape[0], _ffi.stream_ptr()), "ivr_bin_index_add")
+            torch.cuda.current_stream().synchronize()  # `t` may be a temporary staging copy
+
+    def search(self, codes, k):
+        """(D, I) numpy arrays: D int32 [nq,k] Hamming distances ascending, I int64 row numbers; equal distances rank the lower row
+        first; unused slots (2147483647, -1)."""
+        D, I = self.search_device(codes, k)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    def search_device(self, codes, k):
+        """search returning CUDA tensors; no host synchronisation unless `codes` had to be staged."""
+        t = _dev_u8(codes, self.code_size, self.device, "search")
+        k = int(k)
+        if k < 1 or k > _ffi.IVR_MAX_K:
+            raise ValueError(f"k={k} outside [1,{_ffi.IVR_MAX_K}]")
+        nq = t.shape[0]
+        if nq < 1:
+            raise ValueError("search: no queries")
+        staged = t.data_ptr() != (codes.data_ptr() if isinstance(codes, torch.Tensor) else 0)
+        D = torch.empty((nq, k), dtype=torch.int32, device=self.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self._lib.ivr_bin_index_search(self._h, C.c_void_p(t.data_ptr()), nq, k, C.c_void_p(D.data_ptr()),
+                                                      C.c_void_p(I.data_ptr()), _ffi.stream_ptr()), "ivr_bin_index_search")
+            if staged:
+                torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
+        return D, I
+
+    def reconstruct_n(self, start=0, n=None):
+        """The stored codes of rows [start, start + n) as numpy uint8 [n, d/8]."""
+        return self._codes_device(start, n).cpu().numpy()
+
+    def _codes_device(self, start=0, n=None):
+        start = int(start)
+        n = self.ntotal - start if n is None else int(n)
+        if start < 0 or n < 0 or start + n > self.ntotal:
+            raise ValueError(f"reconstruct_n: rows [{start},{start + n}) outside [0,{self.ntotal})")
+        out = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device)
+        if n:
+            with torch.cuda.device(self.device):
+                _ffi.check(self._lib.ivr_bin_index_get_codes(self._h, start, n, C.c_void_p(out.data_ptr()), _ffi.stream_ptr()),
+                           "ivr_bin_index_get_codes")
+        return out
+
+    def reset(self):
+        _ffi.check(self._lib.ivr_bin_index_reset(self._h), "ivr_bin_index_reset")
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.ivr_bin_index_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def IndexBinaryFlat(d):
+    """faiss.IndexBinaryFlat(d) drop-in: d is the code length in bits, a multiple of 8."""
+    return BinaryFlatIndex(d)
+
+
+class IndexLSH:
+    """faiss.IndexLSH(d, nbits, rotate_data, train_thresholds) on one GPU: bit j of a row's code is the sign of
+    <x, rrot[j]> - thresholds[j] (>= 0 sets the bit), and search ranks the stored codes by Hamming distance to the query's code.
+
+    search(x, k) returns (D float32, I int64): the Hamming distance as a float, ascending, equal distances rank the lower row first,
+    unused slots (2147483648.0, -1).  rotate_data=False takes the first nbits coordinates instead of a rotation and needs
+    nbits <= d.  train_thresholds=True makes train(x) set thresholds[j] to the median of projection j over x (element n // 2 of the
+    sorted column); add() raises RuntimeError until then."""
+
+    def __init__(self, d, nbits, rotate_data=True, train_thresholds=False, seed=5, device=None):
+        self.d, self.nbits = int(d), int(nbits)
+        if self.d < 1 or self.d > 65536 or self.nbits < 1 or self.nbits > 2048:
+            raise ValueError(f"IndexLSH: d={d} outside [1,65536] or nbits={nbits} outside [1,2048]")
+        self.rotate_data, self.train_thresholds = bool(rotate_data), bool(train_thresholds)
+        if not self.rotate_data and self.nbits > self.d:
+            raise ValueError(f"IndexLSH: rotate_data=False needs nbits={self.nbits} <= d={self.d}")
+        self.code_size = (self.nbits + 7) // 8
+        self.metric_type = METRIC_L2
+        self.is_trained = not self.train_thresholds
+        self._index = BinaryFlatIndex(8 * self.code_size, device=device)
+        self.device = self._index.device
+        self._lib = self._index._lib
+        self._rrot = lsh_rotation(self.d, self.nbits, seed)
+        self._thresholds = np.zeros(self.nbits, np.float32)
+        self._rot_dev = self._thr_dev = None
+
+    # -- attributes ------------------------------------------------------------------------------
+    @property
+    def ntotal(self):
+        return self._index.ntotal
+
+    @property
+    def rrot(self):
+        """numpy float32 [nbits, d]: row j is the direction of bit j.  Assignable while the index is empty."""
+        return self._rrot
+
+    @rrot.setter
+    def rrot(self, m):
+        if self.ntotal:
+            raise RuntimeError(f"rrot: the index holds {self.ntotal} rows encoded with the current rotation")
+        m = np.asarray(m)
+        if m.shape != (self.nbits, self.d):
+            raise ValueError(f"rrot expects [{self.nbits},{self.d}], got {m.shape}")
+        self._rrot = np.ascontiguousarray(m, dtype=np.float32)
+        self._rot_dev = None
+
+    @property
+    def thresholds(self):
+        """numpy float32 [nbits]; applied only when train_thresholds is set.  Assignable while the index is empty."""
+        return self._thresholds
+
+    @thresholds.setter
+    def thresholds(self, t):
+        if self.ntotal:
+            raise RuntimeError(f"thresholds: the index holds {self.ntotal} rows encoded with the current thresholds")
+        t = np.asarray(t)
+        if t.shape != (self.nbits,):
+            raise ValueError(f"thresholds expects [{self.nbits}], got {t.shape}")
+        self._thresholds = np.ascontiguousarray(t, dtype=np.float32)
+        self._thr_dev = None
+
+    @property
+    def codes(self):
+        """The stored codes, numpy uint8 [ntotal, code_size]."""
+        return self._index.reconstruct_n()
+
+    # -- encoding --------------------------------------------------------------------------------
+    def _rows(self, x, what):
+        if isinstance(x, np.ndarray) and x.ndim == 1:
+            x = x.reshape(1, -1)
+        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"{what} expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        return x
+
+    def _encode_device(self, t, want_proj=False, use_thresholds=True):
+        """t: contiguous float32 CUDA tensor [n,d] -> (codes uint8 CUDA [n,code_size], proj float32 CUDA [n,nbits] or None)."""
+        n = t.shape[0]
+        codes = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device)
+        proj = torch.empty((n, self.nbits), dtype=torch.float32, device=self.device) if want_proj else None
+        with torch.cuda.device(self.device):
+            rot = thr = None
+            if self.rotate_data:
+                if self._rot_dev is None:
+                    self._rot_dev = torch.from_numpy(self._rrot).to(self.device)
+                rot = C.c_void_p(self._rot_dev.data_ptr())
+            if self.train_thresholds and use_thresholds:
+                if self._thr_dev is None:
+                    self._thr_dev = torch.from_numpy(self._thresholds).to(self.device)
+                thr = C.c_void_p(self._thr_dev.data_ptr())
+            _ffi.check(self._lib.ivr_sign_encode(_ffi.context(self.device.index), C.c_void_p(t.data_ptr()), n, self.d, rot, thr, self.nbits,
+                                                 C.c_void_p(codes.data_ptr()), C.c_void_p(proj.data_ptr()) if want_proj else None,
+                                                 _ffi.stream_ptr()), "ivr_sign_encode")
+        return codes, proj
+
+    def _chunks(self, x):
+        """x as contiguous float32 CUDA tensors: a CUDA tensor whole, a host array in blocks of _ENCODE_CHUNK rows."""
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            yield _dev_f32(x, self.device)
+            return
+        for i in range(0, max(len(x), 1), _ENCODE_CHUNK):
+            yield _dev_f32(x[i:i + _ENCODE_CHUNK], self.device)
+
+    def _release(self, t, x):
+        """Wait for the kernels that read t when it is a temporary copy of x (a staged host array, a converted tensor)."""
+        if not (isinstance(x, torch.Tensor) and t.data_ptr() == x.data_ptr()):
+            torch.cuda.current_stream(self.device).synchronize()
+
+    def sa_encode_device(self, x, want_proj=False):
+        """(codes uint8 CUDA [n,code_size], proj float32 CUDA [n,nbits] or None): proj is the encoder's own float32 projection
+        <x, rrot[j]> (before the threshold) of the same launch that produced the codes.  No host synchronisation when x is a
+        contiguous float32 CUDA tensor on the index's device."""
+        x = self._rows(x, "sa_encode")
+        parts = []
+        for t in self._chunks(x):
+            parts.append(self._encode_device(t, want_proj))
+            self._release(t, x)
+        codes = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
+        proj = None if not want_proj else parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
+        return codes, proj
+
+    def sa_encode(self, x):
+        """The codes of x, numpy uint8 [n, code_size]."""
+        return self.sa_encode_device(x)[0].cpu().numpy()
+
+    def train(self, x):
+        """Nothing unless train_thresholds is set; then thresholds[j] = element n // 2 of the sorted projections of x on rrot[j]
+        (faiss's median rule), computed from the encoder's own float32 projections."""
+        if not self.train_thresholds:
+            return
+        if self.ntotal:
+            raise RuntimeError(f"train: the index holds {self.ntotal} rows encoded with the current thresholds")
+        x = self._rows(x, "train")
+        n = len(x)
+        if n < 1:
+            raise ValueError("train: no training rows")
+        parts = []
+        for t in self._chunks(x):
+            parts.append(self._encode_device(t, True, use_thresholds=False)[1])
+            self._release(t, x)
+        proj = parts[0] if len(parts) == 1 else torch.cat(parts)
+        self._thresholds = torch.sort(proj, dim=0).values[n // 2].contiguous().cpu().numpy()
+        self._thr_dev = None
+        self.is_trained = True
+
+    # -- FAISS surface ---------------------------------------------------------------------------
+    def add(self, x):
+        """Append rows: float32 [n,d], numpy or torch.  RuntimeError while untrained (train_thresholds without train())."""
+        if not self.is_trained:
+            raise RuntimeError("add: the index is not trained")
+        x = self._rows(x, "add")
+        for t in self._chunks(x):
+            if t.shape[0]:
+                self._index._add_device(self._encode_device(t)[0])
+
+    def search(self, x, k):
+        """(D, I) numpy arrays: D float32 Hamming distances ascending, I int64 rows; unused slots (2147483648.0, -1)."""
+        D, I = self.search_device(x, k)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    def search_device(self, x, k):
+        """search returning CUDA tensors."""
+        if not self.is_trained:
+            raise RuntimeError("search: the index is not trained")
+        k = int(k)
+        if k < 1 or k > _ffi.IVR_MAX_K:
+            raise ValueError(f"k={k} outside [1,{_ffi.IVR_MAX_K}]")
+        codes = self.sa_encode_device(x)[0]
+        D, I = self._index.search_device(codes, k)
+        return D.to(torch.float32), I
+
+    def reset(self):
+        """Drop the rows; rotation and thresholds stay."""
+        self._index.reset()
+
+    def close(self):
+        x = getattr(self, "_index", None)
+        if x is not None:
+            x.close()
