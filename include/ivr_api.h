@@ -439,6 +439,52 @@ int ivr_sign_encode(ivr_ctx *ctx, const float *x /*DEV [n][d]*/, int64_t n, int 
                     const float *thr /*DEV [nbits] or NULL*/, int nbits, uint8_t *codes /*DEV [n][code_size]*/,
                     float *proj /*DEV [n][nbits] or NULL*/, ivr_stream stream);
 
+/* ---- graph index (in the place of faiss IndexHNSWFlat) ------------------------------------------------------
+ * Stands in for faiss.IndexHNSWFlat(dimension, 32), the IndexHNSW type of _create_index (core.py:1213-1214).  It is NOT a port of
+ * faiss's HNSW: one layer of fixed out-degree (2 M, HNSW's level-0 width), built in bulk from exact kNN lists, entered through
+ * caller-chosen entry rows, inner product only ("graph index"; the definitions are the numpy functions of
+ * ivr_amd/graph.py).  Row numbers are int32 positions in [0, ntotal), -1 = none.  Every order is (score descending, row ascending):
+ * the (ordered score, ~row) key of ivr_index_search.  A score is accumulated in the summation order of ivr_index_search and so
+ * carries its bits for the same pair.
+ * The object keeps a ROW-MAJOR float32 copy of the rows, each padded with zeros to a multiple of 16 floats, so that four lanes read
+ * 64 contiguous bytes of a neighbour (the tiled layout of ivr_index spaces the quads of a row 256 bytes apart), and the int32
+ * neighbour table [ntotal][degree].  One stream at a time per handle. */
+typedef struct ivr_graph ivr_graph;
+#define IVR_GRAPH_MAX_EF 256        /* longest candidate list of a search (ef), and so the largest k */
+#define IVR_GRAPH_MAX_CAND 64       /* most candidates per row ivr_graph_prune takes (efConstruction) */
+#define IVR_GRAPH_MAX_DEGREE 64     /* largest out-degree, and most entry rows per query */
+int ivr_graph_max_ef(void);         /* the two limits as the library was built (core.py:1213-1214) */
+int ivr_graph_max_cand(void);
+/* core.py:1213-1214.  1 <= d <= 8192, 1 <= degree <= IVR_GRAPH_MAX_DEGREE */
+int ivr_graph_create(ivr_ctx *ctx, int d, int degree, ivr_graph **out);
+int ivr_graph_destroy(ivr_graph *g);                        /* core.py:1213-1214 */
+int ivr_graph_reset(ivr_graph *g);                          /* core.py:1213-1214: ntotal = 0, no neighbours */
+int64_t ivr_graph_ntotal(ivr_graph *g);                     /* core.py:1213-1214 */
+/* core.py:1213-1214.  Replace the stored rows by the n given ones (n < 2^31; n == 0 empties the object) and forget the neighbour
+ * table.  A call that grows the allocation synchronises the device. */
+int ivr_graph_set_rows(ivr_graph *g, const float *rows /*DEV [n,d] row-major*/, int64_t n, ivr_stream stream);
+/* core.py:1213-1214.  HNSW's neighbour-selection heuristic (faiss shrink_neighbor_list with distance -ip) on the stored rows, one
+ * workgroup per base row r: walk cand[r] in order, keep c iff <c, g> <= <r, c> for every g kept so far, stop at M kept; the rest of
+ * nbr[r] is -1 with score 0.  nbr_score[r][i] = <r, nbr[r][i]>.  Entries of cand outside [0, ntotal) are skipped.  The C x C Gram
+ * matrix of the candidates and the base scores run on the float32 MFMA.  1 <= C <= IVR_GRAPH_MAX_CAND, 1 <= M <= 64.  Enqueue-only. */
+int ivr_graph_prune(ivr_graph *g, const int32_t *cand /*DEV [n][C]*/, int C, int M, int32_t *nbr /*DEV [n][M]*/,
+                    float *nbr_score /*DEV [n][M]*/, ivr_stream stream);
+/* core.py:1213-1214.  Install the neighbour table (copied); n must equal ntotal.  Entries outside [0, ntotal) are never
+ * dereferenced by a search: it skips them. */
+int ivr_graph_set_neighbors(ivr_graph *g, const int32_t *graph /*DEV [n][degree]*/, int64_t n, ivr_stream stream);
+/* core.py:1213-1214.  Best-first walk of the graph, one workgroup per query (graph_search_ref of ivr_amd/graph.py):
+ *   L := the distinct valid rows of entries[q] with their scores, in order, cut to ef
+ *   at most max_expansions times: cur := the first row of L not yet expanded (none: stop); new := the distinct valid neighbours of
+ *   cur that are not in L, scored; L := the first ef of sort(L + new)
+ *   D / I := the first k of L; unused slots (-FLT_MAX, -1) as ivr_index_search leaves them; n_expanded[q] := rows expanded.
+ * 1 <= k <= ef <= IVR_GRAPH_MAX_EF, 1 <= ne <= IVR_GRAPH_MAX_DEGREE, 1 <= nq <= 2^22; max_expansions is clamped to [1, max(ntotal, 1)], so
+ * every loop of the kernel is bounded by it and by the degree.  normalize_q: the queries are L2-normalised first (into scratch).
+ * IVR_ERR_STATE while rows are stored without a neighbour table; an empty object returns unused slots only.  Scratch: nq d floats
+ * when normalize_q, else nothing.  Enqueue-only once that scratch has grown. */
+int ivr_graph_search(ivr_graph *g, const float *q /*DEV [nq,d]*/, int nq, int k, int ef, const int32_t *entries /*DEV [nq][ne]*/, int ne,
+                     int max_expansions, int normalize_q, float *D /*DEV [nq,k]*/, int64_t *I /*DEV [nq,k]*/,
+                     int32_t *n_expanded /*DEV [nq] or NULL*/, ivr_stream stream);
+
 /* Merge per-shard candidate lists (the reference's concat + sort of peer results, system.py:1744-1746):
  * D_parts/I_parts DEV [parts, nq, k] with global ids, parts ordered by ascending id range. */
 int ivr_topk_merge(ivr_ctx *ctx, const float *D_parts /*DEV*/, const int64_t *I_parts /*DEV*/, int parts,

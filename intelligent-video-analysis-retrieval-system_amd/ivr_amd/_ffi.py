@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IVR_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libivr_hip.so")
 
 IVR_MAX_K = 2048
+IVR_GRAPH_MAX_EF, IVR_GRAPH_MAX_CAND, IVR_GRAPH_MAX_DEGREE = 256, 64, 64       # include/ivr_api.h
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -109,6 +110,16 @@ _SIGS = {
     "ivr_bin_index_get_codes": (_i, [_p, _i64, _i64, _p, _p]),
     "ivr_bin_index_search": (_i, [_p, _p, _i, _i, _p, _p, _p]),
     "ivr_sign_encode": (_i, [_p, _p, _i64, _i, _p, _p, _i, _p, _p, _p]),
+    "ivr_graph_max_ef": (_i, []),
+    "ivr_graph_max_cand": (_i, []),
+    "ivr_graph_create": (_i, [_p, _i, _i, C.POINTER(_p)]),
+    "ivr_graph_destroy": (_i, [_p]),
+    "ivr_graph_reset": (_i, [_p]),
+    "ivr_graph_ntotal": (_i64, [_p]),
+    "ivr_graph_set_rows": (_i, [_p, _p, _i64, _p]),
+    "ivr_graph_prune": (_i, [_p, _p, _i, _i, _p, _p, _p]),
+    "ivr_graph_set_neighbors": (_i, [_p, _p, _i64, _p]),
+    "ivr_graph_search": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
     "ivr_topk_merge": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_topk_pack": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "ivr_topk_merge_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
