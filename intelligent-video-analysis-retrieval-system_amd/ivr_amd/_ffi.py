@@ -6,6 +6,7 @@ reference raises at the same places (IVR_ERR_INVALID -> ValueError as in
 core.py:1178-1191, everything else -> RuntimeError as in core.py:894-896).
 """
 import ctypes as C
+import operator
 import os
 import threading
 
@@ -131,6 +132,21 @@ _SIGS = {
     "ivr_frame_quality": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 EXPORTS = tuple(_SIGS)
+# the exports that return a value; every other one returns a status that call() hands to check()
+_VALUE = frozenset(("ivr_api_version", "ivr_last_error", "ivr_preprocess_scratch_bytes", "ivr_tower_workspace_bytes", "ivr_index_ntotal",
+                    "ivr_index_dim", "ivr_index_capacity", "ivr_index_has_ids", "ivr_bin_index_ntotal", "ivr_bin_index_block_rows",
+                    "ivr_graph_max_ef", "ivr_graph_max_cand", "ivr_graph_ntotal", "ivr_frame_quality_scratch_bytes"))
+# the slot of the ivr_stream argument (the last one wherever there is one): call() fills it when the caller leaves it out
+_STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
+    "ivr_release_stream_scratch", "ivr_preprocess", "ivr_tower_encode_image", "ivr_tower_encode_text", "ivr_tower_debug_hidden",
+    "ivr_linear", "ivr_attention", "ivr_qkv_attention", "ivr_layernorm", "ivr_linear_fp8", "ivr_gemm", "ivr_l2_normalize",
+    "ivr_index_add", "ivr_index_write", "ivr_index_write_ring", "ivr_index_reconstruct", "ivr_index_search", "ivr_index_range_search",
+    "ivr_index_search_filtered", "ivr_index_range_search_filtered", "ivr_index_remove_ids", "ivr_index_add_with_ids",
+    "ivr_index_get_ids", "ivr_index_find_ids", "ivr_index_gather", "ivr_index_scatter", "ivr_index_search_reconstruct",
+    "ivr_index_search_lists", "ivr_segment_mean", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
+    "ivr_sign_encode", "ivr_graph_set_rows", "ivr_graph_prune", "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
+    "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
+    "ivr_scene_keep_mask_window", "ivr_frame_quality")}
 
 _lib = None
 _lock = threading.Lock()
@@ -205,6 +221,101 @@ def stream_ptr(stream=None):
 
 def f3(v):
     return (_f * 3)(*[float(x) for x in v])
+
+
+CTX = object()      # in an ivr_ctx* slot of call(): the context of `device`, made (on first use) with that device current
+
+
+def _plan(argtypes):
+    """The slots of one export by how call() treats them: addresses (c_void_p), integers, floats, and (slot, T) for POINTER(T).
+    What is left (char*, and a POINTER slot given anything but a T) goes to ctypes as it is."""
+    at = lambda *ts: tuple(i for i, t in enumerate(argtypes) if t in ts)     # noqa: E731
+    refs = tuple((i, t._type_) for i, t in enumerate(argtypes) if isinstance(getattr(t, "_type_", None), type))
+    return len(argtypes), at(_p), at(_i, _i64), at(_f), refs
+
+
+_PLANS = {n: _plan(sig[1]) for n, sig in _SIGS.items()}
+
+
+def _call(name, args, device, what):
+    n, ptrs, ints, floats, refs = _PLANS[name]
+    slot = _STREAM.get(name)
+    if len(args) == n - 1 and slot is not None:
+        args = args[:slot] + (stream_ptr(),) + args[slot:]
+    elif len(args) != n:
+        raise TypeError(f"{name} takes {n} arguments{' (the stream may be left out)' if slot is not None else ''}, got {len(args)}")
+    out = list(args)
+    for i in ptrs:
+        a = out[i]
+        ptr = getattr(a, "data_ptr", None)
+        if ptr is not None:
+            out[i] = ptr()
+        elif a is CTX and device is not None:
+            out[i] = context(device if isinstance(device, int) else device.index)
+        elif not (a is None or isinstance(a, (int, C.c_void_p, C.Array))):
+            raise TypeError(f"{name}: argument {i} takes a tensor, None, an address or a c_void_p, got {type(a).__name__}")
+    for i in ints:
+        if not isinstance(out[i], int):                 # bool included; anything else must be an integer type (numpy.int64), as for ctypes
+            try:
+                out[i] = operator.index(out[i])
+            except TypeError:
+                raise TypeError(f"{name}: argument {i} takes an int, got {type(out[i]).__name__}") from None
+    for i in floats:
+        if not isinstance(out[i], float):
+            raise TypeError(f"{name}: argument {i} takes a float, got {type(out[i]).__name__}")
+    for i, T in refs:
+        if isinstance(out[i], T):
+            out[i] = C.byref(out[i])
+    rc = getattr(_lib or load(), name)(*out)
+    if name in _VALUE:
+        return rc
+    check(rc, what or name)
+
+
+def call(name, *args, device=None, what=None):
+    """The one way the package calls the library: lib.<name>(*args), marshalled from _SIGS[name].
+      c_void_p slot      a torch tensor (its data_ptr()), None, an address, a c_void_p, or CTX (the ivr_ctx of `device`)
+      int / float slot   an int, a bool or a numpy integer / a float
+      POINTER(T) slot    a T (passed by reference), or whatever ctypes takes there (None, an array)
+    device: the call runs under torch.cuda.device(device).  A stream slot the caller leaves out is filled with the current stream
+    (of `device` when given).  A status goes through check(rc, what or name); the value exports (_VALUE) return their value."""
+    if device is None:
+        return _call(name, args, None, what)
+    import torch
+    with torch.cuda.device(device):
+        return _call(name, args, device, what)
+
+
+class Handle:
+    """Base of the objects that own one library handle (an index, a tower): _lib, _h, device, close() / __del__, and _call, which
+    supplies the handle, the device and the stream.  A subclass names its destroy export and opens the handle with _open."""
+    _DESTROY = None
+    _h = None
+
+    def _open(self, create, device, *args):
+        """self._h = the handle that `create`(ctx, *args, &handle) makes on `device` (None: the current device)."""
+        import torch
+        self._lib = load()
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+        h = _p()
+        call(create, CTX, *args, h, device=self.device)
+        self._h = h
+
+    def _call(self, name, *args, what=None):
+        import torch
+        with torch.cuda.device(self.device):
+            return _call(name, (self._h,) + args, self.device, what)
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            getattr(self._lib, self._DESTROY)(h)        # the status of a destroy is dropped
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def profile_enable(on=True, device=0):

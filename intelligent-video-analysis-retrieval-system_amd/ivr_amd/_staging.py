@@ -1,0 +1,114 @@
+"""Staging and checking of what callers hand to an index: rows, queries, k, integer tables.
+
+Host arrays are staged through torch tensors on the index's device; a tensor that is already there, contiguous and of the right
+dtype is used in place.  A staged copy is a temporary that must outlive the kernels reading it: whoever stages asks is_staged and
+ends with sync_if_staged.  Every check raises the ValueError text the index classes share.
+"""
+import numpy as np
+import torch
+
+
+# -- staging -------------------------------------------------------------------------------------------------------------------
+def dev_f32(x, device):
+    """numpy / torch -> contiguous float32 tensor on `device` (a view when already there)."""
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    if not isinstance(x, torch.Tensor):
+        raise ValueError("expected a numpy array or a torch tensor")
+    return x.to(device=device, dtype=torch.float32, non_blocking=False).contiguous()
+
+
+def dev_u8(x, width, device, what):
+    """numpy / torch uint8 [n, width] (or one code [width]) -> contiguous uint8 tensor on `device` (a view when already there)."""
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.uint8:
+            raise ValueError(f"{what}: codes must be uint8, got {x.dtype}")
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise ValueError(f"{what}: codes must be a uint8 numpy array or torch tensor")
+    if x.dim() == 1 and width and x.shape[0] == width:
+        x = x.reshape(1, -1)
+    if x.dim() != 2 or x.shape[1] != width:
+        raise ValueError(f"{what} expects uint8 [n,{width}], got {tuple(x.shape)}")
+    return x.to(device=device).contiguous()
+
+
+def as_rows(x, tensors_too=True):
+    """The 1-D -> [1,d] rule of the query arguments: anything but a tensor goes through numpy.asarray, and a single vector becomes
+    one row (a 1-D tensor only with tensors_too)."""
+    q = x if isinstance(x, torch.Tensor) else np.asarray(x)
+    if q.ndim == 1 and (tensors_too or isinstance(q, np.ndarray)):
+        q = q.reshape(1, -1)
+    return q
+
+
+def is_staged(t, x):
+    """Whether the device tensor t is a temporary copy of the caller's x (a host array, a converted or compacted tensor) and not
+    x's own storage."""
+    return not (isinstance(x, torch.Tensor) and t.data_ptr() == x.data_ptr())
+
+
+def sync_if_staged(staged, device=None):
+    """The staging copy must outlive the kernels: wait for the current stream (of `device`) when there was a copy."""
+    if staged:
+        torch.cuda.current_stream(device).synchronize()
+
+
+def queries_f32(x, d, device):
+    """Queries [nq,d] -> (contiguous float32 tensor on `device`, is_staged)."""
+    t = dev_f32(x, device)
+    if t.dim() != 2 or t.shape[1] != d:
+        raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({d})")
+    return t, is_staged(t, x)
+
+
+# -- checks --------------------------------------------------------------------------------------------------------------------
+def check_rows(x, d, what):
+    """x must be a numpy array or torch tensor [n,d]."""
+    if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != d:
+        raise ValueError(f"{what} expects [n,{d}], got {tuple(getattr(x, 'shape', ()))}")
+
+
+def check_k(k, kmax):
+    k = int(k)
+    if k < 1 or k > kmax:
+        raise ValueError(f"k={k} outside [1,{kmax}]")
+    return k
+
+
+def check_nq(nq, what="search"):
+    if nq < 1:
+        raise ValueError(f"{what}: no queries")
+
+
+def alloc_DI(nq, k, device, dtype=torch.float32):
+    """The (D, I) pair of a search: D `dtype` [nq,k], I int64 [nq,k]."""
+    return torch.empty((nq, k), dtype=dtype, device=device), torch.empty((nq, k), dtype=torch.int64, device=device)
+
+
+# -- caller-supplied integer tables ----------------------------------------------------------------------------------------------
+def int_tensor(a, name, verb="be", np_dtype=None):
+    """An integer numpy array or torch tensor -> torch tensor (where it lives; a numpy array as np_dtype when that is given).
+    name: "who: the table"."""
+    if isinstance(a, np.ndarray):
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must {verb} integers, got {a.dtype}")
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype))
+    if not isinstance(a, torch.Tensor) or a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool:
+        raise ValueError(f"{name} must be an integer numpy array or torch tensor")
+    return a
+
+
+def check_entries(t, n, name):
+    """Every entry of the device tensor t must lie in [-1, n): checked on the tensor (one host sync) before anything is launched."""
+    if bool(((t >= n) | (t < -1)).any().item()):
+        raise ValueError(f"{name} must lie in [-1, {n})")
+
+
+def entry_table(entries, nq, max_cols, what):
+    """The entries of a graph walk: integers [nq, 1..max_cols] -> numpy int32, clipped to [-1, 2^31) (rows outside the index are
+    skipped by the walk itself)."""
+    e = np.asarray(entries)
+    if not np.issubdtype(e.dtype, np.integer) or e.ndim != 2 or e.shape[0] != nq or not 1 <= e.shape[1] <= max_cols:
+        raise ValueError(f"{what}: entries must be integers [{nq},1..{max_cols}]")
+    return np.ascontiguousarray(e.clip(-1, 2**31 - 1), dtype=np.int32)

@@ -1,7 +1,5 @@
 """Attention and LayerNorm of the towers as building blocks (ivr_attention, ivr_qkv_attention, ivr_layernorm): parity tests and
 kernel benchmarks."""
-import ctypes as C
-
 import torch
 
 from . import _ffi
@@ -9,14 +7,9 @@ from . import _ffi
 OUT_BF16, OUT_F32, OUT_FP8 = 0, 1, 2
 
 
-def _ptr(a):
-    return C.c_void_p(a.data_ptr()) if a is not None else None
-
-
 def attention(qkv, T, heads, causal=False, out_fp8=False):
     """qkv [n*T, 3D] CUDA tensor, bf16 or float32 (row = q | k | v, head h at columns h*64 .. h*64+63 of each part) ->
     att [n*T, D]: bf16 or float8_e4m3fn (out_fp8) for bf16 input, float32 for float32 input.  No 1/sqrt(64) scale."""
-    lib = _ffi.load()
     if qkv.dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("qkv must be bf16 or float32")
     if qkv.dim() != 2 or qkv.shape[1] % 3 or T < 1 or qkv.shape[0] % T:
@@ -28,16 +21,13 @@ def attention(qkv, T, heads, causal=False, out_fp8=False):
     rows, D = qkv.shape[0], qkv.shape[1] // 3
     odt = torch.float32 if f32 else torch.uint8 if out_fp8 else torch.bfloat16
     att = torch.empty((rows, D), dtype=odt, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _ffi.check(lib.ivr_attention(_ffi.context(qkv.device.index), int(f32), _ptr(qkv), rows // T, int(T), D, int(heads),
-                                     int(bool(causal)), int(bool(out_fp8)), _ptr(att), _ffi.stream_ptr()), "ivr_attention")
+    _ffi.call("ivr_attention", _ffi.CTX, f32, qkv, rows // T, int(T), D, int(heads), bool(causal), bool(out_fp8), att, device=qkv.device)
     return att.view(torch.float8_e4m3fn) if out_fp8 else att
 
 
 def qkv_attention(xn, w, bias, T, heads, out_fp8=False):
     """Fused projection + attention: xn bf16 [n*T, D], w bf16 [3D, D], bias float32 [3D] -> attention of (xn w^T + bias rounded
     to bf16), not causal; bf16 or float8_e4m3fn [n*T, D]."""
-    lib = _ffi.load()
     if xn.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or bias.dtype != torch.float32:
         raise ValueError("xn and w must be bf16, bias float32")
     if xn.dim() != 2 or T < 1 or xn.shape[0] % T:
@@ -47,9 +37,7 @@ def qkv_attention(xn, w, bias, T, heads, out_fp8=False):
         raise ValueError(f"w must be [3D, D] and bias [3D] for D={D}")
     xn, w, bias = xn.contiguous(), w.contiguous(), bias.contiguous()
     att = torch.empty((rows, D), dtype=torch.uint8 if out_fp8 else torch.bfloat16, device=xn.device)
-    with torch.cuda.device(xn.device):
-        _ffi.check(lib.ivr_qkv_attention(_ffi.context(xn.device.index), _ptr(xn), _ptr(w), _ptr(bias), rows // T, int(T), D,
-                                         int(heads), int(bool(out_fp8)), _ptr(att), _ffi.stream_ptr()), "ivr_qkv_attention")
+    _ffi.call("ivr_qkv_attention", _ffi.CTX, xn, w, bias, rows // T, int(T), D, int(heads), bool(out_fp8), att, device=xn.device)
     return att.view(torch.float8_e4m3fn) if out_fp8 else att
 
 
@@ -57,7 +45,6 @@ def layernorm(x, g, b, eps, out_kind, row_mul=1, offs=None, reverse=False):
     """out row r = LN(x row r*row_mul + offs[r]) with x float32 [R, D], g / b float32 [D], offs int32 [rows] or None;
     out_kind OUT_BF16 / OUT_F32 / OUT_FP8 -> bf16 / float32 / float8_e4m3fn [rows, D].  rows = len(offs), or without offsets
     ceil(R / row_mul) (every row_mul-th row); every source row must lie inside x."""
-    lib = _ffi.load()
     if x.dtype != torch.float32 or g.dtype != torch.float32 or b.dtype != torch.float32:
         raise ValueError("x, g and b must be float32")
     if x.dim() != 2 or tuple(g.shape) != (x.shape[1],) or tuple(b.shape) != (x.shape[1],):
@@ -78,8 +65,6 @@ def layernorm(x, g, b, eps, out_kind, row_mul=1, offs=None, reverse=False):
             raise ValueError("a gathered source row lies outside x")
     odt = {OUT_BF16: torch.bfloat16, OUT_F32: torch.float32, OUT_FP8: torch.uint8}[out_kind]
     out = torch.empty((rows, D), dtype=odt, device=x.device)
-    with torch.cuda.device(x.device):
-        _ffi.check(lib.ivr_layernorm(_ffi.context(x.device.index), int(out_kind), _ptr(x), int(row_mul), _ptr(offs), _ptr(g), _ptr(b),
-                                     float(eps), int(rows), int(D), int(bool(reverse)), _ptr(out), _ffi.stream_ptr()),
-                   "ivr_layernorm")
+    _ffi.call("ivr_layernorm", _ffi.CTX, int(out_kind), x, int(row_mul), offs, g, b, float(eps), int(rows), int(D), bool(reverse), out,
+              device=x.device)
     return out.view(torch.float8_e4m3fn) if out_kind == OUT_FP8 else out

@@ -13,15 +13,13 @@ numpy.packbits(bits, axis=1, bitorder="little").
 faiss's own random stream cannot be reproduced here, so the default rotation is defined by `lsh_rotation` (numpy, seeded); a matrix
 exported from a real faiss index can be assigned to `IndexLSH.rrot` while the index is empty and then reproduces that index's codes.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _ffi
-from .index import _dev_f32
+from . import _ffi, _staging
+from ._faiss import METRIC_L2, search_numpy
+from ._staging import dev_f32 as _dev_f32, dev_u8 as _dev_u8
 
-METRIC_L2 = 1                 # faiss.METRIC_L2: what faiss.IndexLSH reports as its metric_type
 _ENCODE_CHUNK = 1 << 18       # rows of a host array staged per encoder launch
 
 
@@ -39,42 +37,23 @@ def lsh_rotation(d, nbits, seed=5):
     return np.ascontiguousarray(q[:nbits, :d], dtype=np.float32)
 
 
-def _dev_u8(x, width, device, what):
-    """numpy / torch uint8 [n, width] -> contiguous uint8 CUDA tensor on `device` (a view when already there)."""
-    if isinstance(x, np.ndarray):
-        if x.dtype != np.uint8:
-            raise ValueError(f"{what}: codes must be uint8, got {x.dtype}")
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
-        raise ValueError(f"{what}: codes must be a uint8 numpy array or torch tensor")
-    if x.dim() == 1 and width and x.shape[0] == width:
-        x = x.reshape(1, -1)
-    if x.dim() != 2 or x.shape[1] != width:
-        raise ValueError(f"{what} expects uint8 [n,{width}], got {tuple(x.shape)}")
-    return x.to(device=device).contiguous()
-
-
-class BinaryFlatIndex:
+class BinaryFlatIndex(_ffi.Handle):
     """Exact Hamming-distance index over binary codes (FAISS IndexBinaryFlat contract) on one GPU.  d_bits is the code length in
     bits and must be a multiple of 8, as in faiss; a code is d_bits / 8 bytes."""
+    _DESTROY = "ivr_bin_index_destroy"
 
     def __init__(self, d_bits, device=None):
         d_bits = int(d_bits)
         if d_bits < 8 or d_bits % 8 != 0:
             raise ValueError(f"BinaryFlatIndex: d={d_bits} must be a positive multiple of 8")
-        self._lib = _ffi.load()
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         self.d = d_bits
         self.code_size = d_bits // 8
         self.is_trained = True
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_bin_index_create(_ffi.context(self.device.index), self.d, 0, C.byref(h)), "ivr_bin_index_create")
-        self._h = h
+        self._open("ivr_bin_index_create", device, self.d, 0)
 
     @property
     def ntotal(self):
-        return int(self._lib.ivr_bin_index_ntotal(self._h))
+        return int(_ffi.call("ivr_bin_index_ntotal", self._h))
 
     def train(self, x):
         return None
@@ -84,33 +63,23 @@ class BinaryFlatIndex:
         self._add_device(_dev_u8(codes, self.code_size, self.device, "add"))
 
     def _add_device(self, t):
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_bin_index_add(self._h, C.c_void_p(t.data_ptr()), t.shape[0], _ffi.stream_ptr()), "ivr_bin_index_add")
-            torch.cuda.current_stream().synchronize()  # `t` may be a temporary staging copy
+        self._call("ivr_bin_index_add", t, t.shape[0])
+        torch.cuda.current_stream(self.device).synchronize()  # `t` may be a temporary staging copy
 
     def search(self, codes, k):
         """(D, I) numpy arrays: D int32 [nq,k] Hamming distances ascending, I int64 row numbers; equal distances rank the lower row
         first; unused slots (2147483647, -1)."""
-        D, I = self.search_device(codes, k)
-        return D.cpu().numpy(), I.cpu().numpy()
+        return search_numpy(self, codes, k)
 
     def search_device(self, codes, k):
         """search returning CUDA tensors; no host synchronisation unless `codes` had to be staged."""
         t = _dev_u8(codes, self.code_size, self.device, "search")
-        k = int(k)
-        if k < 1 or k > _ffi.IVR_MAX_K:
-            raise ValueError(f"k={k} outside [1,{_ffi.IVR_MAX_K}]")
+        k = _staging.check_k(k, _ffi.IVR_MAX_K)
         nq = t.shape[0]
-        if nq < 1:
-            raise ValueError("search: no queries")
-        staged = t.data_ptr() != (codes.data_ptr() if isinstance(codes, torch.Tensor) else 0)
-        D = torch.empty((nq, k), dtype=torch.int32, device=self.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_bin_index_search(self._h, C.c_void_p(t.data_ptr()), nq, k, C.c_void_p(D.data_ptr()),
-                                                      C.c_void_p(I.data_ptr()), _ffi.stream_ptr()), "ivr_bin_index_search")
-            if staged:
-                torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
+        _staging.check_nq(nq)
+        D, I = _staging.alloc_DI(nq, k, self.device, torch.int32)
+        self._call("ivr_bin_index_search", t, nq, k, D, I)
+        _staging.sync_if_staged(_staging.is_staged(t, codes), self.device)
         return D, I
 
     def reconstruct_n(self, start=0, n=None):
@@ -124,24 +93,11 @@ class BinaryFlatIndex:
             raise ValueError(f"reconstruct_n: rows [{start},{start + n}) outside [0,{self.ntotal})")
         out = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device)
         if n:
-            with torch.cuda.device(self.device):
-                _ffi.check(self._lib.ivr_bin_index_get_codes(self._h, start, n, C.c_void_p(out.data_ptr()), _ffi.stream_ptr()),
-                           "ivr_bin_index_get_codes")
+            self._call("ivr_bin_index_get_codes", start, n, out)
         return out
 
     def reset(self):
-        _ffi.check(self._lib.ivr_bin_index_reset(self._h), "ivr_bin_index_reset")
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.ivr_bin_index_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("ivr_bin_index_reset")
 
 
 def IndexBinaryFlat(d):
@@ -219,8 +175,7 @@ class IndexLSH:
     def _rows(self, x, what):
         if isinstance(x, np.ndarray) and x.ndim == 1:
             x = x.reshape(1, -1)
-        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"{what} expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        _staging.check_rows(x, self.d, what)
         return x
 
     def _encode_device(self, t, want_proj=False, use_thresholds=True):
@@ -228,19 +183,16 @@ class IndexLSH:
         n = t.shape[0]
         codes = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device)
         proj = torch.empty((n, self.nbits), dtype=torch.float32, device=self.device) if want_proj else None
-        with torch.cuda.device(self.device):
-            rot = thr = None
-            if self.rotate_data:
-                if self._rot_dev is None:
-                    self._rot_dev = torch.from_numpy(self._rrot).to(self.device)
-                rot = C.c_void_p(self._rot_dev.data_ptr())
-            if self.train_thresholds and use_thresholds:
-                if self._thr_dev is None:
-                    self._thr_dev = torch.from_numpy(self._thresholds).to(self.device)
-                thr = C.c_void_p(self._thr_dev.data_ptr())
-            _ffi.check(self._lib.ivr_sign_encode(_ffi.context(self.device.index), C.c_void_p(t.data_ptr()), n, self.d, rot, thr, self.nbits,
-                                                 C.c_void_p(codes.data_ptr()), C.c_void_p(proj.data_ptr()) if want_proj else None,
-                                                 _ffi.stream_ptr()), "ivr_sign_encode")
+        rot = thr = None
+        if self.rotate_data:
+            if self._rot_dev is None:
+                self._rot_dev = torch.from_numpy(self._rrot).to(self.device)
+            rot = self._rot_dev
+        if self.train_thresholds and use_thresholds:
+            if self._thr_dev is None:
+                self._thr_dev = torch.from_numpy(self._thresholds).to(self.device)
+            thr = self._thr_dev
+        _ffi.call("ivr_sign_encode", _ffi.CTX, t, n, self.d, rot, thr, self.nbits, codes, proj, device=self.device)
         return codes, proj
 
     def _chunks(self, x):
@@ -251,11 +203,6 @@ class IndexLSH:
         for i in range(0, max(len(x), 1), _ENCODE_CHUNK):
             yield _dev_f32(x[i:i + _ENCODE_CHUNK], self.device)
 
-    def _release(self, t, x):
-        """Wait for the kernels that read t when it is a temporary copy of x (a staged host array, a converted tensor)."""
-        if not (isinstance(x, torch.Tensor) and t.data_ptr() == x.data_ptr()):
-            torch.cuda.current_stream(self.device).synchronize()
-
     def sa_encode_device(self, x, want_proj=False):
         """(codes uint8 CUDA [n,code_size], proj float32 CUDA [n,nbits] or None): proj is the encoder's own float32 projection
         <x, rrot[j]> (before the threshold) of the same launch that produced the codes.  No host synchronisation when x is a
@@ -264,7 +211,7 @@ class IndexLSH:
         parts = []
         for t in self._chunks(x):
             parts.append(self._encode_device(t, want_proj))
-            self._release(t, x)
+            _staging.sync_if_staged(_staging.is_staged(t, x), self.device)
         codes = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
         proj = None if not want_proj else parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
         return codes, proj
@@ -287,7 +234,7 @@ class IndexLSH:
         parts = []
         for t in self._chunks(x):
             parts.append(self._encode_device(t, True, use_thresholds=False)[1])
-            self._release(t, x)
+            _staging.sync_if_staged(_staging.is_staged(t, x), self.device)
         proj = parts[0] if len(parts) == 1 else torch.cat(parts)
         self._thresholds = torch.sort(proj, dim=0).values[n // 2].contiguous().cpu().numpy()
         self._thr_dev = None
@@ -305,16 +252,13 @@ class IndexLSH:
 
     def search(self, x, k):
         """(D, I) numpy arrays: D float32 Hamming distances ascending, I int64 rows; unused slots (2147483648.0, -1)."""
-        D, I = self.search_device(x, k)
-        return D.cpu().numpy(), I.cpu().numpy()
+        return search_numpy(self, x, k)
 
     def search_device(self, x, k):
         """search returning CUDA tensors."""
         if not self.is_trained:
             raise RuntimeError("search: the index is not trained")
-        k = int(k)
-        if k < 1 or k > _ffi.IVR_MAX_K:
-            raise ValueError(f"k={k} outside [1,{_ffi.IVR_MAX_K}]")
+        k = _staging.check_k(k, _ffi.IVR_MAX_K)
         codes = self.sa_encode_device(x)[0]
         D, I = self._index.search_device(codes, k)
         return D.to(torch.float32), I

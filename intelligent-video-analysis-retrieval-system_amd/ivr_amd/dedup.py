@@ -1,6 +1,4 @@
 """Device-side near-duplicate filter: the keep/drop rule of video_frame_filter.py:63-70."""
-import ctypes as C
-
 import torch
 
 from . import _ffi
@@ -25,9 +23,5 @@ class DedupState:
             raise ValueError(f"emb must be a float32 CUDA tensor [n,{self.d}]")
         emb = emb.contiguous()
         keep = torch.empty(emb.shape[0], dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_dedup_keep_mask(_ffi.context(self.device.index), C.c_void_p(emb.data_ptr()),
-                                                     emb.shape[0], self.d, float(threshold),
-                                                     C.c_void_p(self.state.data_ptr()), C.c_void_p(keep.data_ptr()),
-                                                     _ffi.stream_ptr()), "ivr_dedup_keep_mask")
+        _ffi.call("ivr_dedup_keep_mask", _ffi.CTX, emb, emb.shape[0], self.d, float(threshold), self.state, keep, device=self.device)
         return keep

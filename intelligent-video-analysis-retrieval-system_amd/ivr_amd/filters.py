@@ -11,8 +11,6 @@
 The cosines come from the HIP kernels (ivr_rowwise_cosine, the flat index self-search); the list bookkeeping is the
 reference's, kept on the host.  Blur / edge-density gating (filter.py:63-92): ivr_amd/quality.py.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -32,10 +30,7 @@ def rowwise_cosine(a, b):
     if a.shape != b.shape or a.dim() != 2:
         raise ValueError("rowwise_cosine expects two [n,d] arrays of the same shape")
     out = torch.empty(a.shape[0], dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        _ffi.check(_ffi.load().ivr_rowwise_cosine(_ffi.context(a.device.index), C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                                  a.shape[0], a.shape[1], C.c_void_p(out.data_ptr()), _ffi.stream_ptr()),
-                   "ivr_rowwise_cosine")
+    _ffi.call("ivr_rowwise_cosine", _ffi.CTX, a, b, a.shape[0], a.shape[1], out, device=a.device)
     return out
 
 
@@ -75,9 +70,7 @@ def filter_similar_frames_in_scene(scene_embeddings, scene_indices, config):
     thr, min_dist = float(config["similarity_threshold"]), max(1, int(config["min_frame_distance"]))
     e = _dev(np.asarray(scene_embeddings) if not isinstance(scene_embeddings, torch.Tensor) else scene_embeddings)
     keep = torch.empty(n, dtype=torch.uint8, device=e.device)
-    with torch.cuda.device(e.device):
-        _ffi.check(_ffi.load().ivr_scene_keep_mask(_ffi.context(e.device.index), C.c_void_p(e.data_ptr()), n, e.shape[1], thr, min_dist,
-                                                   C.c_void_p(keep.data_ptr()), _ffi.stream_ptr()), "ivr_scene_keep_mask")
+    _ffi.call("ivr_scene_keep_mask", _ffi.CTX, e, n, e.shape[1], thr, min_dist, keep, device=e.device)
     kept = np.nonzero(keep.cpu().numpy())[0].tolist()
     if kept[-1] != n - 1:
         kept.append(n - 1)
@@ -94,9 +87,7 @@ def filter_similar_frames_advanced(scene_embeddings, scene_indices, config):
     thr, window = float(config["similarity_threshold"]), max(1, int(config["similarity_window_size"]))
     e = _dev(np.asarray(scene_embeddings) if not isinstance(scene_embeddings, torch.Tensor) else scene_embeddings)
     keep = torch.empty(n, dtype=torch.uint8, device=e.device)
-    with torch.cuda.device(e.device):
-        _ffi.check(_ffi.load().ivr_scene_keep_mask_window(_ffi.context(e.device.index), C.c_void_p(e.data_ptr()), n, e.shape[1], thr, window,
-                                                          C.c_void_p(keep.data_ptr()), _ffi.stream_ptr()), "ivr_scene_keep_mask_window")
+    _ffi.call("ivr_scene_keep_mask_window", _ffi.CTX, e, n, e.shape[1], thr, window, keep, device=e.device)
     return [scene_indices[j] for j in np.nonzero(keep.cpu().numpy())[0].tolist()]
 
 

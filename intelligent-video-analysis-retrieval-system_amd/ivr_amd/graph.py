@@ -16,15 +16,14 @@ Scores are inner products only, and each carries the bits FlatIPIndex.search giv
 faiss's own default metric for IndexHNSWFlat is L2; on the unit-norm rows the reference stores the ranking is the same and D is the
 inner product.
 """
-import ctypes as C
 import time
 
 import numpy as np
 import torch
 
-from . import _ffi
-from .index import FlatIPIndex, _dev_f32, normalize_L2
-from .ivf import METRIC_INNER_PRODUCT
+from . import _ffi, _staging
+from ._faiss import METRIC_INNER_PRODUCT, search_numpy, to_numpy, typed_params
+from .index import FlatIPIndex, normalize_L2
 
 _KNN_BLOCK = 1 << 16          # rows per kNN search of the build: bounds the query workspace of the storage
 _FLT_MAX = np.finfo(np.float32).max
@@ -235,30 +234,26 @@ class SearchParametersHNSW:
         self.sel = sel
 
 
-class GraphFlatIndex:
+class GraphFlatIndex(_ffi.Handle):
     """Single-layer graph index with exact float32 inner-product scores on one GPU, in the place of faiss IndexHNSWFlat (see the
     module docstring: not a port, parity-unpinned against faiss; the contract is graph_build_ref / graph_search_ref).
 
     search(x, k) returns (D, I) under the contract of FlatIPIndex.search: float32 descending, int64 row numbers, -1 padding.  Rows
     are labelled by position.  Every add() call rebuilds the graph over ALL stored rows (kNN lists, prune, link): add in large
     batches."""
+    _DESTROY = "ivr_graph_destroy"
 
     def __init__(self, d, M=32, device=None):
         self.d, self.M = int(d), int(M)
         if self.d < 1 or not 1 <= 2 * self.M <= _ffi.IVR_GRAPH_MAX_DEGREE:
             raise ValueError(f"GraphFlatIndex: d={d} M={M} (2 M at most {_ffi.IVR_GRAPH_MAX_DEGREE})")
-        self._lib = _ffi.load()
         self._storage = FlatIPIndex(self.d, device=device)
-        self.device = self._storage.device
-        self._entry = FlatIPIndex(self.d, device=self.device.index)
+        self._entry = FlatIPIndex(self.d, device=self._storage.device.index)
         self.metric_type = METRIC_INNER_PRODUCT
         self.is_trained = True
         self.hnsw = _HNSWKnobs()
         self.build_times = {}         # seconds of the last add(): knn / prune / link
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_graph_create(_ffi.context(self.device.index), self.d, 2 * self.M, C.byref(h)), "ivr_graph_create")
-        self._h = h
+        self._open("ivr_graph_create", self._storage.device.index, self.d, 2 * self.M)
         self._graph = torch.zeros((0, 2 * self.M), dtype=torch.int32, device=self.device)
 
     @property
@@ -270,8 +265,7 @@ class GraphFlatIndex:
         """Append rows labelled ntotal, ntotal + 1, ... and rebuild the graph over all stored rows.  graph: the neighbour table an
         earlier build made over the same rows (graph(), e.g. saved with numpy.save); it is installed through set_graph, with its
         checks, in place of the kNN / prune / link steps."""
-        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"add expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        _staging.check_rows(x, self.d, "add")
         if len(x) == 0:
             return
         if graph is not None:
@@ -292,14 +286,13 @@ class GraphFlatIndex:
         Cn = min(self.hnsw.efConstruction, n - 1)
         self.build_times = {}
         with torch.cuda.device(self.device):
-            sp = _ffi.stream_ptr()
             allrows = torch.arange(n, dtype=torch.int64, device=self.device)
             torch.cuda.current_stream().synchronize()
             t0 = time.perf_counter()
             # the graph's own row-major copy; the gathered rows are dropped again before the kNN lists are made
             rows = torch.cat([st.gather_device(allrows[i:i + _KNN_BLOCK]) for i in range(0, n, _KNN_BLOCK)]) if n > _KNN_BLOCK \
                 else st.gather_device(allrows)
-            _ffi.check(self._lib.ivr_graph_set_rows(self._h, C.c_void_p(rows.data_ptr()), n, sp), "ivr_graph_set_rows")
+            self._call("ivr_graph_set_rows", rows, n)
             del rows                                     # same stream: the block is not reused before the copy has run
             if graph is not None:
                 self._install(graph)
@@ -316,8 +309,7 @@ class GraphFlatIndex:
                 t0 = self._timed("knn", t0)
                 nbr = torch.empty((n, M), dtype=torch.int32, device=self.device)
                 nsc = torch.empty((n, M), dtype=torch.float32, device=self.device)
-                _ffi.check(self._lib.ivr_graph_prune(self._h, C.c_void_p(cand.data_ptr()), Cn, M, C.c_void_p(nbr.data_ptr()),
-                                                     C.c_void_p(nsc.data_ptr()), sp), "ivr_graph_prune")
+                self._call("ivr_graph_prune", cand, Cn, M, nbr, nsc)
                 t0 = self._timed("prune", t0)
                 self._install(link_device(nbr, nsc, 2 * M))
                 self._timed("link", t0)
@@ -329,8 +321,7 @@ class GraphFlatIndex:
 
     def _install(self, graph):
         graph = graph.contiguous()
-        _ffi.check(self._lib.ivr_graph_set_neighbors(self._h, C.c_void_p(graph.data_ptr()), len(graph), _ffi.stream_ptr()),
-                   "ivr_graph_set_neighbors")
+        self._call("ivr_graph_set_neighbors", graph, len(graph))
         self._graph = graph
 
     def graph(self):
@@ -344,53 +335,32 @@ class GraphFlatIndex:
 
     def _checked_graph(self, graph, n, who):
         """graph as an int32 tensor [n, 2 M] on the device, or ValueError."""
-        if isinstance(graph, np.ndarray):
-            if not np.issubdtype(graph.dtype, np.integer):
-                raise ValueError(f"{who}: the graph must hold integers, got {graph.dtype}")
-            graph = torch.from_numpy(np.ascontiguousarray(graph))
-        if not isinstance(graph, torch.Tensor) or graph.dtype.is_floating_point or graph.dtype.is_complex or graph.dtype == torch.bool:
-            raise ValueError(f"{who}: the graph must be an integer numpy array or torch tensor")
+        graph = _staging.int_tensor(graph, f"{who}: the graph", "hold")
         if tuple(graph.shape) != (n, 2 * self.M):
             raise ValueError(f"{who}: expected [{n},{2 * self.M}], got {tuple(graph.shape)}")
         with torch.cuda.device(self.device):
             graph = graph.to(self.device)
-            if graph.numel() and bool(((graph >= n) | (graph < -1)).any().item()):
-                raise ValueError(f"{who}: entries must lie in [-1, {n})")
+            if graph.numel():
+                _staging.check_entries(graph, n, f"{who}: entries")
             return graph.to(torch.int32)
 
     # -- search ----------------------------------------------------------------------------------
     def _queries(self, x, k):
-        q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        t = _dev_f32(q, self.device)
-        if t.dim() != 2 or t.shape[1] != self.d:
-            raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({self.d})")
-        k = int(k)
-        if k < 1 or k > _ffi.IVR_GRAPH_MAX_EF:
-            raise ValueError(f"k={k} outside [1,{_ffi.IVR_GRAPH_MAX_EF}]")
-        if t.shape[0] < 1:
-            raise ValueError("search: no queries")
-        return t, k
+        t, staged = _staging.queries_f32(_staging.as_rows(x), self.d, self.device)
+        k = _staging.check_k(k, _ffi.IVR_GRAPH_MAX_EF)
+        _staging.check_nq(t.shape[0])
+        return t, k, staged
 
     def search(self, x, k, params=None):
         """(D, I) numpy arrays under the contract of FlatIPIndex.search.  params = SearchParametersHNSW(efSearch=...) overrides
         efSearch for this call; a selector raises ValueError."""
-        ef = None
-        if params is not None:
-            if not isinstance(params, SearchParametersHNSW):
-                raise ValueError(f"params must be a SearchParametersHNSW, got {type(params).__name__}")
-            if params.sel is not None:
-                raise ValueError("search: ID selectors are not supported on GraphFlatIndex")
-            ef = params.efSearch
-        D, I = self.search_device(x, k, efSearch=ef)
-        return D.cpu().numpy(), I.cpu().numpy()
+        params = typed_params(params, SearchParametersHNSW, "GraphFlatIndex")
+        return search_numpy(self, x, k, efSearch=None if params is None else params.efSearch)
 
     def search_device(self, x, k, normalize=False, efSearch=None):
         """Device-resident search: CUDA tensors.  The entries are the best n_entry rows of the entry sample for each query.
         normalize: a copy of the queries is L2-normalised once (normalize_L2) and serves the entry search and the walk."""
-        t, k = self._queries(x, k)
-        staged = t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0)
+        t, k, staged = self._queries(x, k)
         with torch.cuda.device(self.device):
             if self.ntotal == 0:
                 return (torch.full((t.shape[0], k), -_FLT_MAX, dtype=torch.float32, device=self.device),
@@ -401,23 +371,18 @@ class GraphFlatIndex:
             ne = max(1, min(int(self.hnsw.n_entry), self._entry.ntotal, _ffi.IVR_GRAPH_MAX_DEGREE))
             entries = self._entry.search_device(t, ne)[1].to(torch.int32)
             D, I, _ = self._walk(t, k, entries, efSearch, None)
-            if staged:
-                torch.cuda.current_stream().synchronize()    # the staging copy must outlive the kernels
+            _staging.sync_if_staged(staged)
         return D, I
 
     def search_from(self, x, k, entries, efSearch=None, max_expansions=None, return_stats=False, normalize=False):
         """The walk from caller-chosen entries: integers [nq, ne] (ne <= 64; -1 and repeats are skipped, as are rows outside the
         index).  normalize: ivr_graph_search L2-normalises the queries itself (normalize_q).  Returns numpy (D, I), and with
         return_stats also n_expanded int32 [nq]."""
-        t, k = self._queries(x, k)
-        e = np.asarray(entries)
-        if not np.issubdtype(e.dtype, np.integer) or e.ndim != 2 or e.shape[0] != t.shape[0] or not 1 <= e.shape[1] <= _ffi.IVR_GRAPH_MAX_DEGREE:
-            raise ValueError(f"search_from: entries must be integers [{t.shape[0]},1..{_ffi.IVR_GRAPH_MAX_DEGREE}]")
+        t, k, _ = self._queries(x, k)
+        e = _staging.entry_table(entries, t.shape[0], _ffi.IVR_GRAPH_MAX_DEGREE, "search_from")
         with torch.cuda.device(self.device):
-            et = torch.from_numpy(np.ascontiguousarray(e.clip(-1, 2**31 - 1), dtype=np.int32)).to(self.device)
-            D, I, nexp = self._walk(t, k, et, efSearch, max_expansions, normalize)
-            out = (D.cpu().numpy(), I.cpu().numpy())
-            return out + (nexp.cpu().numpy(),) if return_stats else out
+            D, I, nexp = self._walk(t, k, torch.from_numpy(e).to(self.device), efSearch, max_expansions, normalize)
+            return to_numpy((D, I, nexp) if return_stats else (D, I))
 
     def _walk(self, t, k, entries, efSearch, max_expansions, normalize=False):
         ef = max(int(self.hnsw.efSearch if efSearch is None else efSearch), k)
@@ -428,12 +393,9 @@ class GraphFlatIndex:
             mx = 8 * ef
         nq = t.shape[0]
         entries = entries.contiguous()
-        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        D, I = _staging.alloc_DI(nq, k, self.device)
         nexp = torch.empty(nq, dtype=torch.int32, device=self.device)
-        _ffi.check(self._lib.ivr_graph_search(self._h, C.c_void_p(t.data_ptr()), nq, k, ef, C.c_void_p(entries.data_ptr()), entries.shape[1],
-                                              min(mx, 2**31 - 1), int(bool(normalize)), C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()),
-                                              C.c_void_p(nexp.data_ptr()), _ffi.stream_ptr()), "ivr_graph_search")
+        self._call("ivr_graph_search", t, nq, k, ef, entries, entries.shape[1], min(mx, 2**31 - 1), bool(normalize), D, I, nexp)
         return D, I, nexp
 
     # -- maintenance -----------------------------------------------------------------------------
@@ -447,7 +409,7 @@ class GraphFlatIndex:
         """Drop the rows, the graph and the entry sample."""
         self._storage.reset()
         self._entry.reset()
-        _ffi.check(self._lib.ivr_graph_reset(self._h), "ivr_graph_reset")
+        self._call("ivr_graph_reset")
         self._graph = torch.zeros((0, 2 * self.M), dtype=torch.int32, device=self.device)
 
     def close(self):
@@ -455,15 +417,7 @@ class GraphFlatIndex:
         for x in (getattr(self, "_storage", None), getattr(self, "_entry", None)):
             if x is not None:
                 x.close()
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.ivr_graph_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 def IndexHNSWFlat(d, M=32, metric=METRIC_INNER_PRODUCT):

@@ -17,7 +17,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _ffi
+from . import _ffi, _staging
+from ._faiss import METRIC_INNER_PRODUCT, search_numpy, to_numpy
+from ._staging import dev_f32 as _dev_f32
 
 
 def _ids_i64(ids, n, what):
@@ -35,15 +37,6 @@ def _ids_i64(ids, n, what):
     return ids
 
 
-def _dev_f32(x, device):
-    """numpy / torch -> contiguous float32 CUDA tensor on `device` (a view when already there)."""
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-    if not isinstance(x, torch.Tensor):
-        raise ValueError("expected a numpy array or a torch tensor")
-    return x.to(device=device, dtype=torch.float32, non_blocking=False).contiguous()
-
-
 def normalize_L2(x):
     """faiss.normalize_L2(x): in-place row L2 normalisation of a float32 [n,d] array (zero rows stay zero)."""
     if isinstance(x, np.ndarray):
@@ -55,19 +48,13 @@ def normalize_L2(x):
         return
     if x.dtype != torch.float32 or x.dim() != 2 or not x.is_cuda or not x.is_contiguous():
         raise ValueError("normalize_L2 expects a contiguous float32 [n,d] CUDA tensor")
-    lib = _ffi.load()
-    with torch.cuda.device(x.device):
-        _ffi.check(lib.ivr_l2_normalize(_ffi.context(x.device.index), C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1],
-                                        None, _ffi.stream_ptr()), "ivr_l2_normalize")
+    _ffi.call("ivr_l2_normalize", _ffi.CTX, x, x.shape[0], x.shape[1], None, device=x.device)
 
 
 def count_nonfinite_and_normalize(t):
     """In-place normalise a CUDA tensor and return how many input elements were NaN/Inf (N2 validation)."""
-    lib = _ffi.load()
     flag = torch.zeros(1, dtype=torch.int32, device=t.device)
-    with torch.cuda.device(t.device):
-        _ffi.check(lib.ivr_l2_normalize(_ffi.context(t.device.index), C.c_void_p(t.data_ptr()), t.shape[0], t.shape[1],
-                                        C.c_void_p(flag.data_ptr()), _ffi.stream_ptr()), "ivr_l2_normalize")
+    _ffi.call("ivr_l2_normalize", _ffi.CTX, t, t.shape[0], t.shape[1], flag, device=t.device)
     return int(flag.item())
 
 
@@ -200,30 +187,25 @@ def _selector(params=None, sel=None):
     return sel
 
 
-class FlatIPIndex:
+class FlatIPIndex(_ffi.Handle):
     """Exact inner-product index (FAISS IndexFlatIP contract) on one GPU."""
+    _DESTROY = "ivr_index_destroy"
 
     def __init__(self, d, capacity=0, device=None):
-        self._lib = _ffi.load()
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         self.d = int(d)
         self.is_trained = True
-        self.metric_type = 0  # faiss.METRIC_INNER_PRODUCT
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_create(_ffi.context(self.device.index), self.d, int(capacity), C.byref(h)),
-                       "ivr_index_create")
-        self._h = h
+        self.metric_type = METRIC_INNER_PRODUCT
+        self._open("ivr_index_create", device, self.d, int(capacity))
 
     # -- FAISS surface ---------------------------------------------------------------------------
     @property
     def ntotal(self):
-        return int(self._lib.ivr_index_ntotal(self._h))
+        return int(_ffi.call("ivr_index_ntotal", self._h))
 
     def scan_stats(self):
         """(has_bf16_scan_copy, queries of the last scan chunk that were redone by the exact float32 scan)."""
         out = (C.c_int * 2)()
-        _ffi.check(self._lib.ivr_index_scan_stats(self._h, out), "ivr_index_scan_stats")
+        _ffi.call("ivr_index_scan_stats", self._h, out)
         return bool(out[0]), int(out[1])
 
     def train(self, x):  # core.py:817-820 calls train() when is_trained is False; flat indexes never need it
@@ -234,25 +216,19 @@ class FlatIPIndex:
         rows never needs a second full copy on either side (the reference adds 10k-row slices, unified_index.py:1770)."""
         if isinstance(x, np.ndarray) or (isinstance(x, torch.Tensor) and not x.is_cuda):
             n = len(x)
-            if x.ndim != 2 or x.shape[1] != self.d:
-                raise ValueError(f"add expects [n,{self.d}], got {tuple(x.shape)}")
+            _staging.check_rows(x, self.d, "add")
             for i in range(0, n, chunk_rows):
                 self._add_device(_dev_f32(x[i:i + chunk_rows], self.device), normalize)
             return
         self._add_device(_dev_f32(x, self.device), normalize)
 
     def _add_device(self, t, normalize, ids=None):
-        if t.dim() != 2 or t.shape[1] != self.d:
-            raise ValueError(f"add expects [n,{self.d}], got {tuple(t.shape)}")
-        with torch.cuda.device(self.device):
-            if ids is None:
-                _ffi.check(self._lib.ivr_index_add(self._h, C.c_void_p(t.data_ptr()), t.shape[0], int(bool(normalize)),
-                                                   _ffi.stream_ptr()), "ivr_index_add")
-            else:
-                i = torch.from_numpy(ids).to(self.device)
-                _ffi.check(self._lib.ivr_index_add_with_ids(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(i.data_ptr()), t.shape[0],
-                                                            int(bool(normalize)), _ffi.stream_ptr()), "ivr_index_add_with_ids")
-            torch.cuda.current_stream().synchronize()  # `t` may be a temporary staging copy
+        _staging.check_rows(t, self.d, "add")
+        if ids is None:
+            self._call("ivr_index_add", t, t.shape[0], bool(normalize))
+        else:
+            self._call("ivr_index_add_with_ids", t, torch.from_numpy(ids).to(self.device), t.shape[0], bool(normalize))
+        torch.cuda.current_stream(self.device).synchronize()  # `t` may be a temporary staging copy
 
     def add_with_ids(self, x, ids, normalize=False, chunk_rows=1 << 20):
         """faiss add_with_ids(x, ids): append rows under caller-chosen int64 labels (numpy or torch, one per row, every id >= 0: -1 is
@@ -260,8 +236,7 @@ class FlatIPIndex:
         makes it id-mapped until reset(): search / range_search return the stored ids, selectors and remove_ids name stored ids, and
         add() is refused.  ValueError for a wrong length, a non-integer dtype or a negative id; refused on an index that already holds
         rows without ids."""
-        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"add_with_ids expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        _staging.check_rows(x, self.d, "add_with_ids")
         n = len(x)
         ids = _ids_i64(ids, n, "add_with_ids")
         if n and int(ids.min()) < 0:
@@ -274,15 +249,14 @@ class FlatIPIndex:
     @property
     def has_ids(self):
         """True once add_with_ids (or IndexIDMap / IndexIDMap2) has made the index id-mapped; False again after reset()."""
-        return bool(self._lib.ivr_index_has_ids(self._h))
+        return bool(_ffi.call("ivr_index_has_ids", self._h))
 
     @property
     def id_map(self):
         """The stored ids in row order as a numpy int64 copy: faiss.vector_to_array(index.id_map)."""
         n = self.ntotal
         out = torch.empty(n, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_get_ids(self._h, 0, n, C.c_void_p(out.data_ptr()), _ffi.stream_ptr()), "ivr_index_get_ids")
+        self._call("ivr_index_get_ids", 0, n, out)
         return out.cpu().numpy()
 
     def find(self, ids):
@@ -295,9 +269,7 @@ class FlatIPIndex:
     def _find_device(self, keys):
         """keys: int64 CUDA tensor [n] of stored ids -> int64 CUDA tensor of their lowest rows (-1: not stored); no host sync."""
         rows = torch.empty(len(keys), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_find_ids(self._h, C.c_void_p(keys.data_ptr()), len(keys), C.c_void_p(rows.data_ptr()),
-                                                    _ffi.stream_ptr()), "ivr_index_find_ids")
+        self._call("ivr_index_find_ids", keys, len(keys), rows)
         return rows
 
     # -- row access by position / by key ---------------------------------------------------------
@@ -312,9 +284,7 @@ class FlatIPIndex:
         bits reconstruct_n returns; an entry outside [0, ntotal), -1 included, gives a NaN row.  Repeats are allowed.  No host sync."""
         rows = self._rows_i64(rows, "gather_device")
         out = torch.empty((len(rows), self.d), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_gather(self._h, C.c_void_p(rows.data_ptr()), len(rows), C.c_void_p(out.data_ptr()),
-                                                  _ffi.stream_ptr()), "ivr_index_gather")
+        self._call("ivr_index_gather", rows, len(rows), out)
         return out
 
     def scatter_device(self, rows, x, normalize=False):
@@ -325,9 +295,7 @@ class FlatIPIndex:
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
                 and x.dim() == 2 and x.shape == (len(rows), self.d)):
             raise ValueError(f"scatter_device expects a contiguous float32 CUDA tensor [{len(rows)},{self.d}]")
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_scatter(self._h, C.c_void_p(rows.data_ptr()), C.c_void_p(x.data_ptr()), len(rows),
-                                                   int(bool(normalize)), _ffi.stream_ptr()), "ivr_index_scatter")
+        self._call("ivr_index_scatter", rows, x, len(rows), bool(normalize))
 
     def _keys_device(self, keys, what):
         """keys (row numbers on a plain index, stored ids on an id-mapped one) -> (numpy int64 keys, int64 CUDA tensor of their rows,
@@ -358,8 +326,7 @@ class FlatIPIndex:
         """faiss IndexIVF::update_vectors on the flat index: the vectors stored under keys (as for reconstruct_batch) become x [n,d];
         ids and every other row stay.  ValueError for duplicate keys or a wrong shape; RuntimeError when a key names no row, and then
         nothing has been written."""
-        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"update_vectors expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        _staging.check_rows(x, self.d, "update_vectors")
         keys = _ids_i64(np.atleast_1d(keys) if not isinstance(keys, torch.Tensor) else keys, len(x), "update_vectors")
         if len(np.unique(keys)) != len(keys):
             raise ValueError("update_vectors: duplicate keys")
@@ -369,74 +336,49 @@ class FlatIPIndex:
             raise RuntimeError(f"update_vectors: key {int(keys[missing[0]])} is not in the index ({len(missing)} of {len(keys)} missing)")
         t = _dev_f32(x, self.device)
         self.scatter_device(rows, t, normalize)
-        with torch.cuda.device(self.device):
-            torch.cuda.current_stream().synchronize()  # `t` and `rows` are temporaries
+        torch.cuda.current_stream(self.device).synchronize()  # `t` and `rows` are temporaries
 
     def write(self, start, x, normalize=False):
         """Overwrite rows [start, start+n): ring-buffer maintenance for rolling indexes."""
         t = _dev_f32(x, self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_write(self._h, int(start), C.c_void_p(t.data_ptr()), t.shape[0],
-                                                 int(bool(normalize)), _ffi.stream_ptr()), "ivr_index_write")
-            torch.cuda.current_stream().synchronize()
+        self._call("ivr_index_write", int(start), t, t.shape[0], bool(normalize))
+        torch.cuda.current_stream(self.device).synchronize()
 
     def write_device(self, start, rows, normalize=False):
         """Stream-ordered overwrite from a float32 CUDA tensor already on this device (no host sync)."""
         if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous()
                 and rows.dim() == 2 and rows.shape[1] == self.d):
             raise ValueError(f"write_device expects a contiguous float32 CUDA tensor [n,{self.d}]")
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_write(self._h, int(start), C.c_void_p(rows.data_ptr()), rows.shape[0],
-                                                 int(bool(normalize)), _ffi.stream_ptr()), "ivr_index_write")
+        self._call("ivr_index_write", int(start), rows, rows.shape[0], bool(normalize))
 
     def write_ring(self, rows, cursor, normalize=False):
         """Overwrite the rows at *cursor (int64 CUDA scalar tensor) and advance it, all stream-ordered (graph-capturable)."""
         if cursor.dtype != torch.int64 or not cursor.is_cuda or cursor.numel() != 1:
             raise ValueError("cursor must be a 1-element int64 CUDA tensor")
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_write_ring(self._h, C.c_void_p(rows.data_ptr()), rows.shape[0], int(bool(normalize)),
-                                                      C.c_void_p(cursor.data_ptr()), _ffi.stream_ptr()), "ivr_index_write_ring")
+        self._call("ivr_index_write_ring", rows, rows.shape[0], bool(normalize), cursor)
 
     def search(self, x, k, params=None):
         """(D, I) numpy arrays, exactly like faiss: D float32 [nq,k] descending, I int64 [nq,k], -1 padded.  params =
         SearchParameters(sel=IDSelector...): the top k among the ids the selector allows.  On an id-mapped index (add_with_ids) the
         labels are the stored ids and the selector names stored ids; equal scores still rank the lower ROW first."""
         sel = _selector(params)
-        q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
-        if isinstance(q, np.ndarray) and q.ndim == 1:
-            q = q.reshape(1, -1)
-        D, I = self.search_device(q, k) if sel is None else self.search_device(q, k, sel=sel)
-        return D.cpu().numpy(), I.cpu().numpy()
+        q = _staging.as_rows(x, tensors_too=False)
+        return search_numpy(self, q, k) if sel is None else search_numpy(self, q, k, sel=sel)
 
     def search_device(self, x, k, normalize=False, id_base=0, out=None, sel=None):
         """Device-resident variant: returns CUDA tensors and does not synchronise.  sel: an IDSelector (ids = id_base + row).  On an
         id-mapped index id_base is ignored: labels and selectors are stored ids (one extra pass over the id table per filtered call,
         still without a host synchronisation, and the whole index is scanned whatever the selector's range)."""
         sel = _selector(sel=sel)
-        t = _dev_f32(x, self.device)
-        if t.dim() != 2 or t.shape[1] != self.d:
-            raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({self.d})")
-        k = int(k)
-        if k < 1 or k > _ffi.IVR_MAX_K:
-            raise ValueError(f"k={k} outside [1,{_ffi.IVR_MAX_K}]")
+        t, staged = _staging.queries_f32(x, self.d, self.device)
+        k = _staging.check_k(k, _ffi.IVR_MAX_K)
         nq = t.shape[0]
-        if out is None:
-            D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        D, I = _staging.alloc_DI(nq, k, self.device) if out is None else out
+        if sel is None:
+            self._call("ivr_index_search", t, nq, k, bool(normalize), int(id_base), D, I)
         else:
-            D, I = out
-        with torch.cuda.device(self.device):
-            if sel is None:
-                _ffi.check(self._lib.ivr_index_search(self._h, C.c_void_p(t.data_ptr()), nq, k, int(bool(normalize)),
-                                                      int(id_base), C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()),
-                                                      _ffi.stream_ptr()), "ivr_index_search")
-            else:
-                f = sel._filter(self.device)
-                _ffi.check(self._lib.ivr_index_search_filtered(self._h, C.c_void_p(t.data_ptr()), nq, k, int(bool(normalize)), int(id_base),
-                                                               C.byref(f), C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()),
-                                                               _ffi.stream_ptr()), "ivr_index_search_filtered")
-            if t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0):
-                torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
+            self._call("ivr_index_search_filtered", t, nq, k, bool(normalize), int(id_base), sel._filter(self.device), D, I)
+        _staging.sync_if_staged(staged, self.device)
         return D, I
 
     def search_and_reconstruct(self, x, k, params=None):
@@ -444,33 +386,19 @@ class FlatIPIndex:
         the stored row behind each slot (the row that scored, also where an id-mapped index stores a label twice), NaN rows for the
         -1 slots.  params = SearchParameters(sel=...) as for search."""
         sel = _selector(params)
-        q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
-        if isinstance(q, np.ndarray) and q.ndim == 1:
-            q = q.reshape(1, -1)
-        D, I, R = self.search_and_reconstruct_device(q, k, sel=sel)
-        return D.cpu().numpy(), I.cpu().numpy(), R.cpu().numpy()
+        return to_numpy(self.search_and_reconstruct_device(_staging.as_rows(x, tensors_too=False), k, sel=sel))
 
     def search_and_reconstruct_device(self, x, k, normalize=False, id_base=0, sel=None):
         """Device-resident search_and_reconstruct: (D, I, R) CUDA tensors, arguments as for search_device."""
         sel = _selector(sel=sel)
-        t = _dev_f32(x, self.device)
-        if t.dim() != 2 or t.shape[1] != self.d:
-            raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({self.d})")
-        k = int(k)
-        if k < 1 or k > _ffi.IVR_MAX_K:
-            raise ValueError(f"k={k} outside [1,{_ffi.IVR_MAX_K}]")
+        t, staged = _staging.queries_f32(x, self.d, self.device)
+        k = _staging.check_k(k, _ffi.IVR_MAX_K)
         nq = t.shape[0]
-        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        D, I = _staging.alloc_DI(nq, k, self.device)
         R = torch.empty((nq, k, self.d), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            f = None if sel is None else sel._filter(self.device)
-            _ffi.check(self._lib.ivr_index_search_reconstruct(self._h, C.c_void_p(t.data_ptr()), nq, k, int(bool(normalize)), int(id_base),
-                                                              None if f is None else C.byref(f), C.c_void_p(D.data_ptr()),
-                                                              C.c_void_p(I.data_ptr()), C.c_void_p(R.data_ptr()), _ffi.stream_ptr()),
-                       "ivr_index_search_reconstruct")
-            if t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0):
-                torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
+        f = None if sel is None else sel._filter(self.device)
+        self._call("ivr_index_search_reconstruct", t, nq, k, bool(normalize), int(id_base), f, D, I, R)
+        _staging.sync_if_staged(staged, self.device)
         return D, I, R
 
     def range_search(self, x, radius, params=None):
@@ -479,10 +407,7 @@ class FlatIPIndex:
         pass only when the first-guess capacity was too small.  params = SearchParameters(sel=...): only the allowed ids.  On an
         id-mapped index I holds stored ids (in ascending ROW order within a query) and the selector names stored ids."""
         sel = _selector(params)
-        q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
-        if isinstance(q, np.ndarray) and q.ndim == 1:
-            q = q.reshape(1, -1)
-        t = _dev_f32(q, self.device)
+        t = _dev_f32(_staging.as_rows(x, tensors_too=False), self.device)
         cap = max(1024, 64 * t.shape[0])
         lims, D, I, total = self.range_search_device(t, radius, cap=cap, sel=sel)
         n = int(total.item())
@@ -499,27 +424,19 @@ class FlatIPIndex:
         radius = float(radius)
         if radius != radius:
             raise ValueError("range_search: radius is NaN")
-        t = _dev_f32(x, self.device)
-        if t.dim() != 2 or t.shape[1] != self.d:
-            raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({self.d})")
+        t, staged = _staging.queries_f32(x, self.d, self.device)
         nq = t.shape[0]
-        if nq < 1:
-            raise ValueError("range_search: no queries")
+        _staging.check_nq(nq, "range_search")
         lims = torch.empty(nq + 1, dtype=torch.int64, device=self.device)
 
         def run(c):
             D = torch.empty(max(c, 1), dtype=torch.float32, device=self.device)   # never a NULL pointer, even for cap 0
             I = torch.empty(max(c, 1), dtype=torch.int64, device=self.device)
             if sel is None:
-                _ffi.check(self._lib.ivr_index_range_search(self._h, C.c_void_p(t.data_ptr()), nq, C.c_float(radius), int(bool(normalize)),
-                                                            int(id_base), C.c_void_p(lims.data_ptr()), C.c_void_p(D.data_ptr()),
-                                                            C.c_void_p(I.data_ptr()), int(c), _ffi.stream_ptr()), "ivr_index_range_search")
+                self._call("ivr_index_range_search", t, nq, radius, bool(normalize), int(id_base), lims, D, I, int(c))
             else:
-                f = sel._filter(self.device)
-                _ffi.check(self._lib.ivr_index_range_search_filtered(self._h, C.c_void_p(t.data_ptr()), nq, C.c_float(radius),
-                                                                     int(bool(normalize)), int(id_base), C.byref(f), C.c_void_p(lims.data_ptr()),
-                                                                     C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()), int(c),
-                                                                     _ffi.stream_ptr()), "ivr_index_range_search_filtered")
+                self._call("ivr_index_range_search_filtered", t, nq, radius, bool(normalize), int(id_base), sel._filter(self.device),
+                           lims, D, I, int(c))
             return D[:c], I[:c]
 
         with torch.cuda.device(self.device):
@@ -527,20 +444,16 @@ class FlatIPIndex:
                 run(0)
                 cap = int(lims[nq].item())
             D, I = run(int(cap))
-            if t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0):
-                torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
+            _staging.sync_if_staged(staged)
         return lims, D, I, lims[nq:]
 
     def reserve_search(self, max_nq, max_k):
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_reserve_search(self._h, int(max_nq), int(max_k)), "ivr_index_reserve_search")
+        self._call("ivr_index_reserve_search", int(max_nq), int(max_k))
 
     def reconstruct_n(self, start=0, n=None):
         n = self.ntotal - start if n is None else n
         out = torch.empty((n, self.d), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_reconstruct(self._h, int(start), int(n), C.c_void_p(out.data_ptr()),
-                                                       _ffi.stream_ptr()), "ivr_index_reconstruct")
+        self._call("ivr_index_reconstruct", int(start), int(n), out)
         return out.cpu().numpy()
 
     def reconstruct(self, i):
@@ -566,26 +479,11 @@ class FlatIPIndex:
             raise ValueError(f"remove_ids: sel must be an IDSelectorRange / IDSelectorBatch / IDSelectorBitmap or an integer array, "
                              f"got {type(sel).__name__}")
         n = C.c_int64(0)
-        with torch.cuda.device(self.device):
-            f = sel._filter(self.device)
-            _ffi.check(self._lib.ivr_index_remove_ids(self._h, int(id_base), C.byref(f), C.byref(n), _ffi.stream_ptr()),
-                       "ivr_index_remove_ids")
+        self._call("ivr_index_remove_ids", int(id_base), sel._filter(self.device), n)
         return int(n.value)
 
     def reset(self):
-        with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_index_reset(self._h), "ivr_index_reset")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ivr_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("ivr_index_reset")
 
 
 def IndexFlatIP(d):
@@ -609,39 +507,26 @@ IndexIDMap = IndexIDMap2      # faiss.IndexIDMap differs only in lacking reconst
 
 def topk_merge(D_parts, I_parts, k=None):
     """Merge per-shard candidates [parts,nq,k] (CUDA tensors, global ids, parts in ascending id order)."""
-    lib = _ffi.load()
     parts, nq, kk = D_parts.shape
     k = kk if k is None else k
-    D = torch.empty((nq, k), dtype=torch.float32, device=D_parts.device)
-    I = torch.empty((nq, k), dtype=torch.int64, device=D_parts.device)
+    D, I = _staging.alloc_DI(nq, k, D_parts.device)
     if k != kk:
         raise ValueError("merge k must equal the per-shard k")
-    with torch.cuda.device(D_parts.device):
-        _ffi.check(lib.ivr_topk_merge(_ffi.context(D_parts.device.index), C.c_void_p(D_parts.contiguous().data_ptr()),
-                                      C.c_void_p(I_parts.contiguous().data_ptr()), parts, nq, k,
-                                      C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()), _ffi.stream_ptr()),
-                   "ivr_topk_merge")
+    _ffi.call("ivr_topk_merge", _ffi.CTX, D_parts.contiguous(), I_parts.contiguous(), parts, nq, k, D, I, device=D_parts.device)
     return D, I
 
 
 def topk_pack(D, I):
     """(D float32 [nq,k], I int64 [nq,k]) CUDA -> int32 [nq,k,3] (score bits, id lo, id hi): the wire format of the one all-gather."""
-    lib = _ffi.load()
     nq, k = D.shape
     out = torch.empty((nq, k, 3), dtype=torch.int32, device=D.device)
-    with torch.cuda.device(D.device):
-        _ffi.check(lib.ivr_topk_pack(_ffi.context(D.device.index), C.c_void_p(D.contiguous().data_ptr()), C.c_void_p(I.contiguous().data_ptr()),
-                                     nq, k, C.c_void_p(out.data_ptr()), _ffi.stream_ptr()), "ivr_topk_pack")
+    _ffi.call("ivr_topk_pack", _ffi.CTX, D.contiguous(), I.contiguous(), nq, k, out, device=D.device)
     return out
 
 
 def topk_merge_packed(packed_parts):
     """Merge gathered candidates int32 [parts,nq,k,3] (parts in ascending id order) -> (D [nq,k], I [nq,k])."""
-    lib = _ffi.load()
     parts, nq, k, _ = packed_parts.shape
-    D = torch.empty((nq, k), dtype=torch.float32, device=packed_parts.device)
-    I = torch.empty((nq, k), dtype=torch.int64, device=packed_parts.device)
-    with torch.cuda.device(packed_parts.device):
-        _ffi.check(lib.ivr_topk_merge_packed(_ffi.context(packed_parts.device.index), C.c_void_p(packed_parts.data_ptr()), parts, nq, k,
-                                             C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()), _ffi.stream_ptr()), "ivr_topk_merge_packed")
+    D, I = _staging.alloc_DI(nq, k, packed_parts.device)
+    _ffi.call("ivr_topk_merge_packed", _ffi.CTX, packed_parts, parts, nq, k, D, I, device=packed_parts.device)
     return D, I

@@ -13,16 +13,12 @@ update are HIP kernels of libivr_hip.so (csrc/search_ivf.hip), torch only orders
 Tie rule: equal scores rank the row in the LOWER LIST first, and within a list the row ADDED EARLIER (the lower storage row).  A
 result therefore does not depend on the order in which lists were probed.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _ffi
+from . import _ffi, _staging
+from ._faiss import METRIC_INNER_PRODUCT, METRIC_L2, search_numpy, to_numpy, typed_params  # noqa: F401  (METRIC_L2: exported from here)
 from .index import FlatIPIndex, _dev_f32, _ids_i64, normalize_L2
-
-METRIC_INNER_PRODUCT = 0      # faiss.METRIC_INNER_PRODUCT
-METRIC_L2 = 1                 # faiss.METRIC_L2: named so that asking for it can be refused
 
 
 # -- pure numpy helpers (no GPU) ---------------------------------------------------------------------------------------------
@@ -142,9 +138,7 @@ class IVFFlatIndex:
         n = self.ntotal - start if n is None else n
         out = torch.empty(n, dtype=torch.int64, device=self.device)
         if n:
-            with torch.cuda.device(self.device):
-                _ffi.check(self._lib.ivr_index_get_ids(self._storage._h, int(start), int(n), C.c_void_p(out.data_ptr()), _ffi.stream_ptr()),
-                           "ivr_index_get_ids")
+            self._storage._call("ivr_index_get_ids", int(start), int(n), out)
         return out
 
     def _set_lists(self, row_list):
@@ -171,8 +165,7 @@ class IVFFlatIndex:
             return
         if self.quantizer.ntotal != 0:
             raise ValueError(f"train: the quantizer holds {self.quantizer.ntotal} rows, expected 0 or nlist={self.nlist}")
-        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"train expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        _staging.check_rows(x, self.d, "train")
         n = len(x)
         if n < self.nlist:
             raise ValueError(f"train: {n} training rows for nlist={self.nlist}")
@@ -205,9 +198,7 @@ class IVFFlatIndex:
         counts = torch.bincount(a, minlength=self.nlist)
         off = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(counts, 0)]).contiguous()
         out = torch.empty((self.nlist, self.d), dtype=torch.float32, device=self.device)
-        _ffi.check(self._lib.ivr_segment_mean(_ffi.context(self.device.index), C.c_void_p(rows.data_ptr()), len(rows), C.c_void_p(off.data_ptr()),
-                                              self.nlist, self.d, int(spherical), C.c_void_p(out.data_ptr()), _ffi.stream_ptr()),
-                   "ivr_segment_mean")
+        _ffi.call("ivr_segment_mean", _ffi.CTX, rows, len(rows), off, self.nlist, self.d, spherical, out, device=self.device)
         counts = counts.cpu().numpy()
         if (counts == 0).any():
             c = out.cpu().numpy()
@@ -238,8 +229,7 @@ class IVFFlatIndex:
         the index in flight, so add in large batches.  RuntimeError while untrained."""
         if not self.is_trained:
             raise RuntimeError(f"{_what}: the index is not trained")
-        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"{_what} expects [n,{self.d}], got {tuple(getattr(x, 'shape', ()))}")
+        _staging.check_rows(x, self.d, _what)
         n = len(x)
         ids = _ids_i64(ids, n, _what)
         if n and int(ids.min()) < 0:
@@ -268,32 +258,17 @@ class IVFFlatIndex:
 
     # -- search ----------------------------------------------------------------------------------
     def _queries(self, x, k, what):
-        q = np.asarray(x) if not isinstance(x, torch.Tensor) else x
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        t = _dev_f32(q, self.device)
-        if t.dim() != 2 or t.shape[1] != self.d:
-            raise ValueError(f"Query dimension ({tuple(t.shape)}) != index dimension ({self.d})")
-        k = int(k)
-        if k < 1 or k > _ffi.IVR_MAX_K:
-            raise ValueError(f"k={k} outside [1,{_ffi.IVR_MAX_K}]")
+        t, staged = _staging.queries_f32(_staging.as_rows(x), self.d, self.device)
+        k = _staging.check_k(k, _ffi.IVR_MAX_K)
         if not self.is_trained:
             raise RuntimeError(f"{what}: the index is not trained")
-        staged = t.data_ptr() != (x.data_ptr() if isinstance(x, torch.Tensor) else 0)
         return t, k, staged
 
     def search(self, x, k, params=None):
         """(D, I) numpy arrays under the contract of FlatIPIndex.search, over the rows of the nprobe lists nearest to each query.
         params = SearchParametersIVF(nprobe=...) overrides nprobe for this call; a selector raises ValueError."""
-        nprobe = None
-        if params is not None:
-            if not isinstance(params, SearchParametersIVF):
-                raise ValueError(f"params must be a SearchParametersIVF, got {type(params).__name__}")
-            if params.sel is not None:
-                raise ValueError("search: ID selectors are not supported on IVFFlatIndex")
-            nprobe = params.nprobe
-        D, I = self.search_device(x, k, nprobe=nprobe)
-        return D.cpu().numpy(), I.cpu().numpy()
+        params = typed_params(params, SearchParametersIVF, "IVFFlatIndex")
+        return search_numpy(self, x, k, nprobe=None if params is None else params.nprobe)
 
     def search_device(self, x, k, normalize=False, nprobe=None):
         """Device-resident search: CUDA tensors, no host synchronisation (unless x had to be staged).  nprobe (default: the
@@ -315,41 +290,28 @@ class IVFFlatIndex:
         """faiss search_preassigned: assign int64 [nq,p] (numpy or CUDA tensor) names the lists to scan for each query; -1 entries
         are skipped and a list named twice is scanned once.  ValueError for an entry >= nlist or < -1 (checked on the tensor, before
         any kernel of the scan is launched).  Returns (D, I) numpy arrays."""
-        D, I = self.search_preassigned_device(x, k, assign)
-        return D.cpu().numpy(), I.cpu().numpy()
+        return to_numpy(self.search_preassigned_device(x, k, assign))
 
     def search_preassigned_device(self, x, k, assign, normalize=False):
         """search_preassigned returning CUDA tensors; the range check of assign synchronises once."""
         t, k, staged = self._queries(x, k, "search_preassigned")
-        if isinstance(assign, np.ndarray):
-            if not np.issubdtype(assign.dtype, np.integer):
-                raise ValueError(f"search_preassigned: assign must be integers, got {assign.dtype}")
-            assign = torch.from_numpy(np.ascontiguousarray(assign, dtype=np.int64))
-        if not isinstance(assign, torch.Tensor) or assign.dtype.is_floating_point or assign.dtype in (torch.bool,):
-            raise ValueError("search_preassigned: assign must be an integer numpy array or torch tensor")
+        assign = _staging.int_tensor(assign, "search_preassigned: assign", np_dtype=np.int64)
         if assign.dim() != 2 or assign.shape[0] != t.shape[0] or assign.shape[1] < 1:
             raise ValueError(f"search_preassigned: assign must be [{t.shape[0]},p] with p >= 1, got {tuple(assign.shape)}")
         with torch.cuda.device(self.device):
             assign = assign.to(device=self.device, dtype=torch.int64)
-            if bool(((assign >= self.nlist) | (assign < -1)).any().item()):
-                raise ValueError(f"search_preassigned: assign entries must lie in [-1, {self.nlist})")
+            _staging.check_entries(assign, self.nlist, "search_preassigned: assign entries")
             return self._scan(t, k, assign, normalize, staged)
 
     def _scan(self, t, k, assign, normalize, staged):
         """assign: int64 CUDA [nq,p], entries in [-1, nlist).  The kernel wants every row ascending (a repeated list is then adjacent)."""
         nq, p = assign.shape
-        if nq < 1:
-            raise ValueError("search: no queries")
+        _staging.check_nq(nq)
         assign = torch.sort(assign, dim=1).values.contiguous()
-        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        D, I = _staging.alloc_DI(nq, k, self.device)
         bound = int(self._by_size[min(p, self.nlist)])
-        _ffi.check(self._lib.ivr_index_search_lists(self._storage._h, C.c_void_p(self._off.data_ptr()), self.nlist, C.c_void_p(t.data_ptr()), nq,
-                                                    C.c_void_p(assign.data_ptr()), p, bound, k, int(bool(normalize)),
-                                                    C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()), _ffi.stream_ptr()),
-                   "ivr_index_search_lists")
-        if staged:
-            torch.cuda.current_stream().synchronize()  # staging copy must outlive the kernels
+        self._storage._call("ivr_index_search_lists", self._off, self.nlist, t, nq, assign, p, bound, k, bool(normalize), D, I)
+        _staging.sync_if_staged(staged, self.device)
         return D, I
 
     # -- maintenance -----------------------------------------------------------------------------

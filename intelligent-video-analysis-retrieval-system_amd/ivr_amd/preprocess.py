@@ -4,8 +4,6 @@ Mirrors what `HFCLIPProcessor(images=...)` (core.py:1613) and
 `Image.resize` + the ViT processor (video_frame_filter.py:58-59,29) compute,
 but takes a batch of same-sized uint8 NHWC frames already in HBM.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -18,7 +16,6 @@ def preprocess_frames(frames, mode="identity", mean=CLIP_MEAN, std=CLIP_STD, bgr
     """frames: uint8 [n,h,w,3] (numpy or CUDA tensor).  Returns a CUDA tensor:
     patch=None -> [n,3,size,size] (NCHW);  patch=P -> patch-major [n*(size/P)^2, Kpad], Kpad = 3*P*P rounded up to 64.
     """
-    lib = _ffi.load()
     if isinstance(frames, np.ndarray):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
@@ -49,8 +46,6 @@ def preprocess_frames(frames, mode="identity", mean=CLIP_MEAN, std=CLIP_STD, bgr
         out = torch.empty(shape, dtype=out_dtype, device=frames.device)
     elif tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous {out_dtype} tensor of shape {shape}")
-    with torch.cuda.device(frames.device):
-        _ffi.check(lib.ivr_preprocess(_ffi.context(frames.device.index), C.c_void_p(frames.data_ptr()), n, h, w, flags,
-                                      _ffi.f3(mean), _ffi.f3(std), int(size), int(patch or size),
-                                      C.c_void_p(out.data_ptr()), _ffi.stream_ptr()), "ivr_preprocess")
+    _ffi.call("ivr_preprocess", _ffi.CTX, frames, n, h, w, flags, _ffi.f3(mean), _ffi.f3(std), int(size), int(patch or size), out,
+              device=frames.device)
     return out

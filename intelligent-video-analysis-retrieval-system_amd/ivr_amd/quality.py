@@ -13,8 +13,6 @@ ivr_frame_quality (csrc/quality.hip) for a whole batch of same-sized frames in H
 reference uses cv2.imread).  OpenCV is not installed in this environment: the operators follow their published definitions
 and are checked against oracle/quality_ref.py, which is "parity unpinned" for the same reason.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -38,10 +36,7 @@ def frame_quality_scores(frames, bgr=False, canny_low=CANNY_LOW, canny_high=CANN
         return []
     lap = torch.empty((n, 2), dtype=torch.int64, device=frames.device)
     cnt = torch.empty(n, dtype=torch.int64, device=frames.device)
-    with torch.cuda.device(frames.device):
-        _ffi.check(_ffi.load().ivr_frame_quality(_ffi.context(frames.device.index), C.c_void_p(frames.data_ptr()), n, h, w, int(bool(bgr)),
-                                                 int(canny_low), int(canny_high), C.c_void_p(lap.data_ptr()), C.c_void_p(cnt.data_ptr()),
-                                                 _ffi.stream_ptr()), "ivr_frame_quality")
+    _ffi.call("ivr_frame_quality", _ffi.CTX, frames, n, h, w, bool(bgr), int(canny_low), int(canny_high), lap, cnt, device=frames.device)
     lap, cnt = lap.cpu().numpy(), cnt.cpu().numpy()
     N = float(h * w)
     out = []

@@ -80,9 +80,7 @@ class StreamingSession:
         self.graph = None
         if stream is not None and self.tower.device.type == "cuda":
             from . import _ffi
-            import ctypes as C
-            _ffi.check(_ffi.load().ivr_release_stream_scratch(_ffi.context(self.tower.device.index), C.c_void_p(stream.cuda_stream)),
-                       "ivr_release_stream_scratch")
+            _ffi.call("ivr_release_stream_scratch", _ffi.context(self.tower.device.index), stream.cuda_stream)
             self.stream = None
 
     def step(self, frames=None):

@@ -18,8 +18,6 @@ is reachable offline.  Activations are cast to e4m3 at unit scale (saturation at
 outlier stress test of tests/test_fp8_gpu.py exercises: trained CLIP towers have outlier channels, so re-run tools/fp8_error_budget.py
 on the real checkpoint (model_path= directory) before trusting a preset with it.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -30,10 +28,11 @@ from .preprocess import preprocess_frames
 FP8_PRESETS = ("fp8", "fp8_strict", "fp8_mlp", "fp8_all")
 
 
-class Tower:
+class Tower(_ffi.Handle):
+    _DESTROY = "ivr_tower_destroy"
+
     def __init__(self, cfg: TowerConfig, weights, max_batch=256, compute="bf16", device=None, fp8_sites=None, fp8_cls_bf16=None,
                  fp8_first_layer=None):
-        self._lib = _ffi.load()
         self.cfg = cfg
         self.compute = compute
         sites, cls, first = 0, 0, 0
@@ -54,7 +53,6 @@ class Tower:
         elif fp8_sites is not None or fp8_cls_bf16 is not None or fp8_first_layer is not None:
             raise ValueError("fp8_sites / fp8_cls_bf16 / fp8_first_layer only apply to compute='fp8' / 'fp8_mlp' / 'fp8_all'")
         self.fp8_sites, self.fp8_cls_bf16, self.fp8_first_layer = sites, cls, first
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
         self.max_batch = int(max_batch)
         # patch-major pixels stay bf16 in the fp8 mode (only the four GEMMs of every block run on the fp8 MFMA)
         self.act_dtype = torch.float32 if compute == "f32" else torch.bfloat16
@@ -64,16 +62,12 @@ class Tower:
                            vocab=cfg.vocab, eos_id=cfg.eos_id, causal=int(cfg.causal),
                            compute={"bf16": 0, "f32": 1, "fp8": 2, "fp8_strict": 2, "fp8_mlp": 2, "fp8_all": 2}[compute], ln_eps=cfg.ln_eps,
                            fp8_sites=sites, fp8_mlp_cls_bf16=cls, fp8_first_layer=first)
-        h = C.c_void_p()
+        self._open("ivr_tower_create", device, d)
         with torch.cuda.device(self.device):
-            _ffi.check(self._lib.ivr_tower_create(_ffi.context(self.device.index), C.byref(d), C.byref(h)),
-                       "ivr_tower_create")
-            self._h = h
             for name, arr in weights.items():
                 a = np.ascontiguousarray(arr, dtype=np.float32)
-                _ffi.check(self._lib.ivr_tower_set_weight(h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size),
-                           f"ivr_tower_set_weight({name})")
-            _ffi.check(self._lib.ivr_tower_finalize(h, self.max_batch), "ivr_tower_finalize")
+                self._call("ivr_tower_set_weight", name.encode(), a.ctypes.data, a.size, what=f"ivr_tower_set_weight({name})")
+            self._call("ivr_tower_finalize", self.max_batch)
 
     @property
     def embed_dim(self):
@@ -81,7 +75,7 @@ class Tower:
 
     @property
     def workspace_bytes(self):
-        return int(self._lib.ivr_tower_workspace_bytes(self._h))
+        return int(_ffi.call("ivr_tower_workspace_bytes", self._h))
 
     # -- vision --------------------------------------------------------------------------------
     def encode_patches(self, patches, n, normalize=True, out=None, capture_hidden=None):
@@ -91,14 +85,10 @@ class Tower:
         if out is None:
             out = torch.empty((n, self.embed_dim), dtype=torch.float32, device=self.device)
         hidden = None
-        with torch.cuda.device(self.device):
-            if capture_hidden is not None:
-                hidden = torch.empty((n, self.cfg.tokens, self.cfg.width), dtype=torch.float32, device=self.device)
-                _ffi.check(self._lib.ivr_tower_debug_hidden(self._h, int(capture_hidden), n, C.c_void_p(hidden.data_ptr()),
-                                                            _ffi.stream_ptr()), "ivr_tower_debug_hidden")
-            _ffi.check(self._lib.ivr_tower_encode_image(self._h, C.c_void_p(patches.data_ptr()), int(n), int(bool(normalize)),
-                                                        C.c_void_p(out.data_ptr()), _ffi.stream_ptr()),
-                       "ivr_tower_encode_image")
+        if capture_hidden is not None:
+            hidden = torch.empty((n, self.cfg.tokens, self.cfg.width), dtype=torch.float32, device=self.device)
+            self._call("ivr_tower_debug_hidden", int(capture_hidden), n, hidden)
+        self._call("ivr_tower_encode_image", patches, int(n), bool(normalize), out)
         return (out, hidden) if capture_hidden is not None else out
 
     def encode_frames(self, frames, mode="identity", mean=None, std=None, bgr=False, normalize=True, out=None):
@@ -128,21 +118,7 @@ class Tower:
         ids = ids.to(device=self.device, dtype=torch.int64).contiguous()
         q, T = ids.shape
         out = torch.empty((q, self.embed_dim), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            for i in range(0, q, self.max_batch):
-                sub = ids[i:i + self.max_batch].contiguous()
-                _ffi.check(self._lib.ivr_tower_encode_text(self._h, C.c_void_p(sub.data_ptr()), sub.shape[0], T,
-                                                           int(bool(normalize)), C.c_void_p(out[i:].data_ptr()),
-                                                           _ffi.stream_ptr()), "ivr_tower_encode_text")
+        for i in range(0, q, self.max_batch):
+            sub = ids[i:i + self.max_batch].contiguous()
+            self._call("ivr_tower_encode_text", sub, sub.shape[0], T, bool(normalize), out[i:])
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ivr_tower_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
