@@ -403,6 +403,25 @@ int ivr_index_search_lists(ivr_index *idx, const int64_t *list_off /*DEV [nlist+
 int ivr_segment_mean(ivr_ctx *ctx, const float *rows /*DEV [n,d]*/, int64_t n, const int64_t *seg_off /*DEV [nseg+1]*/, int nseg, int d,
                      int normalize, float *out /*DEV [nseg,d]*/, ivr_stream stream);
 
+/* ---- exact re-ranking of candidate lists (faiss IndexRefineFlat, IndexFlat::compute_distance_subset) ----
+ * Query i is scored against the kc storage rows cand[i][0 .. kc) only: the rows a cheaper index (binary codes, inverted lists, a
+ * graph) proposed.  The call is positional like ivr_index_gather, on plain and id-mapped indexes alike.  An entry outside
+ * [0, ntotal), -1 included, is absent.  A score is the float32 inner product ivr_index_search reports for the same (query, row), to
+ * the bit (the float32 tiles, the same summation order, -0.0 folded onto +0.0 as there); the bf16 scan copy is not read.
+ *   D_all  DEV [nq][kc] or NULL: D_all[i][j] = the score of cand[i][j], -FLT_MAX for an absent entry.  Order and repeats are the
+ *          caller's (compute_distance_subset).
+ *   D, I   DEV [nq][k], both or neither, 1 <= k <= kc: the best k candidates of each query in the order of ivr_index_search, score
+ *          descending and equal scores the lower row first, wherever they stood in cand.  I holds row positions.  A row named m
+ *          times in one list appears m times, in adjacent slots (faiss does the same).  Slots beyond the present candidates hold
+ *          -FLT_MAX / -1.
+ * 1 <= kc <= IVR_MAX_K, nq >= 1, nq kc < 2^31 and at least one output, IVR_ERR_INVALID otherwise; an empty index gives absent
+ * results only.  One wave scores 16 candidates of one query, so a single query's list spreads over the whole device; a random row
+ * moves 16 times its bytes in cache lines, as for ivr_index_gather.  Scratch: 8 bytes per (query, candidate) when D / I are asked
+ * for, grow-only.  Enqueue-only once the scratch has grown (a call that grows it allocates); not graph-capturable then. */
+int ivr_index_rescore(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, const int64_t *cand /*DEV [nq][kc]*/, int kc, int k,
+                      int normalize_q, float *D_all /*DEV [nq][kc] or NULL*/, float *D /*DEV [nq][k] or NULL*/,
+                      int64_t *I /*DEV [nq][k] or NULL*/, ivr_stream stream);
+
 /* ---- binary codes (faiss IndexBinaryFlat, and the sign-bit encoder of IndexLSH) --------------------------
  * Stands in for faiss.IndexLSH(dimension, 256), one of the index types of _create_index (core.py:1198-1230): a row is stored as
  * nbits sign bits (32 bytes at 256 bits, where the flat index stores 2-4.6 KB) and ranked by Hamming distance.

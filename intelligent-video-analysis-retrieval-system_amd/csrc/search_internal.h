@@ -192,6 +192,8 @@ struct ivr_index {
     DevBuf<int64_t> ivf_off;         // DEV [nlist + 1] pairs in front of each list, then [nlist + 1] 16-query pair tiles in front of it
     DevBuf<int> ivf_pair_q;          // DEV [pairs of a chunk]: the (query, list) pairs grouped by list: the query of the chunk ...
     DevBuf<int64_t> ivf_pair_slot;   // ... and its first key slot for that list
+    // exact re-ranking of candidate lists (ivr_index_rescore, search_refine.hip); grow-only
+    DevBuf<uint64_t> refine_keys;    // DEV [nq][kc]: (ordered score, ~row) of every candidate, 0 for an absent one
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

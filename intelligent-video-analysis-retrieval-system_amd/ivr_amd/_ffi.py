@@ -102,6 +102,7 @@ _SIGS = {
     "ivr_index_search_reconstruct": (_i, [_p, _p, _i, _i, _i, _i64, C.POINTER(IdFilter), _p, _p, _p, _p]),
     "ivr_index_search_lists": (_i, [_p, _p, _i, _p, _i, _p, _i, _i64, _i, _i, _p, _p, _p]),
     "ivr_segment_mean": (_i, [_p, _p, _i64, _p, _i, _i, _i, _p, _p]),
+    "ivr_index_rescore": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
     "ivr_bin_index_create": (_i, [_p, _i, _i64, C.POINTER(_p)]),
     "ivr_bin_index_destroy": (_i, [_p]),
     "ivr_bin_index_reset": (_i, [_p]),
@@ -143,7 +144,7 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_index_add", "ivr_index_write", "ivr_index_write_ring", "ivr_index_reconstruct", "ivr_index_search", "ivr_index_range_search",
     "ivr_index_search_filtered", "ivr_index_range_search_filtered", "ivr_index_remove_ids", "ivr_index_add_with_ids",
     "ivr_index_get_ids", "ivr_index_find_ids", "ivr_index_gather", "ivr_index_scatter", "ivr_index_search_reconstruct",
-    "ivr_index_search_lists", "ivr_segment_mean", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
+    "ivr_index_search_lists", "ivr_segment_mean", "ivr_index_rescore", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
     "ivr_sign_encode", "ivr_graph_set_rows", "ivr_graph_prune", "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
     "ivr_scene_keep_mask_window", "ivr_frame_quality")}

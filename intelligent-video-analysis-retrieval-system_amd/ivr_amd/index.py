@@ -338,6 +338,53 @@ class FlatIPIndex(_ffi.Handle):
         self.scatter_device(rows, t, normalize)
         torch.cuda.current_stream(self.device).synchronize()  # `t` and `rows` are temporaries
 
+    # -- exact scores of candidate lists -----------------------------------------------------------
+    def rescore_device(self, x, cand, k=None, normalize=False, want_all=False):
+        """Exact re-ranking of candidate lists (what faiss IndexRefineFlat does behind its base index).  cand: contiguous int64 CUDA
+        tensor [nq,kc] of row POSITIONS, kc <= IVR_MAX_K; an entry outside [0, ntotal), -1 included, is absent.  Every score has the
+        bits search() reports for that (query, row).
+          k given   (D, I) CUDA tensors [nq,k]: the best k candidates of each query in the order of search() (score descending, equal
+                    scores the lower row first, whatever their place in cand); a row named m times appears m times; (-FLT_MAX, -1)
+                    beyond the present candidates.  I holds positions.  want_all adds D_all from the same call: (D, I, D_all).
+          k None    (D_all,): float32 [nq,kc], D_all[i, j] = the score of cand[i, j], -FLT_MAX for an absent entry.
+        No host synchronisation unless x had to be staged."""
+        t, staged = _staging.queries_f32(x, self.d, self.device)
+        nq = t.shape[0]
+        _staging.check_nq(nq, "rescore")
+        if not (isinstance(cand, torch.Tensor) and cand.is_cuda and cand.device == self.device and cand.dtype == torch.int64
+                and cand.dim() == 2 and cand.shape[0] == nq and cand.is_contiguous()):
+            raise ValueError(f"rescore_device expects a contiguous int64 CUDA tensor [{nq},kc] on {self.device}")
+        kc = cand.shape[1]
+        if kc < 1 or kc > _ffi.IVR_MAX_K:
+            raise ValueError(f"rescore: kc={kc} outside [1,{_ffi.IVR_MAX_K}]")
+        D = I = D_all = None
+        if k is not None:
+            k = _staging.check_k(k, kc)
+            D, I = _staging.alloc_DI(nq, k, self.device)
+        if k is None or want_all:
+            D_all = torch.empty((nq, kc), dtype=torch.float32, device=self.device)
+        self._call("ivr_index_rescore", t, nq, cand, kc, 0 if k is None else k, bool(normalize), D_all, D, I)
+        _staging.sync_if_staged(staged, self.device)
+        if k is None:
+            return (D_all,)
+        return (D, I, D_all) if want_all else (D, I)
+
+    def compute_distance_subset(self, x, labels):
+        """faiss IndexFlat::compute_distance_subset(n, x, k, distances, labels): numpy float32 [nq,kc], entry [i, j] = the score of
+        query i against the row labels[i, j] names, with the bits search() reports.  labels: integers [nq,kc] (numpy or torch), row
+        numbers on a plain index and stored ids on an id-mapped one (the lowest row under the id, as reconstruct_batch); a label that
+        names no row gives -FLT_MAX."""
+        t = _dev_f32(_staging.as_rows(x, tensors_too=False), self.device)
+        labels = _staging.int_tensor(labels, "compute_distance_subset: labels", np_dtype=np.int64)
+        if labels.dim() != 2 or labels.shape[0] != t.shape[0] or labels.shape[1] < 1:
+            raise ValueError(f"compute_distance_subset: labels must be [{t.shape[0]},kc] with kc >= 1, got {tuple(labels.shape)}")
+        with torch.cuda.device(self.device):
+            rows = labels.to(device=self.device, dtype=torch.int64).contiguous()
+            if self.has_ids:
+                rows = self._find_device(rows.reshape(-1)).reshape(rows.shape)
+            out = self.rescore_device(t, rows)[0].cpu().numpy()       # the copy waits for the stream: t and rows may be temporaries
+        return out
+
     def write(self, start, x, normalize=False):
         """Overwrite rows [start, start+n): ring-buffer maintenance for rolling indexes."""
         t = _dev_f32(x, self.device)
