@@ -458,6 +458,37 @@ int ivr_sign_encode(ivr_ctx *ctx, const float *x /*DEV [n][d]*/, int64_t n, int 
                     const float *thr /*DEV [nbits] or NULL*/, int nbits, uint8_t *codes /*DEV [n][code_size]*/,
                     float *proj /*DEV [n][nbits] or NULL*/, ivr_stream stream);
 
+/* ---- product quantisation (faiss IndexPQ) ---------------------------------------------------------------------
+ * The reference's _create_index never builds an IndexPQ; it is here as the compressed base of the re-ranking index: a row is stored
+ * as M bytes, byte m naming one of the 256 centroids of the codebook of slice m (floats m dsub .. (m + 1) dsub of the row, dsub =
+ * d / M), and ranked by a sum of M table lookups (asymmetric inner product).  codebooks: DEV float32 [M][256][dsub].  The codes live
+ * in an ivr_bin_index of 8 M bits (ivr_bin_index_create / _add / _get_codes / _reset as they are), so one lane reads one row with
+ * 16-byte loads ("product quantisation").  1 <= M <= IVR_PQ_MAX_M and d % M == 0, IVR_ERR_INVALID otherwise. */
+#define IVR_PQ_MAX_M 128
+/* codes[i][m] = the j in [0, 256) that minimises |slice m of x[i] - codebooks[m][j]|^2, the lower j on equal distances.  The
+ * distance is evaluated in float32 as |c|^2 - 2 <x, c> (the norm of x is common to all j), each sum in ascending coordinate order:
+ * two centroids with the same bits get the same distance, and a code is within the float32 rounding of the evaluation of the true
+ * argmin (pq_encode_ref of ivr_amd/pq.py states the bound).  A slice's codebook is held in LDS for dsub <= 64; wider slices read it
+ * through the caches (slow, no limit on dsub).  x: DEV float32 [n][d], 1 <= d <= 65536; n == 0 is a no-op.  Enqueue-only. */
+int ivr_pq_encode(ivr_ctx *ctx, const float *x /*DEV [n][d]*/, int64_t n, int d, const float *codebooks /*DEV [M][256][dsub]*/, int M,
+                  uint8_t *codes /*DEV [n][M]*/, ivr_stream stream);
+/* T[i][m][j] = <slice m of q[i], codebooks[m][j]>, accumulated in float32 in ascending coordinate order from zero (no atomics: the
+ * same bits on every run).  nq >= 1.  Enqueue-only. */
+int ivr_pq_tables(ivr_ctx *ctx, const float *q /*DEV [nq][d]*/, int nq, int d, const float *codebooks /*DEV [M][256][dsub]*/, int M,
+                  float *T /*DEV [nq][M][256]*/, ivr_stream stream);
+/* Table-lookup top k over the codes of an index created with nbits = 8 M.  The score of row r for query i is
+ * (((T[i][0][c0] + T[i][1][c1]) + T[i][2][c2]) + ...), c = the code of r: plain float32 additions in ascending m, so the bits are
+ * those of the same loop on a CPU.  D / I under the contract of ivr_index_search: score descending (-0.0 counts and is reported as
+ * +0.0), equal scores the lower row first, I the row number, unused slots (k > ntotal, empty index) -FLT_MAX / -1.  Exact: the best
+ * score of every 64-row group is written, the best k groups are selected, their rows re-scored into 64-bit keys and the best k keys
+ * selected (the top k rows lie in the top k groups by (best score, lower group)).  T: DEV float32 [nq][M][256], 16-byte aligned,
+ * finite.  1 <= k <= IVR_MAX_K, nq >= 1.  A workgroup keeps the tables of 128 / M queries (1 .. 8) in LDS and reads each code word
+ * once for all of them.  Scratch per chunk of queries (at most 4096, fewer when k or the index is large): 4 bytes per (query, 64-row
+ * group) and 520 bytes per (query, selected group), grow-only.  Enqueue-only once the scratch has grown (a call that grows it
+ * allocates and cannot be captured into a hipGraph). */
+int ivr_bin_index_search_pq(ivr_bin_index *idx, const float *T /*DEV [nq][M][256]*/, int nq, int M, int k, float *D /*DEV [nq][k]*/,
+                            int64_t *I /*DEV [nq][k]*/, ivr_stream stream);
+
 /* ---- graph index (in the place of faiss IndexHNSWFlat) ------------------------------------------------------
  * Stands in for faiss.IndexHNSWFlat(dimension, 32), the IndexHNSW type of _create_index (core.py:1213-1214).  It is NOT a port of
  * faiss's HNSW: one layer of fixed out-degree (2 M, HNSW's level-0 width), built in bulk from exact kNN lists, entered through

@@ -22,32 +22,10 @@
 
 namespace {
 
-constexpr int kBinBlockRows = 256;       // rows per workgroup block: one row per lane, four 64-row groups
-constexpr int kBinMaxChunk = 64;         // queries per chunk at most
-constexpr int kBinHistLds = 48 * 1024;   // LDS of the histogram pass: (nbits + 1) bins of 4 bytes per query of a chunk
 constexpr uint64_t kBinEmpty = ~0ull;    // key of an unused result slot
 constexpr int64_t kSignEncodeSmall = 4096;   // ivr_sign_encode: up to this many rows take the latency-oriented instantiation
 
-}  // namespace
-
-struct ivr_bin_index {
-    ivr_ctx *ctx = nullptr;
-    int nbits = 0, code_size = 0, w16 = 0;
-    int64_t cap = 0, ntotal = 0;         // cap is a multiple of kBinBlockRows
-    uint4 *data = nullptr;               // [cap / 64][w16][64]
-    std::mutex mu;
-    // search workspace (grow-only)
-    DevBuf<uint4> q;                     // [nq][w16] staged queries, row-major
-    DevBuf<uint32_t> hist;               // [chunk][nbits + 1]
-    DevBuf<uint32_t> thr;                // [chunk][4]: t, need, below
-    DevBuf<uint32_t> cnt;                // [2][chunk][groups]: rows below t / at t per 64-row group, then their exclusive prefix
-    DevBuf<uint64_t> cand;               // [chunk][k]: (distance << 32 | row) of the chosen rows, kBinEmpty elsewhere
-
-    int chunk() const { return std::max(1, std::min(kBinMaxChunk, kBinHistLds / (4 * (nbits + 1)))); }
-    int64_t group_words() const { return (int64_t)w16 * 64; }
-};
-
-namespace {
+// struct ivr_bin_index, bin_load_row and bin_with_words: search_internal.h (search_pq.hip scans the same storage)
 
 int bin_words(int code_size) {
     const int w = (code_size + 15) / 16;
@@ -101,14 +79,6 @@ __global__ __launch_bounds__(256) void bin_unpack_kernel(const uint32_t *__restr
     const uint32_t x = data[((r >> 6) * w16 * 64 + (int64_t)(j >> 2) * 64 + (r & 63)) * 4 + (j & 3)];
     for (int b = 0; b < 4; ++b)
         if (4 * j + b < code_size) out[i * code_size + 4 * j + b] = (uint8_t)(x >> (8 * b));
-}
-
-// The row of this lane: row 64 g + lane of the index layout
-template <int W>
-__device__ __forceinline__ void bin_load_row(const uint4 *__restrict__ data, int64_t g, uint4 (&row)[W]) {
-    const uint4 *p = data + g * (W * 64) + (threadIdx.x & 63);
-#pragma unroll
-    for (int w = 0; w < W; ++w) row[w] = p[w * 64];
 }
 
 // Hamming distance of the lane's row to a query (q: wave-uniform address, so its words arrive through the scalar cache)
@@ -443,19 +413,6 @@ void bin_launch_pack(const ivr_bin_index *x, const uint8_t *src, uint4 *dst, int
     const int vec = x->code_size % 4 == 0 && ((uintptr_t)src & 3) == 0;
     hipLaunchKernelGGL(bin_pack_kernel, dim3((unsigned)ivr_ceil_div(threads, 256)), dim3(256), 0, s, src, dst, start, n, x->nbits, x->code_size,
                        x->w16, interleaved, vec);
-}
-
-// f(std::integral_constant<int, W>) for the index's word count
-template <typename F>
-void bin_with_words(int w16, F &&f) {
-    switch (w16) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 8: f(std::integral_constant<int, 8>{}); break;
-        default: f(std::integral_constant<int, 16>{}); break;
-    }
 }
 
 }  // namespace

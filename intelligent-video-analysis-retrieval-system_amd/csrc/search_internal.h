@@ -3,7 +3,7 @@
 // id table of an id-mapped index).  It holds what more
 // than one of them needs: the index object with the plan of a search, the view a search scans, the row mask of a filtered search, and
 // the launchers that are defined in one file and called from another.  search_rows.hip (gather / scatter of rows by position) uses it
-// too.  Not part of the C ABI.
+// too, and so do search_binary.hip and search_pq.hip for the binary-code index object at its end.  Not part of the C ABI.
 #pragma once
 #include "ivr_common.h"
 
@@ -273,3 +273,50 @@ void ivr_launch_scan_qt(ivr_index *x, const View &v, int qt, const float *qtile,
 void ivr_launch_fast_scan(ivr_index *x, const View &v, int qt, int64_t tile0, hipStream_t s);
 // search_scanq.hip
 int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s, const RowMask *mask = nullptr);
+
+// ---- binary codes (search_binary.hip) and the product-quantisation scan over the same storage (search_pq.hip) -----------------
+constexpr int kBinBlockRows = 256;       // rows per workgroup block: one row per lane, four 64-row groups
+constexpr int kBinMaxChunk = 64;         // queries per chunk at most
+constexpr int kBinHistLds = 48 * 1024;   // LDS of the histogram pass: (nbits + 1) bins of 4 bytes per query of a chunk
+
+struct ivr_bin_index {
+    ivr_ctx *ctx = nullptr;
+    int nbits = 0, code_size = 0, w16 = 0;
+    int64_t cap = 0, ntotal = 0;         // cap is a multiple of kBinBlockRows
+    uint4 *data = nullptr;               // [cap / 64][w16][64]
+    std::mutex mu;
+    // search workspace (grow-only)
+    DevBuf<uint4> q;                     // [nq][w16] staged queries, row-major
+    DevBuf<uint32_t> hist;               // [chunk][nbits + 1]
+    DevBuf<uint32_t> thr;                // [chunk][4]: t, need, below
+    DevBuf<uint32_t> cnt;                // [2][chunk][groups]: rows below t / at t per 64-row group, then their exclusive prefix
+    DevBuf<uint64_t> cand;               // [chunk][k]: (distance << 32 | row) of the chosen rows, kBinEmpty elsewhere
+    // product-quantisation scan (ivr_bin_index_search_pq, search_pq.hip), one chunk of queries; grow-only
+    DevBuf<float> pq_gmax;               // [chunk][groups rounded up to 64]: best score of each 64-row group
+    DevBuf<uint32_t> pq_sel;             // [chunk][min(k, groups)]: the selected groups, 0xFFFFFFFF = none
+    DevBuf<uint64_t> pq_keys;            // [chunk][min(k, groups) * 64]: (ordered score, ~row) of the rows of the selected groups
+
+    int chunk() const { return std::max(1, std::min(kBinMaxChunk, kBinHistLds / (4 * (nbits + 1)))); }
+    int64_t group_words() const { return (int64_t)w16 * 64; }
+};
+
+// The row of this lane: row 64 g + lane of the index layout
+template <int W>
+__device__ __forceinline__ void bin_load_row(const uint4 *__restrict__ data, int64_t g, uint4 (&row)[W]) {
+    const uint4 *p = data + g * (W * 64) + (threadIdx.x & 63);
+#pragma unroll
+    for (int w = 0; w < W; ++w) row[w] = p[w * 64];
+}
+
+// f(std::integral_constant<int, W>) for the index's word count
+template <typename F>
+void bin_with_words(int w16, F &&f) {
+    switch (w16) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        default: f(std::integral_constant<int, 16>{}); break;
+    }
+}

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("IVR_LIB") or os.path.join(os.path.dirname(_HERE), "li
 
 IVR_MAX_K = 2048
 IVR_GRAPH_MAX_EF, IVR_GRAPH_MAX_CAND, IVR_GRAPH_MAX_DEGREE = 256, 64, 64       # include/ivr_api.h
+IVR_PQ_MAX_M = 128
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -112,6 +113,9 @@ _SIGS = {
     "ivr_bin_index_get_codes": (_i, [_p, _i64, _i64, _p, _p]),
     "ivr_bin_index_search": (_i, [_p, _p, _i, _i, _p, _p, _p]),
     "ivr_sign_encode": (_i, [_p, _p, _i64, _i, _p, _p, _i, _p, _p, _p]),
+    "ivr_pq_encode": (_i, [_p, _p, _i64, _i, _p, _i, _p, _p]),
+    "ivr_pq_tables": (_i, [_p, _p, _i, _i, _p, _i, _p, _p]),
+    "ivr_bin_index_search_pq": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_graph_max_ef": (_i, []),
     "ivr_graph_max_cand": (_i, []),
     "ivr_graph_create": (_i, [_p, _i, _i, C.POINTER(_p)]),
@@ -145,7 +149,8 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_index_search_filtered", "ivr_index_range_search_filtered", "ivr_index_remove_ids", "ivr_index_add_with_ids",
     "ivr_index_get_ids", "ivr_index_find_ids", "ivr_index_gather", "ivr_index_scatter", "ivr_index_search_reconstruct",
     "ivr_index_search_lists", "ivr_segment_mean", "ivr_index_rescore", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
-    "ivr_sign_encode", "ivr_graph_set_rows", "ivr_graph_prune", "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
+    "ivr_sign_encode", "ivr_pq_encode", "ivr_pq_tables", "ivr_bin_index_search_pq", "ivr_graph_set_rows", "ivr_graph_prune",
+    "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
     "ivr_scene_keep_mask_window", "ivr_frame_quality")}
 

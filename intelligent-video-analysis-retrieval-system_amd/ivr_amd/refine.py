@@ -1,7 +1,7 @@
 """FAISS-shaped IndexRefineFlat resident in MI355X HBM: a cheap base index proposes k * k_factor candidates per query, a flat index
 over the same rows scores exactly those and returns the best k.
 
-Stands in for `faiss.IndexRefineFlat(base)`.  The base is one of the approximate indexes of this package (`IndexLSH`,
+Stands in for `faiss.IndexRefineFlat(base)`.  The base is one of the approximate indexes of this package (`IndexLSH`, `PQIndex`,
 `IVFFlatIndex`, `GraphFlatIndex`) or a plain `FlatIPIndex`; the refine index is a plain `FlatIPIndex` that receives every row the
 base receives, in the same order, so a base label is a row of the refine index (there is no add_with_ids, as in faiss).  The base's
 labels never leave the device: they go straight into `FlatIPIndex.rescore_device` (ivr_index_rescore, csrc/search_refine.hip), whose
@@ -16,6 +16,7 @@ from .binary import IndexLSH
 from .graph import GraphFlatIndex, SearchParametersHNSW
 from .index import FlatIPIndex, SearchParameters, _selector
 from .ivf import IVFFlatIndex, SearchParametersIVF
+from .pq import PQIndex
 
 _FLT_MAX = np.finfo(np.float32).max
 
@@ -57,7 +58,7 @@ def refine_order_ref(S, cand, k, ntotal=None):
 class IndexRefineSearchParameters:
     """faiss.IndexRefineSearchParameters(k_factor=..., base_index_params=...): k_factor overrides the index attribute for one call,
     base_index_params is what the base index's own search() takes as params (SearchParametersIVF, SearchParametersHNSW, or
-    SearchParameters(sel=...) for a flat base; None for IndexLSH).  A selector on the refine level is not supported: search raises
+    SearchParameters(sel=...) for a flat base; None for IndexLSH and PQIndex).  A selector on the refine level is not supported: search raises
     ValueError when sel is set."""
 
     def __init__(self, k_factor=None, base_index_params=None, sel=None):
@@ -75,9 +76,9 @@ def _check_k_factor(v, who):
 
 def _base_kwargs(base, params):
     """The keyword arguments of base.search_device that carry base_index_params."""
-    if isinstance(base, IndexLSH):
+    if isinstance(base, (IndexLSH, PQIndex)):
         if params is not None:
-            raise ValueError(f"base_index_params must be None for IndexLSH, got {type(params).__name__}")
+            raise ValueError(f"base_index_params must be None for {type(base).__name__}, got {type(params).__name__}")
         return {}
     if isinstance(base, IVFFlatIndex):
         params = typed_params(params, SearchParametersIVF, "IVFFlatIndex")
@@ -99,8 +100,8 @@ class RefineFlatIndex:
     padding.  The base must be empty when it is wrapped and receives its rows through add() of this object only."""
 
     def __init__(self, base_index, device=None):
-        if not isinstance(base_index, (IndexLSH, IVFFlatIndex, GraphFlatIndex, FlatIPIndex)):
-            raise ValueError(f"RefineFlatIndex: the base must be an IndexLSH, IVFFlatIndex, GraphFlatIndex or FlatIPIndex, "
+        if not isinstance(base_index, (IndexLSH, PQIndex, IVFFlatIndex, GraphFlatIndex, FlatIPIndex)):
+            raise ValueError(f"RefineFlatIndex: the base must be an IndexLSH, PQIndex, IVFFlatIndex, GraphFlatIndex or FlatIPIndex, "
                              f"got {type(base_index).__name__}")
         if isinstance(base_index, FlatIPIndex) and base_index.has_ids:
             raise ValueError("RefineFlatIndex: a flat base must be a plain index, this one is id-mapped")
@@ -194,6 +195,6 @@ class RefineFlatIndex:
 
 
 def IndexRefineFlat(base_index):
-    """faiss.IndexRefineFlat(base_index) drop-in: base_index is an EMPTY IndexLSH, IVFFlatIndex, GraphFlatIndex or plain FlatIPIndex
+    """faiss.IndexRefineFlat(base_index) drop-in: base_index is an EMPTY IndexLSH, PQIndex, IVFFlatIndex, GraphFlatIndex or plain FlatIPIndex
     (ValueError otherwise)."""
     return RefineFlatIndex(base_index)
