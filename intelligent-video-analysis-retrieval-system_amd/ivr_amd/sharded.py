@@ -44,7 +44,10 @@ def merge_host(D_parts, I_parts, k):
     i = I_parts.permute(1, 0, 2).reshape(nq, G * kk)
     d = torch.where(i >= 0, d, torch.full_like(d, float("-inf")))
     # stable sort on the score keeps candidate order among ties = ascending (shard, rank) = ascending id
-    order = torch.sort(d, dim=1, descending=True, stable=True).indices[:, :k]
+    order = torch.sort(d, dim=1, descending=True, stable=True).indices
+    # a candidate whose score IS -inf ties with the unused slots: a second stable pass puts every candidate before every unused slot
+    valid_first = torch.sort((torch.gather(i, 1, order) < 0).to(torch.int8), dim=1, stable=True).indices
+    order = torch.gather(order, 1, valid_first)[:, :k]
     D = torch.gather(d, 1, order)
     I = torch.gather(i, 1, order)
     D = torch.where(I >= 0, D, torch.full_like(D, NEG_FLT_MAX))

@@ -290,3 +290,76 @@ def similarity_graph(features, keys, top=10, threshold=0.7):
         order = np.argsort(sim[i])[::-1][1:top + 1]
         out[key] = [keys[j] for j in order if sim[i][j] > threshold]
     return out
+
+
+# ---- the per-query top-k selector (csrc/search_select.h) -----------------------------------------------------------------
+def select_ref(D_parts, I_parts, k):
+    """What select_topk_kernel must return for the shard-merge key sources: D_parts float32 [parts,nq,kk], I_parts int64
+    [parts,nq,kk] -> (D float32 [nq,k], I int64 [nq,k]).  Candidate position p = part * kk + j; a candidate is absent iff its
+    id is < 0.  Order: score descending (-0.0 == +0.0), then POSITION ascending - the kernel's rule; merge_shards breaks ties
+    by id, which is the same when the parts are in ascending id order, as the API requires.  Unused slots are (-FLT_MAX, -1).
+    The scores keep their bits (a -0.0 stays -0.0 here; the kernel may return it as +0.0)."""
+    D_parts = np.asarray(D_parts, dtype=np.float32)
+    I_parts = np.asarray(I_parts, dtype=np.int64)
+    parts, nq, kk = D_parts.shape
+    D = np.full((nq, k), NEG_FLT_MAX, dtype=np.float32)
+    I = np.full((nq, k), -1, dtype=np.int64)
+    for q in range(nq):
+        d = D_parts[:, q, :].reshape(-1)
+        i = I_parts[:, q, :].reshape(-1)
+        p = np.nonzero(i >= 0)[0]
+        order = p[np.lexsort((p, -d[p].astype(np.float64)))][:k]
+        D[q, :len(order)] = d[order]
+        I[q, :len(order)] = i[order]
+    return D, I
+
+
+# the constants of search_select.h that select_path copies (tests/test_select_ref_cpu.py parses the header against them)
+SEL_THREADS = 1024          # kSelThreads
+SEL_SHORT_THREADS = 256     # sel_threads: n <= SEL_REG_KEYS * 256 keys run with 256 threads
+SEL_REG_KEYS = 16           # kRegKeys: keys cached per thread
+SEL_FAST_ROUNDS = 16        # survivor path: ceil(keff / waves) <= 16
+SEL_EXTRACT_KEFF = 64       # extraction path: keff <= 64 (and the keys cached)
+
+
+def select_ord(scores):
+    """ivr_f2ord: float32 scores -> uint32 whose unsigned order is the scores' order (-0.0 folded onto +0.0)."""
+    u = (np.asarray(scores, dtype=np.float32) + np.float32(0.0)).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def select_path(scores, valid, k):
+    """MODEL of the code under test, never a source of expected results: which of select_topk_kernel's branches the key list of
+    one query takes.  scores float32 [n], valid bool [n] (key i = 0 where not valid), key i lives in thread i % blockDim.
+    Returns (path, block_threads, cached); path is `fast`, or `<extract|radix>/<why the survivor path was left>` with
+    short = a wave ran out of keys (T == 0), ties = more than blockDim keys survive, bigk = more than 16 rounds, empty = no
+    valid key.  A line-for-line restatement of the kernel's dispatch: change the two together."""
+    scores = np.asarray(scores, dtype=np.float32)
+    valid = np.asarray(valid, dtype=bool)
+    n = scores.shape[0]
+    nthr = SEL_SHORT_THREADS if n <= SEL_REG_KEYS * SEL_SHORT_THREADS else SEL_THREADS        # sel_threads
+    cached = n <= SEL_REG_KEYS * nthr
+    hi = np.where(valid, select_ord(scores), np.uint32(0)).astype(np.uint32)                 # the score word of every key
+    keff = min(int(k), int(valid.sum()))
+    nwv = nthr // 64
+    rounds = (keff + nwv - 1) // nwv
+    if keff >= 1 and rounds <= SEL_FAST_ROUNDS:
+        pad = np.zeros((-n) % nthr, dtype=np.uint32)
+        cur = np.concatenate([hi, pad]).reshape(-1, nthr).max(axis=0).reshape(nwv, 64)       # per-thread maxima, by wave
+        last = np.zeros(nwv, dtype=np.uint32)
+        for _ in range(rounds):
+            last = cur.max(axis=1)
+            cur[cur == last[:, None]] = 0
+        T = int(last.min())
+        if T != 0:
+            ns = int((valid & (hi >= T)).sum())
+            if ns <= nthr:
+                return "fast", nthr, cached
+            why = "ties"
+        else:
+            why = "short"
+    else:
+        why = "empty" if keff == 0 else "bigk"
+    if cached and keff <= SEL_EXTRACT_KEFF:
+        return "extract/" + why, nthr, cached
+    return "radix/" + why, nthr, cached
