@@ -489,6 +489,48 @@ int ivr_pq_tables(ivr_ctx *ctx, const float *q /*DEV [nq][d]*/, int nq, int d, c
 int ivr_bin_index_search_pq(ivr_bin_index *idx, const float *T /*DEV [nq][M][256]*/, int nq, int M, int k, float *D /*DEV [nq][k]*/,
                             int64_t *I /*DEV [nq][k]*/, ivr_stream stream);
 
+/* ---- scalar quantisation (faiss IndexScalarQuantizer, QT_8bit, inner product) ------------------------------------
+ * The reference's _create_index never builds an IndexScalarQuantizer; it is here as the compressed base between the flat index and
+ * the 32 - 64 byte codes: a row is stored as d bytes, byte j = the bucket of coordinate j between vmin[j] and vmin[j] + vdiff[j], and
+ * ranked by an exact integer inner product on the int8 MFMA ("scalar quantisation"; the definitions are the
+ * numpy functions sq_encode_ref, sq_query_ref and sq_scan_ref of ivr_amd/sq.py).  1 <= d <= 1024, IVR_ERR_INVALID otherwise: the
+ * bound keeps 16256 * 128 * d inside the int32 accumulator. */
+/* codes[i][j] = min(255, int(255 * xi)), xi = clamp((x[i][j] - vmin[j]) / vdiff[j], 0, 1) and 0 where vdiff[j] == 0: faiss's
+ * Codec8bit, every operation one float32 rounding (correctly rounded division, no fused multiply-add), truncating.  x must be
+ * finite: what a NaN encodes to is unspecified.  n == 0 is a no-op.  Enqueue-only. */
+int ivr_sq_encode(ivr_ctx *ctx, const float *x /*DEV [n][d]*/, int64_t n, int d, const float *vmin /*DEV [d]*/,
+                  const float *vdiff /*DEV [d]*/, uint8_t *codes /*DEV [n][d]*/, ivr_stream stream);
+/* The integer form of a batch of queries.  With w[j] = q[j] * gain[j] and m = max |w[j]|: scale = m / 16256 (1 when m == 0),
+ * t[j] = clamp(rint(w[j] / scale), -16256, 16256) (float32 division, rounding half to even), bias = sum q[j] * offset[j] in float32
+ * (within (d + 2) 2^-24 sum |q[j] offset[j]| of the exact sum).  t and scale carry the bits of sq_query_ref.  q must be finite.
+ * nq >= 1.  Enqueue-only. */
+int ivr_sq_query(ivr_ctx *ctx, const float *q /*DEV [nq][d]*/, int nq, int d, const float *gain /*DEV [d]*/,
+                 const float *offset /*DEV [d]*/, int16_t *t /*DEV [nq][d]*/, float *scale /*DEV [nq]*/, float *bias /*DEV [nq]*/,
+                 ivr_stream stream);
+/* The stored codes: signed c' = code - 128, K padded with zeros to a multiple of 64, tiled per 16 rows so that one wave-wide 16-byte
+ * load is 1 KiB contiguous and is the A operand of one v_mfma_i32_16x16x64_i8.  Rows are allocated by the first add, in whole 64-row
+ * groups; capacity below 2^31 rows. */
+typedef struct ivr_sq_index ivr_sq_index;
+int ivr_sq_index_create(ivr_ctx *ctx, int d, ivr_sq_index **out);
+int ivr_sq_index_destroy(ivr_sq_index *idx);                /* IVR_ERR_INVALID for NULL, as every entry of this section */
+int ivr_sq_index_reset(ivr_sq_index *idx);                  /* ntotal = 0; the bytes stay and are never read as rows */
+int64_t ivr_sq_index_ntotal(ivr_sq_index *idx);             /* -1 for NULL */
+/* append n codes as ivr_sq_encode makes them (unsigned); writes the new rows only */
+int ivr_sq_index_add(ivr_sq_index *idx, const uint8_t *codes /*DEV [n][d]*/, int64_t n, ivr_stream stream);
+/* codes of rows [start, start + n) as they were added; start + n <= ntotal */
+int ivr_sq_index_get_codes(ivr_sq_index *idx, int64_t start, int64_t n, uint8_t *out /*DEV [n][d]*/, ivr_stream stream);
+/* Integer top k.  acc of row r for query i = sum_j t[i][j] * c'[r][j], exact in int32 (t as ivr_sq_query makes it; a |t| beyond 16256
+ * is clamped to it).  Rows are ranked by (acc descending, row ascending): integers only.  D = float(acc) * scale[i] + bias[i]: one
+ * conversion to nearest-even, one float32 multiplication, one float32 addition; I the row number; unused slots (k > ntotal, empty
+ * index) -FLT_MAX / -1.  Exact: the best acc of every 64-row group is written, the best k groups are selected, their rows re-scored
+ * into 64-bit keys (acc ^ 0x80000000) << 32 | ~row and the best k keys selected.  1 <= k <= IVR_MAX_K, nq >= 1.  The index is read
+ * once per 32 queries.  Scratch: 2 ceil(d / 64) 64 bytes per query, and per chunk of queries (at most 4096, fewer when k or the
+ * index is large) 4 bytes per (query, 64-row group) and 520 bytes per (query, selected group), grow-only.  Enqueue-only once the
+ * scratch has grown (a call that grows it allocates and cannot be captured into a hipGraph). */
+int ivr_sq_index_search(ivr_sq_index *idx, const int16_t *t /*DEV [nq][d]*/, const float *scale /*DEV [nq]*/,
+                        const float *bias /*DEV [nq]*/, int nq, int k, float *D /*DEV [nq][k]*/, int64_t *I /*DEV [nq][k]*/,
+                        ivr_stream stream);
+
 /* ---- graph index (in the place of faiss IndexHNSWFlat) ------------------------------------------------------
  * Stands in for faiss.IndexHNSWFlat(dimension, 32), the IndexHNSW type of _create_index (core.py:1213-1214).  It is NOT a port of
  * faiss's HNSW: one layer of fixed out-degree (2 M, HNSW's level-0 width), built in bulk from exact kNN lists, entered through

@@ -2,7 +2,7 @@
 over the same rows scores exactly those and returns the best k.
 
 Stands in for `faiss.IndexRefineFlat(base)`.  The base is one of the approximate indexes of this package (`IndexLSH`, `PQIndex`,
-`IVFFlatIndex`, `GraphFlatIndex`) or a plain `FlatIPIndex`; the refine index is a plain `FlatIPIndex` that receives every row the
+`SQIndex`, `IVFFlatIndex`, `GraphFlatIndex`) or a plain `FlatIPIndex`; the refine index is a plain `FlatIPIndex` that receives every row the
 base receives, in the same order, so a base label is a row of the refine index (there is no add_with_ids, as in faiss).  The base's
 labels never leave the device: they go straight into `FlatIPIndex.rescore_device` (ivr_index_rescore, csrc/search_refine.hip), whose
 scores carry the bits of `FlatIPIndex.search` and whose ordering is pinned to `refine_order_ref` below.
@@ -17,6 +17,7 @@ from .graph import GraphFlatIndex, SearchParametersHNSW
 from .index import FlatIPIndex, SearchParameters, _selector
 from .ivf import IVFFlatIndex, SearchParametersIVF
 from .pq import PQIndex
+from .sq import SQIndex
 
 _FLT_MAX = np.finfo(np.float32).max
 
@@ -58,7 +59,7 @@ def refine_order_ref(S, cand, k, ntotal=None):
 class IndexRefineSearchParameters:
     """faiss.IndexRefineSearchParameters(k_factor=..., base_index_params=...): k_factor overrides the index attribute for one call,
     base_index_params is what the base index's own search() takes as params (SearchParametersIVF, SearchParametersHNSW, or
-    SearchParameters(sel=...) for a flat base; None for IndexLSH and PQIndex).  A selector on the refine level is not supported: search raises
+    SearchParameters(sel=...) for a flat base; None for IndexLSH, PQIndex and SQIndex).  A selector on the refine level is not supported: search raises
     ValueError when sel is set."""
 
     def __init__(self, k_factor=None, base_index_params=None, sel=None):
@@ -76,7 +77,7 @@ def _check_k_factor(v, who):
 
 def _base_kwargs(base, params):
     """The keyword arguments of base.search_device that carry base_index_params."""
-    if isinstance(base, (IndexLSH, PQIndex)):
+    if isinstance(base, (IndexLSH, PQIndex, SQIndex)):
         if params is not None:
             raise ValueError(f"base_index_params must be None for {type(base).__name__}, got {type(params).__name__}")
         return {}
@@ -100,8 +101,8 @@ class RefineFlatIndex:
     padding.  The base must be empty when it is wrapped and receives its rows through add() of this object only."""
 
     def __init__(self, base_index, device=None):
-        if not isinstance(base_index, (IndexLSH, PQIndex, IVFFlatIndex, GraphFlatIndex, FlatIPIndex)):
-            raise ValueError(f"RefineFlatIndex: the base must be an IndexLSH, PQIndex, IVFFlatIndex, GraphFlatIndex or FlatIPIndex, "
+        if not isinstance(base_index, (IndexLSH, PQIndex, SQIndex, IVFFlatIndex, GraphFlatIndex, FlatIPIndex)):
+            raise ValueError(f"RefineFlatIndex: the base must be an IndexLSH, PQIndex, SQIndex, IVFFlatIndex, GraphFlatIndex or FlatIPIndex, "
                              f"got {type(base_index).__name__}")
         if isinstance(base_index, FlatIPIndex) and base_index.has_ids:
             raise ValueError("RefineFlatIndex: a flat base must be a plain index, this one is id-mapped")
@@ -195,6 +196,6 @@ class RefineFlatIndex:
 
 
 def IndexRefineFlat(base_index):
-    """faiss.IndexRefineFlat(base_index) drop-in: base_index is an EMPTY IndexLSH, PQIndex, IVFFlatIndex, GraphFlatIndex or plain FlatIPIndex
+    """faiss.IndexRefineFlat(base_index) drop-in: base_index is an EMPTY IndexLSH, PQIndex, SQIndex, IVFFlatIndex, GraphFlatIndex or plain FlatIPIndex
     (ValueError otherwise)."""
     return RefineFlatIndex(base_index)
