@@ -392,22 +392,6 @@ __global__ __launch_bounds__(256) void sign_encode_plain_kernel(const float *__r
     if (lane < 8 && j0 / 8 + lane < code_size) codes[i * code_size + j0 / 8 + lane] = (uint8_t)(code >> (8 * lane));
 }
 
-int bin_alloc(ivr_bin_index *x, int64_t rows) {
-    rows = ivr_round_up(std::max<int64_t>(rows, kBinBlockRows), kBinBlockRows);
-    const size_t bytes = (size_t)(rows / 64) * x->group_words() * sizeof(uint4);
-    uint4 *nd = nullptr;
-    IVR_HIP(hipMalloc(&nd, bytes));
-    IVR_HIP(hipMemset(nd, 0, bytes));
-    if (x->data) {
-        if (x->ntotal > 0)
-            IVR_HIP(hipMemcpy(nd, x->data, (size_t)ivr_ceil_div(x->ntotal, 64) * x->group_words() * sizeof(uint4), hipMemcpyDeviceToDevice));
-        IVR_HIP(hipFree(x->data));
-    }
-    x->data = nd;
-    x->cap = rows;
-    return IVR_OK;
-}
-
 void bin_launch_pack(const ivr_bin_index *x, const uint8_t *src, uint4 *dst, int64_t start, int64_t n, int interleaved, hipStream_t s) {
     const int64_t threads = ivr_ceil_div(n, 64) * x->w16 * 64;
     const int vec = x->code_size % 4 == 0 && ((uintptr_t)src & 3) == 0;
@@ -416,6 +400,37 @@ void bin_launch_pack(const ivr_bin_index *x, const uint8_t *src, uint4 *dst, int
 }
 
 }  // namespace
+
+// ---- what the coded indexes share (search_internal.h) -----------------------------------------------------------------------------
+int CodeRows::grow(int64_t rows) {
+    rows = ivr_round_up(std::max<int64_t>(rows, granule), granule);
+    uint4 *nd = nullptr;
+    IVR_HIP(hipMalloc(&nd, bytes(rows)));
+    IVR_HIP(hipMemset(nd, 0, bytes(rows)));
+    if (data) {
+        if (ntotal > 0) IVR_HIP(hipMemcpy(nd, data, bytes(ntotal), hipMemcpyDeviceToDevice));
+        IVR_HIP(hipFree(data));
+    }
+    data = nd;
+    cap = rows;
+    return IVR_OK;
+}
+
+int CodeRows::reserve_for_add(int64_t n, const char *what) {
+    if (ntotal + n <= cap) return IVR_OK;
+    IVR_REQUIRE(ntotal + n < (1ll << 31) - granule, "%s: index would exceed 2^31 rows", what);
+    IVR_HIP(hipDeviceSynchronize());
+    return grow(std::max<int64_t>(ntotal + n, cap + cap / 2));
+}
+
+int GroupTopK::plan(int nq, int k, int64_t ngroups, int pass, int64_t &mstride, int &ksel, int &qc) {
+    mstride = ivr_round_up(ngroups, 64);
+    ksel = (int)std::min<int64_t>(k, ngroups);
+    const int64_t fit = std::min<int64_t>({(int64_t)kMaxChunk, kChunkKeys / ((int64_t)ksel * 64), kChunkKeys / mstride});
+    qc = (int)std::min<int64_t>(nq, std::max<int64_t>(pass, fit / pass * pass));
+    return ivr_reserve({{&gmax, (size_t)qc * mstride * 4}, {&sel, (size_t)qc * ksel * sizeof(uint32_t)},
+                        {&keys, (size_t)qc * ksel * 64 * sizeof(uint64_t)}});
+}
 
 extern "C" {
 
@@ -432,7 +447,9 @@ int ivr_bin_index_create(ivr_ctx *ctx, int nbits, int64_t capacity_rows, ivr_bin
     x->nbits = nbits;
     x->code_size = (nbits + 7) / 8;
     x->w16 = bin_words(x->code_size);
-    const int rc = bin_alloc(x, capacity_rows);
+    x->granule = kBinBlockRows;
+    x->group_words = (int64_t)x->w16 * 64;
+    const int rc = x->grow(capacity_rows);
     if (rc != IVR_OK) {
         delete x;
         return rc;
@@ -442,9 +459,7 @@ int ivr_bin_index_create(ivr_ctx *ctx, int nbits, int64_t capacity_rows, ivr_bin
 }
 
 int ivr_bin_index_destroy(ivr_bin_index *x) {
-    if (!x) return IVR_OK;
-    if (x->data) (void)hipFree(x->data);
-    delete x;                        // the workspace buffers free themselves
+    delete x;                        // the rows and the workspace buffers free themselves
     return IVR_OK;
 }
 
@@ -453,7 +468,7 @@ int ivr_bin_index_reset(ivr_bin_index *x) {
     std::lock_guard<std::mutex> lk(x->mu);
     IVR_HIP(hipSetDevice(x->ctx->device));
     IVR_HIP(hipDeviceSynchronize());             // a search in flight still reads the rows
-    IVR_HIP(hipMemset(x->data, 0, (size_t)(x->cap / 64) * x->group_words() * sizeof(uint4)));
+    IVR_HIP(hipMemset(x->data, 0, x->bytes(x->cap)));
     x->ntotal = 0;
     return IVR_OK;
 }
@@ -466,12 +481,7 @@ int ivr_bin_index_add(ivr_bin_index *x, const uint8_t *codes, int64_t n, ivr_str
     std::lock_guard<std::mutex> lk(x->mu);
     if (n == 0) return IVR_OK;
     IVR_HIP(hipSetDevice(x->ctx->device));
-    if (x->ntotal + n > x->cap) {
-        IVR_REQUIRE(x->ntotal + n < (1ll << 31) - kBinBlockRows, "ivr_bin_index_add: index would exceed 2^31 rows");
-        IVR_HIP(hipDeviceSynchronize());         // growing re-allocates: wait for work that may still read the old buffer
-        const int rc = bin_alloc(x, std::max<int64_t>(x->ntotal + n, x->cap + x->cap / 2));
-        if (rc != IVR_OK) return rc;
-    }
+    if (int rc = x->reserve_for_add(n, "ivr_bin_index_add")) return rc;
     bin_launch_pack(x, codes, x->data, x->ntotal, n, 1, (hipStream_t)stream);
     IVR_LAUNCH_CHECK();
     x->ntotal += n;
@@ -523,7 +533,7 @@ int ivr_bin_index_search(ivr_bin_index *x, const uint8_t *qcodes, int nq, int k,
         IVR_HIP(hipMemsetAsync(x->cand, 0xff, (size_t)nqc * k * sizeof(uint64_t), s));
         if (ntotal > 0) {
             IVR_HIP(hipMemsetAsync(x->hist, 0, (size_t)nqc * nbins * sizeof(uint32_t), s));
-            const double scan_bytes = (double)ngroups * x->group_words() * 16;
+            const double scan_bytes = (double)ngroups * x->group_words * 16;
             bin_with_words(x->w16, [&](auto w) {
                 constexpr int W = decltype(w)::value;
                 {

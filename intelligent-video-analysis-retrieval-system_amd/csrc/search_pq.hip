@@ -20,7 +20,7 @@
 //   select      select_topk_kernel over the keys -> D, I
 // The lookups are gathers of 4 bytes at random columns of a 1 KiB table row: a wave's 64 addresses fall on the 32 banks of ds_read_b32
 // as they come, which no layout of a table can change, and the scan is bound by them, not by the code stream.
-// Scratch (grow-only, on the index object): 4 bytes per (query, group) and 520 per (query, selected group) of a chunk.
+// Scratch (grow-only, the GroupTopK of the index object): 4 bytes per (query, group) and 520 per (query, selected group) of a chunk.
 #include "ivr_common.h"
 #include "search_internal.h"
 #include "search_select.h"
@@ -35,9 +35,6 @@ constexpr int kPqScanThreads = 512;          // the scan's workgroup: 8 waves sh
 constexpr int pq_scan_rows(int W) { return W <= 4 ? 2 : 1; }
 constexpr int kPqTableLds = 128 * 1024;      // LDS a workgroup spends on tables at most: 128 / M queries of M KiB each
 constexpr int kPqMaxGroupQ = 8;              // queries of a group at most (their scores are live at once)
-constexpr int kPqMaxChunk = 4096;            // queries per chunk at most
-constexpr int64_t kPqChunkKeys = 1ll << 25;  // keys (8 bytes) and group maxima (4 bytes) of a chunk: 256 + 128 MiB at most,
-                                             // or one query's when that is more
 constexpr int kPqEncodeMaxReg = 64;          // widest slice the encoder keeps in registers and its codebook in LDS
 constexpr int kPqTabQ = 8;                   // queries per thread of the table builder
 
@@ -343,13 +340,11 @@ int ivr_bin_index_search_pq(ivr_bin_index *x, const float *T, int nq, int M, int
         IVR_LAUNCH_CHECK();
         return IVR_OK;
     }
-    const int64_t mstride = ivr_round_up(ngroups, 64);
-    const int ksel = (int)std::min<int64_t>(k, ngroups);
-    const int qc = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nq, (int64_t)kPqMaxChunk, kPqChunkKeys / ((int64_t)ksel * 64), kPqChunkKeys / mstride}));
-    int rc = ivr_reserve({{&x->pq_gmax, (size_t)qc * mstride * sizeof(float)},
-                          {&x->pq_sel, (size_t)qc * ksel * sizeof(uint32_t)},
-                          {&x->pq_keys, (size_t)qc * ksel * 64 * sizeof(uint64_t)}});
+    int64_t mstride;
+    int ksel, qc;
+    int rc = x->pq.plan(nq, k, ngroups, 1, mstride, ksel, qc);       // the scan takes any number of queries: a pass is one
     if (rc != IVR_OK) return rc;
+    float *gmax = static_cast<float *>(x->pq.gmax.ptr);
     const int tab = M * kPqKsub;
     const int qg_max = std::max(1, std::min(kPqMaxGroupQ, kPqTableLds / (tab * (int)sizeof(float))));
     bin_with_words(x->w16, [&](auto w) {
@@ -373,21 +368,21 @@ int ivr_bin_index_search_pq(ivr_bin_index *x, const float *T, int nq, int M, int
             {
                 IvrProf prof("pq_scan", s, (double)nqc * ntotal * M);
                 hipLaunchKernelGGL((pq_scan_kernel<WS, R>), dim3(gx, (unsigned)ivr_ceil_div(nqc, qg)), dim3(kPqScanThreads), lds, s, x->data, ntotal, ngroups,
-                                   Tc, nqc, qg, M, (float *)x->pq_gmax, mstride);
+                                   Tc, nqc, qg, M, gmax, mstride);
             }
             {
                 IvrProf prof("pq_select_groups", s, (double)nqc * ngroups * 4, true);
-                launch_select<OUT_GROUPS>(SrcPqGroups{x->pq_gmax, mstride, ngroups}, nqc, ksel, SelectOut::to_groups(x->pq_sel), s);
+                launch_select<OUT_GROUPS>(SrcPqGroups{gmax, mstride, ngroups}, nqc, ksel, SelectOut::to_groups(x->pq.sel), s);
             }
             {
                 const int64_t npairs = (int64_t)nqc * ksel;
                 IvrProf prof("pq_keys", s, (double)npairs * 64 * M, true);
                 hipLaunchKernelGGL(pq_keys_kernel<WS>, dim3((unsigned)ivr_ceil_div(npairs, 4)), dim3(256), 0, s, x->data, ntotal, ngroups, Tc, M,
-                                   (const uint32_t *)x->pq_sel, ksel, npairs, (uint64_t *)x->pq_keys);
+                                   (const uint32_t *)x->pq.sel, ksel, npairs, (uint64_t *)x->pq.keys);
             }
             {
                 IvrProf prof("pq_select_rows", s, (double)nqc * ksel * 64 * 8, true);
-                launch_select<OUT_DI>(SrcPqKeys{x->pq_keys, (int64_t)ksel * 64}, nqc, k, SelectOut::to_rows(D + (int64_t)c0 * k, I + (int64_t)c0 * k), s);
+                launch_select<OUT_DI>(SrcPqKeys{x->pq.keys, (int64_t)ksel * 64}, nqc, k, SelectOut::to_rows(D + (int64_t)c0 * k, I + (int64_t)c0 * k), s);
             }
             if (hipGetLastError() != hipSuccess) rc = ivr_fail(IVR_ERR_HIP, "ivr_bin_index_search_pq: launch failed");
         }

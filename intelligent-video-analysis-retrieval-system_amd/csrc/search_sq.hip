@@ -20,8 +20,8 @@
 //   select      select_topk_kernel over the keys -> I, and in D the key's high word as select_topk_kernel hands every score back
 //               (ivr_ord2f, a bijection of 32-bit patterns)
 //   sq_finish   D = float(acc) * scale + bias from that word: one conversion, one multiplication, one addition
-// Scratch (grow-only, on the index object): both halves of the staged queries, 4 bytes per (query, group) and 520 per (query,
-// selected group) of a chunk.
+// Scratch (grow-only, on the index object): both halves of the staged queries and, in its GroupTopK, 4 bytes per (query, group) and
+// 520 per (query, selected group) of a chunk.
 #include "ivr_common.h"
 #include "search_internal.h"
 #include "search_select.h"
@@ -29,17 +29,11 @@
 #include <cfloat>
 #include <climits>
 
-struct ivr_sq_index {
-    ivr_ctx *ctx = nullptr;
+struct ivr_sq_index : CodeRows {         // data: [cap / 16][ksteps][64], group_words = 4 tile_words()
     int d = 0, ksteps = 0;
-    int64_t cap = 0, ntotal = 0;         // cap is a multiple of 64
-    uint4 *data = nullptr;               // [cap / 16][ksteps][64]
-    std::mutex mu;
     // search workspace (grow-only)
     DevBuf<uint4> qh, ql;                // [query tiles, a multiple of kSqQT][ksteps][64]: the two halves of the staged queries
-    DevBuf<int32_t> gmax;                // [chunk][groups rounded up to 64]: best acc of each 64-row group
-    DevBuf<uint32_t> sel;                // [chunk][min(k, groups)]: the selected groups, 0xFFFFFFFF = none
-    DevBuf<uint64_t> keys;               // [chunk][min(k, groups) * 64]: the keys of the rows of the selected groups
+    GroupTopK topk;                      // int32 maxima: best acc of each 64-row group
 
     int64_t tile_words() const { return (int64_t)ksteps * 64; }      // 16-byte words of one 16-row (or 16-query) tile
 };
@@ -52,9 +46,6 @@ constexpr int kSqMaxD = 1024;                // 16256 * 128 * d fits int32 up to
 constexpr float kSqTMax = 16256.f;           // 127 * 128: the largest |t|
 constexpr int kSqQT = 2;                     // 16-query tiles per index pass: 32 queries
 constexpr int kSqThreads = 256;              // the scan's workgroup: 4 waves share one LDS image of the queries
-constexpr int kSqMaxChunk = 4096;            // queries per chunk at most
-constexpr int64_t kSqChunkKeys = 1ll << 25;  // keys (8 bytes) and group maxima (4 bytes) of a chunk: 256 + 128 MiB at most, or one
-                                             // pass's when that is more
 
 // the keys of the two selections: instantiations of select_topk_kernel of this file's own (search_select.h)
 struct SrcSqGroups {   // the group maxima of query q
@@ -321,22 +312,6 @@ __global__ __launch_bounds__(256) void sq_query_kernel(const float *__restrict__
     }
 }
 
-int sq_alloc(ivr_sq_index *x, int64_t rows) {
-    rows = ivr_round_up(std::max<int64_t>(rows, 64), 64);
-    const size_t bytes = (size_t)(rows / 16) * x->tile_words() * sizeof(uint4);
-    uint4 *nd = nullptr;
-    IVR_HIP(hipMalloc(&nd, bytes));
-    IVR_HIP(hipMemset(nd, 0, bytes));
-    if (x->data) {
-        if (x->ntotal > 0)
-            IVR_HIP(hipMemcpy(nd, x->data, (size_t)ivr_ceil_div(x->ntotal, 16) * x->tile_words() * sizeof(uint4), hipMemcpyDeviceToDevice));
-        IVR_HIP(hipFree(x->data));
-    }
-    x->data = nd;
-    x->cap = rows;
-    return IVR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -376,14 +351,15 @@ int ivr_sq_index_create(ivr_ctx *ctx, int d, ivr_sq_index **out) {
     x->ctx = ctx;
     x->d = d;
     x->ksteps = (d + 63) / 64;
+    x->granule = 64;
+    x->group_words = 4 * x->tile_words();
     *out = x;
     return IVR_OK;
 }
 
 int ivr_sq_index_destroy(ivr_sq_index *x) {
     IVR_REQUIRE(x, "ivr_sq_index_destroy: NULL index");
-    if (x->data) (void)hipFree(x->data);
-    delete x;                                // the workspace buffers free themselves
+    delete x;                                // the rows and the workspace buffers free themselves
     return IVR_OK;
 }
 
@@ -408,12 +384,7 @@ int ivr_sq_index_add(ivr_sq_index *x, const uint8_t *codes, int64_t n, ivr_strea
     std::lock_guard<std::mutex> lk(x->mu);
     if (n == 0) return IVR_OK;
     IVR_HIP(hipSetDevice(x->ctx->device));
-    if (x->ntotal + n > x->cap) {
-        IVR_REQUIRE(x->ntotal + n < (1ll << 31) - 64, "ivr_sq_index_add: index would exceed 2^31 rows");
-        IVR_HIP(hipDeviceSynchronize());     // growing re-allocates: wait for work that may still read the old buffer
-        const int rc = sq_alloc(x, std::max<int64_t>(x->ntotal + n, x->cap + x->cap / 2));
-        if (rc != IVR_OK) return rc;
-    }
+    if (int rc = x->reserve_for_add(n, "ivr_sq_index_add")) return rc;
     const int64_t words = n * x->ksteps * 4;
     const int vec = x->d % 16 == 0 && ((uintptr_t)codes & 15) == 0;
     hipLaunchKernelGGL(sq_pack_kernel, dim3((unsigned)ivr_ceil_div(words, 256)), dim3(256), 0, (hipStream_t)stream, codes, x->data, x->ntotal, n,
@@ -453,17 +424,13 @@ int ivr_sq_index_search(ivr_sq_index *x, const int16_t *t, const float *scale, c
         return IVR_OK;
     }
     constexpr int kPass = 16 * kSqQT;        // queries of one index pass
-    const int64_t mstride = ivr_round_up(ngroups, 64);
-    const int ksel = (int)std::min<int64_t>(k, ngroups);
-    // queries per chunk: whole passes, at least one
-    const int64_t fit = std::min<int64_t>({(int64_t)kSqMaxChunk, kSqChunkKeys / ((int64_t)ksel * 64), kSqChunkKeys / mstride});
-    const int qc = (int)std::min<int64_t>(nq, std::max<int64_t>(kPass, fit / kPass * kPass));
+    int64_t mstride;
+    int ksel, qc;
+    int rc = x->topk.plan(nq, k, ngroups, kPass, mstride, ksel, qc);
+    if (rc != IVR_OK) return rc;
+    int32_t *gmax = static_cast<int32_t *>(x->topk.gmax.ptr);
     const int64_t tw = x->tile_words(), qtiles = ivr_round_up(ivr_ceil_div(nq, 16), kSqQT);
-    int rc = ivr_reserve({{&x->qh, (size_t)(qtiles * tw) * sizeof(uint4)},
-                          {&x->ql, (size_t)(qtiles * tw) * sizeof(uint4)},
-                          {&x->gmax, (size_t)qc * mstride * sizeof(int32_t)},
-                          {&x->sel, (size_t)qc * ksel * sizeof(uint32_t)},
-                          {&x->keys, (size_t)qc * ksel * 64 * sizeof(uint64_t)}});
+    rc = ivr_reserve({{&x->qh, (size_t)(qtiles * tw) * sizeof(uint4)}, {&x->ql, (size_t)(qtiles * tw) * sizeof(uint4)}});
     if (rc != IVR_OK) return rc;
     const size_t lds = (size_t)2 * kSqQT * tw * sizeof(uint4);           // 4 KiB per K step: 64 KiB at d = 1024
     rc = ivr_func_max_lds(reinterpret_cast<const void *>(sq_scan_kernel), (int)lds);
@@ -483,24 +450,24 @@ int ivr_sq_index_search(ivr_sq_index *x, const int16_t *t, const float *scale, c
             1, std::min<int64_t>(ivr_ceil_div(ngroups, kSqThreads / 64), ivr_ceil_div(per_cu * x->ctx->cu_count, passes)));
         {
             IvrProf prof("sq_scan", s, (double)passes * ngroups * 4 * tw * 16);
-            hipLaunchKernelGGL(sq_scan_kernel, dim3(gx, passes), dim3(kSqThreads), lds, s, x->data, ntotal, ngroups, x->ksteps, qh, ql, nqc,
-                               (int32_t *)x->gmax, mstride);
+            hipLaunchKernelGGL(sq_scan_kernel, dim3(gx, passes), dim3(kSqThreads), lds, s, x->data, ntotal, ngroups, x->ksteps, qh, ql, nqc, gmax,
+                               mstride);
         }
         {
             IvrProf prof("sq_select_groups", s, (double)nqc * ngroups * 4, true);
-            launch_select<OUT_GROUPS>(SrcSqGroups{x->gmax, mstride, ngroups}, nqc, ksel, SelectOut::to_groups(x->sel), s);
+            launch_select<OUT_GROUPS>(SrcSqGroups{gmax, mstride, ngroups}, nqc, ksel, SelectOut::to_groups(x->topk.sel), s);
         }
         const int64_t npairs = (int64_t)nqc * ksel;
         {
             IvrProf prof("sq_keys", s, (double)npairs * 4 * tw * 16, true);
             hipLaunchKernelGGL(sq_keys_kernel, dim3((unsigned)ivr_ceil_div(npairs, 4)), dim3(256), 0, s, x->data, ntotal, ngroups, x->ksteps, qh, ql,
-                               (const uint32_t *)x->sel, ksel, npairs, (uint64_t *)x->keys);
+                               (const uint32_t *)x->topk.sel, ksel, npairs, (uint64_t *)x->topk.keys);
         }
         float *Dc = D + (int64_t)c0 * k;
         int64_t *Ic = I + (int64_t)c0 * k;
         {
             IvrProf prof("sq_select_rows", s, (double)nqc * ksel * 64 * 8, true);
-            launch_select<OUT_DI>(SrcSqKeys{x->keys, (int64_t)ksel * 64}, nqc, k, SelectOut::to_rows(Dc, Ic), s);
+            launch_select<OUT_DI>(SrcSqKeys{x->topk.keys, (int64_t)ksel * 64}, nqc, k, SelectOut::to_rows(Dc, Ic), s);
         }
         {
             const int64_t n = (int64_t)nqc * k;

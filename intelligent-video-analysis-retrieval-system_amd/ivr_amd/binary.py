@@ -17,10 +17,9 @@ import numpy as np
 import torch
 
 from . import _ffi, _staging
+from ._coded import CodedIndex, cat_chunks
 from ._faiss import METRIC_L2, search_numpy
-from ._staging import dev_f32 as _dev_f32, dev_u8 as _dev_u8
-
-_ENCODE_CHUNK = 1 << 18       # rows of a host array staged per encoder launch
+from ._staging import dev_u8 as _dev_u8
 
 
 def lsh_rotation(d, nbits, seed=5):
@@ -105,7 +104,7 @@ def IndexBinaryFlat(d):
     return BinaryFlatIndex(d)
 
 
-class IndexLSH:
+class IndexLSH(CodedIndex):
     """faiss.IndexLSH(d, nbits, rotate_data, train_thresholds) on one GPU: bit j of a row's code is the sign of
     <x, rrot[j]> - thresholds[j] (>= 0 sets the bit), and search ranks the stored codes by Hamming distance to the query's code.
 
@@ -126,16 +125,11 @@ class IndexLSH:
         self.is_trained = not self.train_thresholds
         self._index = BinaryFlatIndex(8 * self.code_size, device=device)
         self.device = self._index.device
-        self._lib = self._index._lib
         self._rrot = lsh_rotation(self.d, self.nbits, seed)
         self._thresholds = np.zeros(self.nbits, np.float32)
         self._rot_dev = self._thr_dev = None
 
     # -- attributes ------------------------------------------------------------------------------
-    @property
-    def ntotal(self):
-        return self._index.ntotal
-
     @property
     def rrot(self):
         """numpy float32 [nbits, d]: row j is the direction of bit j.  Assignable while the index is empty."""
@@ -143,8 +137,7 @@ class IndexLSH:
 
     @rrot.setter
     def rrot(self, m):
-        if self.ntotal:
-            raise RuntimeError(f"rrot: the index holds {self.ntotal} rows encoded with the current rotation")
+        self._require_empty("rrot", "rotation")
         m = np.asarray(m)
         if m.shape != (self.nbits, self.d):
             raise ValueError(f"rrot expects [{self.nbits},{self.d}], got {m.shape}")
@@ -158,31 +151,19 @@ class IndexLSH:
 
     @thresholds.setter
     def thresholds(self, t):
-        if self.ntotal:
-            raise RuntimeError(f"thresholds: the index holds {self.ntotal} rows encoded with the current thresholds")
+        self._require_empty("thresholds", "thresholds")
         t = np.asarray(t)
         if t.shape != (self.nbits,):
             raise ValueError(f"thresholds expects [{self.nbits}], got {t.shape}")
         self._thresholds = np.ascontiguousarray(t, dtype=np.float32)
         self._thr_dev = None
 
-    @property
-    def codes(self):
-        """The stored codes, numpy uint8 [ntotal, code_size]."""
-        return self._index.reconstruct_n()
-
     # -- encoding --------------------------------------------------------------------------------
-    def _rows(self, x, what):
-        if isinstance(x, np.ndarray) and x.ndim == 1:
-            x = x.reshape(1, -1)
-        _staging.check_rows(x, self.d, what)
-        return x
-
-    def _encode_device(self, t, want_proj=False, use_thresholds=True):
-        """t: contiguous float32 CUDA tensor [n,d] -> (codes uint8 CUDA [n,code_size], proj float32 CUDA [n,nbits] or None)."""
+    def _encode_device(self, t, proj=None, use_thresholds=True):
+        """t: contiguous float32 CUDA tensor [n,d] -> codes uint8 CUDA [n,code_size].  proj: float32 CUDA [n,nbits] that receives
+        the projections <x, rrot[j]> (before the threshold), or None."""
         n = t.shape[0]
         codes = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device)
-        proj = torch.empty((n, self.nbits), dtype=torch.float32, device=self.device) if want_proj else None
         rot = thr = None
         if self.rotate_data:
             if self._rot_dev is None:
@@ -193,28 +174,21 @@ class IndexLSH:
                 self._thr_dev = torch.from_numpy(self._thresholds).to(self.device)
             thr = self._thr_dev
         _ffi.call("ivr_sign_encode", _ffi.CTX, t, n, self.d, rot, thr, self.nbits, codes, proj, device=self.device)
-        return codes, proj
+        return codes
 
-    def _chunks(self, x):
-        """x as contiguous float32 CUDA tensors: a CUDA tensor whole, a host array in blocks of _ENCODE_CHUNK rows."""
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            yield _dev_f32(x, self.device)
-            return
-        for i in range(0, max(len(x), 1), _ENCODE_CHUNK):
-            yield _dev_f32(x[i:i + _ENCODE_CHUNK], self.device)
+    def _encode_chunks(self, x, want_proj, use_thresholds=True):
+        """(codes, proj) of every chunk of x, from one launch per chunk."""
+        def one(t):
+            proj = torch.empty((t.shape[0], self.nbits), dtype=torch.float32, device=self.device) if want_proj else None
+            return self._encode_device(t, proj, use_thresholds), proj
+        return self._per_chunk(x, one)
 
     def sa_encode_device(self, x, want_proj=False):
         """(codes uint8 CUDA [n,code_size], proj float32 CUDA [n,nbits] or None): proj is the encoder's own float32 projection
         <x, rrot[j]> (before the threshold) of the same launch that produced the codes.  No host synchronisation when x is a
         contiguous float32 CUDA tensor on the index's device."""
-        x = self._rows(x, "sa_encode")
-        parts = []
-        for t in self._chunks(x):
-            parts.append(self._encode_device(t, want_proj))
-            _staging.sync_if_staged(_staging.is_staged(t, x), self.device)
-        codes = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
-        proj = None if not want_proj else parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
-        return codes, proj
+        parts = self._encode_chunks(self._rows(x, "sa_encode"), want_proj)
+        return cat_chunks([p[0] for p in parts]), cat_chunks([p[1] for p in parts]) if want_proj else None
 
     def sa_encode(self, x):
         """The codes of x, numpy uint8 [n, code_size]."""
@@ -225,49 +199,21 @@ class IndexLSH:
         (faiss's median rule), computed from the encoder's own float32 projections."""
         if not self.train_thresholds:
             return
-        if self.ntotal:
-            raise RuntimeError(f"train: the index holds {self.ntotal} rows encoded with the current thresholds")
+        self._require_empty("train", "thresholds")
         x = self._rows(x, "train")
         n = len(x)
         if n < 1:
             raise ValueError("train: no training rows")
-        parts = []
-        for t in self._chunks(x):
-            parts.append(self._encode_device(t, True, use_thresholds=False)[1])
-            _staging.sync_if_staged(_staging.is_staged(t, x), self.device)
-        proj = parts[0] if len(parts) == 1 else torch.cat(parts)
+        proj = cat_chunks([p[1] for p in self._encode_chunks(x, True, use_thresholds=False)])
         self._thresholds = torch.sort(proj, dim=0).values[n // 2].contiguous().cpu().numpy()
         self._thr_dev = None
         self.is_trained = True
 
     # -- FAISS surface ---------------------------------------------------------------------------
-    def add(self, x):
-        """Append rows: float32 [n,d], numpy or torch.  RuntimeError while untrained (train_thresholds without train())."""
-        if not self.is_trained:
-            raise RuntimeError("add: the index is not trained")
-        x = self._rows(x, "add")
-        for t in self._chunks(x):
-            if t.shape[0]:
-                self._index._add_device(self._encode_device(t)[0])
-
-    def search(self, x, k):
-        """(D, I) numpy arrays: D float32 Hamming distances ascending, I int64 rows; unused slots (2147483648.0, -1)."""
-        return search_numpy(self, x, k)
-
     def search_device(self, x, k):
-        """search returning CUDA tensors."""
-        if not self.is_trained:
-            raise RuntimeError("search: the index is not trained")
+        """search returning CUDA tensors: D float32 Hamming distances ascending, I int64 rows; unused slots (2147483648.0, -1)."""
+        self._require_trained("search")
         k = _staging.check_k(k, _ffi.IVR_MAX_K)
         codes = self.sa_encode_device(x)[0]
         D, I = self._index.search_device(codes, k)
         return D.to(torch.float32), I
-
-    def reset(self):
-        """Drop the rows; rotation and thresholds stay."""
-        self._index.reset()
-
-    def close(self):
-        x = getattr(self, "_index", None)
-        if x is not None:
-            x.close()

@@ -22,11 +22,10 @@ import numpy as np
 import torch
 
 from . import _ffi, _staging
-from ._faiss import METRIC_INNER_PRODUCT, search_numpy, to_numpy, typed_params
+from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, search_numpy, to_numpy, typed_params
 from .index import FlatIPIndex, normalize_L2
 
 _KNN_BLOCK = 1 << 16          # rows per kNN search of the build: bounds the query workspace of the storage
-_FLT_MAX = np.finfo(np.float32).max
 
 
 # -- the definitions: pure numpy, no GPU ---------------------------------------------------------------------------------------
@@ -130,7 +129,7 @@ def graph_search_ref(x, graph, q, k, ef, entries, max_expansions):
     q = np.asarray(q, np.float32).reshape(-1, x.shape[1])
     graph, entries = np.asarray(graph), np.asarray(entries).reshape(len(q), -1)
     n, k, ef = len(x), int(k), int(ef)
-    D = np.full((len(q), k), -_FLT_MAX, np.float32)
+    D = np.full((len(q), k), -FLT_MAX, np.float32)
     I = np.full((len(q), k), -1, np.int64)
     nexp = np.zeros(len(q), np.int32)
 
@@ -363,7 +362,7 @@ class GraphFlatIndex(_ffi.Handle):
         t, k, staged = self._queries(x, k)
         with torch.cuda.device(self.device):
             if self.ntotal == 0:
-                return (torch.full((t.shape[0], k), -_FLT_MAX, dtype=torch.float32, device=self.device),
+                return (torch.full((t.shape[0], k), -FLT_MAX, dtype=torch.float32, device=self.device),
                         torch.full((t.shape[0], k), -1, dtype=torch.int64, device=self.device))
             if normalize:
                 t = t.clone()

@@ -18,14 +18,13 @@ import numpy as np
 import torch
 
 from . import _ffi, _staging
-from ._faiss import METRIC_INNER_PRODUCT, METRIC_L2, search_numpy
+from ._coded import DecodableIndex
+from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
 from ._staging import dev_f32 as _dev_f32, dev_u8 as _dev_u8
 from .binary import BinaryFlatIndex
 from .ivf import kmeans_sample, split_empty_clusters
 
 KSUB = 256                    # centroids per slice: nbits = 8
-_ENCODE_CHUNK = 1 << 18       # rows of a host array staged per encoder launch
-_FLT_MAX = np.finfo(np.float32).max
 
 
 # -- pure numpy definitions (no GPU) -------------------------------------------------------------------------------------------
@@ -80,7 +79,7 @@ def pq_scan_ref(T, codes, k):
     n, k = len(codes), int(k)
     if k < 1:
         raise ValueError(f"pq_scan_ref: k={k} < 1")
-    D = np.full((nq, k), -_FLT_MAX, np.float32)
+    D = np.full((nq, k), -FLT_MAX, np.float32)
     I = np.full((nq, k), -1, np.int64)
     if n == 0:
         return D, I
@@ -92,7 +91,7 @@ def pq_scan_ref(T, codes, k):
     return D, I
 
 
-class PQIndex:
+class PQIndex(DecodableIndex):
     """Product-quantisation index (FAISS IndexPQ contract, METRIC_INNER_PRODUCT, nbits = 8) on one GPU.
 
     search(x, k) returns (D float32, I int64): the asymmetric score pq_scan_ref defines, descending, equal scores the lower row
@@ -103,9 +102,7 @@ class PQIndex:
         self.d, self.M = int(d), int(M)
         if int(nbits) != 8:
             raise ValueError(f"PQIndex: only nbits=8 is supported, got {nbits}")
-        if metric != METRIC_INNER_PRODUCT:
-            what = "METRIC_L2 is not supported" if metric == METRIC_L2 else f"got {metric}"
-            raise ValueError(f"PQIndex: only METRIC_INNER_PRODUCT ({METRIC_INNER_PRODUCT}) is supported, {what}")
+        require_inner_product(metric, "PQIndex")
         if self.M < 1 or self.M > _ffi.IVR_PQ_MAX_M:
             raise ValueError(f"PQIndex: M={M} outside [1,{_ffi.IVR_PQ_MAX_M}]")
         if self.d < 1 or self.d > 65536 or self.d % self.M != 0:
@@ -117,15 +114,10 @@ class PQIndex:
         self.is_trained = False
         self._index = BinaryFlatIndex(8 * self.M, device=device)
         self.device = self._index.device
-        self._lib = self._index._lib
         self._centroids = np.zeros((self.M, KSUB, self.dsub), np.float32)
         self._cb_dev = None
 
     # -- attributes ------------------------------------------------------------------------------
-    @property
-    def ntotal(self):
-        return self._index.ntotal
-
     @property
     def centroids(self):
         """numpy float32 [M,256,dsub]: the codebooks.  Assignable while the index is empty, which makes it trained."""
@@ -133,8 +125,7 @@ class PQIndex:
 
     @centroids.setter
     def centroids(self, c):
-        if self.ntotal:
-            raise RuntimeError(f"centroids: the index holds {self.ntotal} rows encoded with the current codebooks")
+        self._require_empty("centroids", "codebooks")
         c = np.asarray(c)
         if c.shape != self._centroids.shape:
             raise ValueError(f"centroids expects [{self.M},{KSUB},{self.dsub}], got {c.shape}")
@@ -149,18 +140,7 @@ class PQIndex:
             self._cb_dev = torch.from_numpy(self._centroids).to(self.device)
         return self._cb_dev
 
-    @property
-    def codes(self):
-        """The stored codes, numpy uint8 [ntotal, M]."""
-        return self._index.reconstruct_n()
-
     # -- encoding --------------------------------------------------------------------------------
-    def _rows(self, x, what):
-        if isinstance(x, np.ndarray) and x.ndim == 1:
-            x = x.reshape(1, -1)
-        _staging.check_rows(x, self.d, what)
-        return x
-
     def _encode_device(self, t, cb=None):
         """t: contiguous float32 CUDA tensor [n,d] -> codes uint8 CUDA [n,M] under the codebooks cb (default: the index's)."""
         codes = torch.empty((t.shape[0], self.M), dtype=torch.uint8, device=self.device)
@@ -168,41 +148,12 @@ class PQIndex:
                   device=self.device)
         return codes
 
-    def _chunks(self, x):
-        """x as contiguous float32 CUDA tensors: a CUDA tensor whole, a host array in blocks of _ENCODE_CHUNK rows."""
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            yield _dev_f32(x, self.device)
-            return
-        for i in range(0, max(len(x), 1), _ENCODE_CHUNK):
-            yield _dev_f32(x[i:i + _ENCODE_CHUNK], self.device)
-
-    def sa_encode_device(self, x):
-        """The codes of x as a uint8 CUDA tensor [n,M].  No host synchronisation when x is a contiguous float32 CUDA tensor on the
-        index's device."""
-        if not self.is_trained:
-            raise RuntimeError("sa_encode: the index is not trained")
-        x = self._rows(x, "sa_encode")
-        parts = []
-        for t in self._chunks(x):
-            parts.append(self._encode_device(t))
-            _staging.sync_if_staged(_staging.is_staged(t, x), self.device)
-        return parts[0] if len(parts) == 1 else torch.cat(parts)
-
-    def sa_encode(self, x):
-        """The codes of x, numpy uint8 [n,M] (pq_encode_ref states what a code is)."""
-        return self.sa_encode_device(x).cpu().numpy()
-
     def sa_decode_device(self, codes):
         """float32 CUDA [n,d]: row i is the concatenation of centroids[m, codes[i,m]] over m (a gather, no arithmetic)."""
-        if not self.is_trained:
-            raise RuntimeError("sa_decode: the index is not trained")
+        self._require_trained("sa_decode")
         c = _dev_u8(codes, self.M, self.device, "sa_decode").to(torch.int64)
         m = torch.arange(self.M, device=self.device).expand(c.shape[0], -1)
         return self._codebooks_device()[m, c].reshape(c.shape[0], self.d)
-
-    def sa_decode(self, codes):
-        """numpy float32 [n,d]: the rows the codes stand for."""
-        return self.sa_decode_device(codes).cpu().numpy()
 
     # -- training --------------------------------------------------------------------------------
     def train(self, x, niter=25, seed=1234, max_points_per_centroid=256):
@@ -213,8 +164,7 @@ class PQIndex:
                    centroid), order the rows of each slice by code (stable), take the mean of every run (ivr_segment_mean with
                    spherical=False: fixed summation order, so a seed gives the same bits every time), repair empty clusters
                    (split_empty_clusters, per slice)."""
-        if self.ntotal:
-            raise RuntimeError(f"train: the index holds {self.ntotal} rows encoded with the current codebooks")
+        self._require_empty("train", "codebooks")
         _staging.check_rows(x, self.d, "train")
         n = len(x)
         if n < KSUB:
@@ -254,20 +204,10 @@ class PQIndex:
         return out
 
     # -- FAISS surface ---------------------------------------------------------------------------
-    def add(self, x):
-        """Append rows: float32 [n,d], numpy or torch; only their codes are kept.  RuntimeError while untrained."""
-        if not self.is_trained:
-            raise RuntimeError("add: the index is not trained")
-        x = self._rows(x, "add")
-        for t in self._chunks(x):
-            if t.shape[0]:
-                self._index._add_device(self._encode_device(t))
-
     def compute_tables_device(self, x):
         """The lookup tables of the queries x [nq,d]: float32 CUDA [nq,M,256], T[i,m,j] = <slice m of x[i], centroids[m,j]>
         (pq_tables_ref states the tolerance)."""
-        if not self.is_trained:
-            raise RuntimeError("compute_tables: the index is not trained")
+        self._require_trained("compute_tables")
         t, staged = _staging.queries_f32(_staging.as_rows(x), self.d, self.device)
         nq = t.shape[0]
         _staging.check_nq(nq, "compute_tables")
@@ -283,8 +223,7 @@ class PQIndex:
     def search_tables_device(self, T, k):
         """The scan on caller-supplied tables T float32 [nq,M,256] (finite): (D, I) CUDA tensors, pq_scan_ref(T, codes, k) to the
         bit."""
-        if not self.is_trained:
-            raise RuntimeError("search: the index is not trained")
+        self._require_trained("search")
         t = _dev_f32(T, self.device)
         if t.dim() != 3 or tuple(t.shape[1:]) != (self.M, KSUB):
             raise ValueError(f"search_tables expects [nq,{self.M},{KSUB}], got {tuple(t.shape)}")
@@ -301,33 +240,11 @@ class PQIndex:
         D, I = self.search_tables_device(T, k)
         return D.cpu().numpy(), I.cpu().numpy()
 
-    def search(self, x, k):
-        """(D, I) numpy arrays: search_tables(compute_tables(x), k), bit for bit."""
-        return search_numpy(self, x, k)
-
     def search_device(self, x, k):
-        """search returning CUDA tensors."""
-        if not self.is_trained:
-            raise RuntimeError("search: the index is not trained")
+        """search returning CUDA tensors: search_tables_device(compute_tables_device(x), k), bit for bit."""
+        self._require_trained("search")
         k = _staging.check_k(k, _ffi.IVR_MAX_K)
         return self.search_tables_device(self.compute_tables_device(x), k)
-
-    def reconstruct_n(self, start=0, n=None):
-        """The decoded rows [start, start + n) as numpy float32 [n,d]: sa_decode of their stored codes."""
-        return self.sa_decode_device(self._index._codes_device(start, n)).cpu().numpy()
-
-    def reconstruct(self, i):
-        """The decoded row i, numpy float32 [d]."""
-        return self.reconstruct_n(int(i), 1)[0]
-
-    def reset(self):
-        """Drop the rows; the codebooks stay."""
-        self._index.reset()
-
-    def close(self):
-        x = getattr(self, "_index", None)
-        if x is not None:
-            x.close()
 
 
 def IndexPQ(d, M, nbits=8, metric=METRIC_INNER_PRODUCT):

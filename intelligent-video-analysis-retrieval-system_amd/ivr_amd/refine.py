@@ -11,15 +11,11 @@ import numpy as np
 import torch
 
 from . import _ffi, _staging
-from ._faiss import METRIC_INNER_PRODUCT, search_numpy, typed_params
-from .binary import IndexLSH
+from ._coded import CodedIndex
+from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, search_numpy, typed_params
 from .graph import GraphFlatIndex, SearchParametersHNSW
 from .index import FlatIPIndex, SearchParameters, _selector
 from .ivf import IVFFlatIndex, SearchParametersIVF
-from .pq import PQIndex
-from .sq import SQIndex
-
-_FLT_MAX = np.finfo(np.float32).max
 
 
 def _ordered(s):
@@ -42,7 +38,7 @@ def refine_order_ref(S, cand, k, ntotal=None):
     k = int(k)
     if k < 1 or k > kc:
         raise ValueError(f"refine_order_ref: k={k} outside [1,{kc}]")
-    D = np.full((nq, k), -_FLT_MAX, np.float32)
+    D = np.full((nq, k), -FLT_MAX, np.float32)
     I = np.full((nq, k), -1, np.int64)
     for i in range(nq):
         here = cand[i] >= 0
@@ -77,7 +73,7 @@ def _check_k_factor(v, who):
 
 def _base_kwargs(base, params):
     """The keyword arguments of base.search_device that carry base_index_params."""
-    if isinstance(base, (IndexLSH, PQIndex, SQIndex)):
+    if isinstance(base, CodedIndex):                # IndexLSH, PQIndex, SQIndex
         if params is not None:
             raise ValueError(f"base_index_params must be None for {type(base).__name__}, got {type(params).__name__}")
         return {}
@@ -101,7 +97,7 @@ class RefineFlatIndex:
     padding.  The base must be empty when it is wrapped and receives its rows through add() of this object only."""
 
     def __init__(self, base_index, device=None):
-        if not isinstance(base_index, (IndexLSH, PQIndex, SQIndex, IVFFlatIndex, GraphFlatIndex, FlatIPIndex)):
+        if not isinstance(base_index, (CodedIndex, IVFFlatIndex, GraphFlatIndex, FlatIPIndex)):
             raise ValueError(f"RefineFlatIndex: the base must be an IndexLSH, PQIndex, SQIndex, IVFFlatIndex, GraphFlatIndex or FlatIPIndex, "
                              f"got {type(base_index).__name__}")
         if isinstance(base_index, FlatIPIndex) and base_index.has_ids:

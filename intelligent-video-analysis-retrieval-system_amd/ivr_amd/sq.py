@@ -18,12 +18,11 @@ import numpy as np
 import torch
 
 from . import _ffi, _staging
-from ._faiss import METRIC_INNER_PRODUCT, METRIC_L2, search_numpy
+from ._coded import DecodableIndex
+from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
 from ._staging import dev_f32 as _dev_f32, dev_u8 as _dev_u8
 
 T_MAX = 16256                 # 127 * 128: the largest |t| of a prepared query
-_ENCODE_CHUNK = 1 << 18       # rows of a host array staged per encoder launch
-_FLT_MAX = np.finfo(np.float32).max
 _F = np.float32
 
 
@@ -135,7 +134,7 @@ def sq_scan_ref(t, scale, bias, codes, k):
     if k < 1:
         raise ValueError(f"sq_scan_ref: k={k} < 1")
     scale, bias = np.asarray(scale, _F).reshape(nq), np.asarray(bias, _F).reshape(nq)
-    D = np.full((nq, k), -_FLT_MAX, _F)
+    D = np.full((nq, k), -FLT_MAX, _F)
     I = np.full((nq, k), -1, np.int64)
     if n == 0:
         return D, I
@@ -170,20 +169,62 @@ def _dev_i16(t, d, device):
     return t.to(device=device).contiguous()
 
 
-class SQIndex(_ffi.Handle):
+class _SQStore(_ffi.Handle):
+    """The code rows of an SQIndex (ivr_sq_index_*): uint8 [n,d] in, the same bytes out.  The library handle is made by the first
+    call that needs it, so that an index can be made and refuse untrained use where there is no GPU."""
+    _DESTROY = "ivr_sq_index_destroy"
+
+    def __init__(self, d, device):
+        self.d = d
+        self.device = torch.device("cuda", int(device) if device is not None else
+                                   torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self._closed = False
+
+    def _call(self, name, *args):
+        if self._h is None:
+            if self._closed:
+                raise RuntimeError("SQIndex: the index is closed")
+            self._open("ivr_sq_index_create", self.device.index, self.d)
+        return super()._call(name, *args)
+
+    def close(self):
+        self._closed = True
+        super().close()
+
+    @property
+    def ntotal(self):
+        return 0 if self._h is None else int(_ffi.call("ivr_sq_index_ntotal", self._h))
+
+    def _add_device(self, codes):
+        self._call("ivr_sq_index_add", codes, codes.shape[0])
+        torch.cuda.current_stream(self.device).synchronize()  # `codes` may be a temporary
+
+    def _codes_device(self, start=0, n=None):
+        start = int(start)
+        n = self.ntotal - start if n is None else int(n)
+        if start < 0 or n < 0 or start + n > self.ntotal:
+            raise ValueError(f"reconstruct_n: rows [{start},{start + n}) outside [0,{self.ntotal})")
+        out = torch.empty((n, self.d), dtype=torch.uint8, device=self.device)
+        if n:
+            self._call("ivr_sq_index_get_codes", start, n, out)
+        return out
+
+    def reset(self):
+        if self._h is not None:
+            self._call("ivr_sq_index_reset")
+
+
+class SQIndex(DecodableIndex):
     """Scalar-quantiser index (FAISS IndexScalarQuantizer contract, QT_8bit, METRIC_INNER_PRODUCT) on one GPU.
 
     search(x, k) returns (D float32, I int64): the score sq_scan_ref defines, descending, equal integer scores the lower row first,
     unused slots (-FLT_MAX, -1).  add() and search() raise RuntimeError until train() has run or `trained` has been assigned."""
-    _DESTROY = "ivr_sq_index_destroy"
 
     def __init__(self, d, qtype=QT_8bit, metric=METRIC_INNER_PRODUCT, device=None):
         self.d = int(d)
         if qtype != QT_8bit:
             raise ValueError(f"SQIndex: only ScalarQuantizer.QT_8bit ({QT_8bit}) is supported, got {qtype}")
-        if metric != METRIC_INNER_PRODUCT:
-            what = "METRIC_L2 is not supported" if metric == METRIC_L2 else f"got {metric}"
-            raise ValueError(f"SQIndex: only METRIC_INNER_PRODUCT ({METRIC_INNER_PRODUCT}) is supported, {what}")
+        require_inner_product(metric, "SQIndex")
         if self.d < 1 or self.d > _ffi.IVR_SQ_MAX_D:
             raise ValueError(f"SQIndex: d={d} outside [1,{_ffi.IVR_SQ_MAX_D}] (the int32 accumulator holds 16256 * 128 * d)")
         self.code_size = self.d
@@ -192,28 +233,10 @@ class SQIndex(_ffi.Handle):
         self.is_trained = False
         self._trained = np.zeros(2 * self.d, _F)
         self._dev = None                     # (vmin, vdiff, gain, offset, decode table) on the device, made on first use
-        # the library handle is made by the first call that needs it (after the is_trained checks), so that an index can be made
-        # and refuse untrained use where there is no GPU
-        self.device = torch.device("cuda", int(device) if device is not None else
-                                   torch.cuda.current_device() if torch.cuda.is_available() else 0)
-        self._closed = False
-
-    def _xcall(self, name, *args):
-        if self._h is None:
-            if self._closed:
-                raise RuntimeError("SQIndex: the index is closed")
-            self._open("ivr_sq_index_create", self.device.index, self.d)
-        return self._call(name, *args)
-
-    def close(self):
-        self._closed = True
-        super().close()
+        self._index = _SQStore(self.d, device)
+        self.device = self._index.device
 
     # -- attributes ------------------------------------------------------------------------------
-    @property
-    def ntotal(self):
-        return 0 if self._h is None else int(_ffi.call("ivr_sq_index_ntotal", self._h))
-
     @property
     def trained(self):
         """numpy float32 [2d] = [vmin | vdiff], as faiss stores it.  Assignable (finite values) while the index is empty, which makes
@@ -222,8 +245,7 @@ class SQIndex(_ffi.Handle):
 
     @trained.setter
     def trained(self, tr):
-        if self.ntotal:
-            raise RuntimeError(f"trained: the index holds {self.ntotal} rows encoded with the current table")
+        self._require_empty("trained", "table")
         tr = np.asarray(tr)
         if tr.shape != (2 * self.d,):
             raise ValueError(f"trained expects [{2 * self.d}], got {tr.shape}")
@@ -241,27 +263,11 @@ class SQIndex(_ffi.Handle):
             self._dev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (vmin, vdiff, gain, offset, table))
         return self._dev
 
-    @property
-    def codes(self):
-        """The stored codes, numpy uint8 [ntotal, d] (faiss's unsigned bytes)."""
-        return self._codes_device().cpu().numpy()
-
-    def _codes_device(self, start=0, n=None):
-        start = int(start)
-        n = self.ntotal - start if n is None else int(n)
-        if start < 0 or n < 0 or start + n > self.ntotal:
-            raise ValueError(f"reconstruct_n: rows [{start},{start + n}) outside [0,{self.ntotal})")
-        out = torch.empty((n, self.d), dtype=torch.uint8, device=self.device)
-        if n:
-            self._xcall("ivr_sq_index_get_codes", start, n, out)
-        return out
-
     # -- training --------------------------------------------------------------------------------
     def train(self, x):
         """trained = sq_train_ref(x): the per-coordinate minimum and range of x [n,d], n >= 1, finite (ValueError otherwise).
         RuntimeError when the index holds rows."""
-        if self.ntotal:
-            raise RuntimeError(f"train: the index holds {self.ntotal} rows encoded with the current table")
+        self._require_empty("train", "table")
         _staging.check_rows(x, self.d, "train")
         if len(x) < 1:
             raise ValueError("train: no training rows")
@@ -277,12 +283,6 @@ class SQIndex(_ffi.Handle):
         self.is_trained = True
 
     # -- encoding --------------------------------------------------------------------------------
-    def _rows(self, x, what):
-        if isinstance(x, np.ndarray) and x.ndim == 1:
-            x = x.reshape(1, -1)
-        _staging.check_rows(x, self.d, what)
-        return x
-
     def _encode_device(self, t):
         """t: contiguous float32 CUDA tensor [n,d] -> codes uint8 CUDA [n,d]."""
         vmin, vdiff = self._tables()[:2]
@@ -290,69 +290,25 @@ class SQIndex(_ffi.Handle):
         _ffi.call("ivr_sq_encode", _ffi.CTX, t, t.shape[0], self.d, vmin, vdiff, codes, device=self.device)
         return codes
 
-    def _chunks(self, x):
-        """x as contiguous float32 CUDA tensors: a CUDA tensor whole, a host array in blocks of _ENCODE_CHUNK rows."""
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            yield _dev_f32(x, self.device)
-            return
-        for i in range(0, max(len(x), 1), _ENCODE_CHUNK):
-            yield _dev_f32(x[i:i + _ENCODE_CHUNK], self.device)
-
-    def sa_encode_device(self, x):
-        """The codes of x as a uint8 CUDA tensor [n,d].  No host synchronisation when x is a contiguous float32 CUDA tensor on the
-        index's device."""
-        if not self.is_trained:
-            raise RuntimeError("sa_encode: the index is not trained")
-        x = self._rows(x, "sa_encode")
-        parts = []
-        for t in self._chunks(x):
-            parts.append(self._encode_device(t))
-            _staging.sync_if_staged(_staging.is_staged(t, x), self.device)
-        return parts[0] if len(parts) == 1 else torch.cat(parts)
-
-    def sa_encode(self, x):
-        """The codes of x, numpy uint8 [n,d]: sq_encode_ref(x, trained) to the bit for finite x (a NaN's code is unspecified)."""
-        return self.sa_encode_device(x).cpu().numpy()
-
     def sa_decode_device(self, codes):
         """float32 CUDA [n,d]: sq_decode_ref(codes, trained) to the bit.  The 256 values a coordinate can decode to are computed on
         the host in sq_decode_ref's float32 order (vmin + vdiff * ((code + 0.5f) / 255f): addition, division, multiplication,
         addition) and gathered on the device: no arithmetic there."""
-        if not self.is_trained:
-            raise RuntimeError("sa_decode: the index is not trained")
+        self._require_trained("sa_decode")
         c = _dev_u8(codes, self.d, self.device, "sa_decode").to(torch.int64)
         j = torch.arange(self.d, device=self.device).expand(c.shape[0], -1)
         return self._tables()[4][c, j]
 
-    def sa_decode(self, codes):
-        """numpy float32 [n,d]: the rows the codes stand for."""
-        return self.sa_decode_device(codes).cpu().numpy()
-
     # -- FAISS surface ---------------------------------------------------------------------------
-    def add(self, x):
-        """Append rows: float32 [n,d], numpy or torch; only their codes are kept.  RuntimeError while untrained."""
-        if not self.is_trained:
-            raise RuntimeError("add: the index is not trained")
-        x = self._rows(x, "add")
-        for t in self._chunks(x):
-            if t.shape[0]:
-                self._add_codes_device(self._encode_device(t))
-
-    def _add_codes_device(self, codes):
-        self._xcall("ivr_sq_index_add", codes, codes.shape[0])
-        torch.cuda.current_stream(self.device).synchronize()  # `codes` may be a temporary
-
     def add_codes(self, codes):
         """Append rows by their codes: uint8 [n,d] as sa_encode returns them (faiss's add_sa_codes)."""
-        if not self.is_trained:
-            raise RuntimeError("add: the index is not trained")
-        self._add_codes_device(_dev_u8(codes, self.d, self.device, "add_codes"))
+        self._require_trained("add")
+        self._index._add_device(_dev_u8(codes, self.d, self.device, "add_codes"))
 
     def compute_query_codes_device(self, x):
         """The integer form of the queries x [nq,d]: (t int16 CUDA [nq,d], scale float32 CUDA [nq], bias float32 CUDA [nq]);
         sq_query_ref states them."""
-        if not self.is_trained:
-            raise RuntimeError("compute_query_codes: the index is not trained")
+        self._require_trained("compute_query_codes")
         q, staged = _staging.queries_f32(_staging.as_rows(x), self.d, self.device)
         nq = q.shape[0]
         _staging.check_nq(nq, "compute_query_codes")
@@ -371,8 +327,7 @@ class SQIndex(_ffi.Handle):
     def search_codes_device(self, t, scale, bias, k):
         """The scan on caller-supplied query codes (t int16 [nq,d], scale and bias float32 [nq]): (D, I) CUDA tensors,
         sq_scan_ref(t, scale, bias, codes, k) to the bit.  A |t| beyond 16256 is clamped to it."""
-        if not self.is_trained:
-            raise RuntimeError("search: the index is not trained")
+        self._require_trained("search")
         td = _dev_i16(t, self.d, self.device)
         nq = td.shape[0]
         _staging.check_nq(nq)
@@ -381,7 +336,7 @@ class SQIndex(_ffi.Handle):
             raise ValueError(f"search_codes expects scale and bias [{nq}], got {tuple(sd.shape)} and {tuple(bd.shape)}")
         k = _staging.check_k(k, _ffi.IVR_MAX_K)
         D, I = _staging.alloc_DI(nq, k, self.device)
-        self._xcall("ivr_sq_index_search", td, sd, bd, nq, k, D, I)
+        self._index._call("ivr_sq_index_search", td, sd, bd, nq, k, D, I)
         staged = _staging.is_staged(td, t) or _staging.is_staged(sd, scale) or _staging.is_staged(bd, bias)
         _staging.sync_if_staged(staged, self.device)
         return D, I
@@ -391,29 +346,11 @@ class SQIndex(_ffi.Handle):
         D, I = self.search_codes_device(t, scale, bias, k)
         return D.cpu().numpy(), I.cpu().numpy()
 
-    def search(self, x, k):
-        """(D, I) numpy arrays: search_codes(*compute_query_codes(x), k), bit for bit."""
-        return search_numpy(self, x, k)
-
     def search_device(self, x, k):
-        """search returning CUDA tensors."""
-        if not self.is_trained:
-            raise RuntimeError("search: the index is not trained")
+        """search returning CUDA tensors: search_codes_device(*compute_query_codes_device(x), k), bit for bit."""
+        self._require_trained("search")
         k = _staging.check_k(k, _ffi.IVR_MAX_K)
         return self.search_codes_device(*self.compute_query_codes_device(x), k)
-
-    def reconstruct_n(self, start=0, n=None):
-        """The decoded rows [start, start + n) as numpy float32 [n,d]: sa_decode of their stored codes."""
-        return self.sa_decode_device(self._codes_device(start, n)).cpu().numpy()
-
-    def reconstruct(self, i):
-        """The decoded row i, numpy float32 [d]."""
-        return self.reconstruct_n(int(i), 1)[0]
-
-    def reset(self):
-        """Drop the rows; the trained table stays."""
-        if self._h is not None:
-            self._call("ivr_sq_index_reset")
 
 
 def IndexScalarQuantizer(d, qtype=QT_8bit, metric=METRIC_INNER_PRODUCT):

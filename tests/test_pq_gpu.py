@@ -149,6 +149,42 @@ def test_scan_ties():
     idx.close()
 
 
+def test_scan_query_cap_second_chunk_of_one_query():
+    """A chunk holds 4096 queries at most: query 4096 of 4097 is a chunk of its own (c0 = 4096).  100 rows of 2-byte codes, the
+    tables of real queries."""
+    rng = np.random.default_rng(21)
+    idx = with_codebooks(4, 2, rng.standard_normal((2, 256, 2)).astype(np.float32))
+    codes = rng.integers(0, 256, (100, 2), dtype=np.uint8)
+    idx._index.add(codes)
+    T = idx.compute_tables(rng.standard_normal((4097, 4)).astype(np.float32))
+    check_scan(idx, T, codes, 4)
+    idx.close()
+
+
+def test_scan_key_budget_second_chunk_of_eight_queries():
+    """65,600 rows are 1025 groups, so k = 1024 selects 1024 groups of 64 keys per query and the 2^25 keys of a chunk hold
+    2^25 / (1024 * 64) = 512 queries: 520 queries are a chunk of 512 and one of 8.  The first 2 and the last 8 queries equal the
+    numpy scan, and the one call equals the two calls that split the queries where the chunks do, bit for bit.  2-byte codes over
+    65,600 rows repeat, so equal scores across groups are ranked by the lower row throughout."""
+    from ivr_amd.pq import pq_scan_ref
+    rng = np.random.default_rng(22)
+    n, nq, k, cut = 65600, 520, 1024, 512
+    codes = rng.integers(0, 256, (n, 2), dtype=np.uint8)
+    idx = scan_index(2, codes, split=50)
+    T = rng.standard_normal((nq, 2, 256)).astype(np.float32)
+    D, I = idx.search_tables(T, k)
+    assert D.shape == I.shape == (nq, k)
+    for part in (slice(0, 2), slice(cut, nq)):
+        Dr, Ir = pq_scan_ref(T[part], codes, k)
+        assert np.array_equal(I[part], Ir)
+        assert np.array_equal(D[part].view(np.uint32), Dr.view(np.uint32))
+    Da, Ia = idx.search_tables(T[:cut], k)
+    Db, Ib = idx.search_tables(T[cut:], k)
+    assert np.array_equal(I, np.concatenate([Ia, Ib]))
+    assert np.array_equal(D.view(np.uint32), np.concatenate([Da, Db]).view(np.uint32))
+    idx.close()
+
+
 def test_search_is_the_scan_of_its_own_tables():
     from ivr_amd.pq import IndexPQ
     rng = np.random.default_rng(12)

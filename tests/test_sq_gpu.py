@@ -149,6 +149,32 @@ def test_search_codes_equals_the_definition(d, n, nq, k):
     idx.close()
 
 
+def test_scan_query_cap_second_chunk_of_one_query():
+    """A chunk holds 4096 queries at most: query 4096 of 4097 is a chunk of its own (c0 = 4096)."""
+    codes, t, scale, bias = _scan_inputs(8, 100, 4097, 21)
+    idx = _index(8, codes)
+    _same(idx.search_codes(t, scale, bias, 4), sq_scan_ref(t, scale, bias, codes, 4))
+    idx.close()
+
+
+def test_scan_key_budget_rounds_the_chunk_down_to_whole_passes():
+    """65,600 rows are 1025 groups, so k = 1000 selects 1000 groups of 64 keys per query and the 2^25 keys of a chunk hold
+    2^25 / 64000 = 524 queries, 512 in whole passes of 32: 520 queries are a chunk of 512 and one of 8.  The first 2 and the last 8
+    queries equal the numpy scan, and the one call equals the two calls that split the queries where the chunks do, bit for bit.
+    A quarter of the rows repeat earlier ones, so equal scores across groups are ranked by the lower row."""
+    n, nq, k, cut = 65600, 520, 1000, 512
+    codes, t, scale, bias = _scan_inputs(16, n, nq, 22)
+    idx = _index(16, codes, [50, n - 50])
+    D, I = idx.search_codes(t, scale, bias, k)
+    assert D.shape == I.shape == (nq, k)
+    for part in (slice(0, 2), slice(cut, nq)):
+        _same((D[part], I[part]), sq_scan_ref(t[part], scale[part], bias[part], codes, k))
+    a = idx.search_codes(t[:cut], scale[:cut], bias[:cut], k)
+    b = idx.search_codes(t[cut:], scale[cut:], bias[cut:], k)
+    _same((D, I), (np.concatenate([a[0], b[0]]), np.concatenate([a[1], b[1]])))
+    idx.close()
+
+
 def test_rows_added_in_two_calls_across_tile_and_group_boundaries():
     codes, t, scale, bias = _scan_inputs(96, 13 + 60 + 130, 9, 5)
     idx = _index(96, codes, [13, 60, 130])                           # 13 -> 73 crosses rows 16 and 64, 73 -> 203 grows the allocation
