@@ -489,6 +489,46 @@ int ivr_pq_tables(ivr_ctx *ctx, const float *q /*DEV [nq][d]*/, int nq, int d, c
 int ivr_bin_index_search_pq(ivr_bin_index *idx, const float *T /*DEV [nq][M][256]*/, int nq, int M, int k, float *D /*DEV [nq][k]*/,
                             int64_t *I /*DEV [nq][k]*/, ivr_stream stream);
 
+/* ---- inverted lists over product-quantised codes (faiss IndexIVFPQ, inner product) ---------------------------------
+ * The coarse quantizer of the inverted-file index joined with the codes of the product quantiser ("inverted
+ * lists over PQ codes"; the definitions are the numpy functions ivfpq_pack_ref, ivfpq_unpack_ref and ivfpq_scan_ref of
+ * ivr_amd/ivfpq.py).  The object stores M-byte codes ordered by list, every list padded to whole 64-row groups in the interleaved
+ * layout of ivr_bin_index (pad bytes and pad rows zero), and the int64 label of every packed position (-1 on a pad row).  Training,
+ * the coarse assignment and the encoding of residuals are the caller's (ivr_pq_encode, ivr_pq_tables as they are).  Packed positions,
+ * pads included, stay below 2^32.  One stream at a time per handle. */
+typedef struct ivr_ivfpq ivr_ivfpq;
+int ivr_ivfpq_create(ivr_ctx *ctx, int M, int nlist, ivr_ivfpq **out);     /* 1 <= M <= IVR_PQ_MAX_M, nlist >= 1; holds no rows */
+int ivr_ivfpq_destroy(ivr_ivfpq *idx);
+int ivr_ivfpq_reset(ivr_ivfpq *idx);                         /* ntotal = 0, every list empty */
+int64_t ivr_ivfpq_ntotal(ivr_ivfpq *idx);
+int ivr_ivfpq_probe_queries(void);      /* queries per workgroup of the probe-table kernel (the scan takes one query per workgroup):
+                                           tests size their cases from it */
+/* Replace the content: n rows ordered by list, list l = rows [list_off[l], list_off[l + 1]) with list_off[0] = 0 and list_off[nlist]
+ * = n (IVR_ERR_INVALID otherwise, and for more than 2^32 packed positions).  Every label must be >= 0: a negative one marks a pad
+ * row, and a row stored under it is left out of every search (the labels live on the device and are not checked here).  list_off is
+ * read on the HOST during the call; codes and ids are packed by one kernel on `stream` and may be released once it has run.  When the
+ * call fails after its arguments were accepted (allocation, copy or launch), the object is left empty.  Synchronises the device first (a search in flight
+ * still reads the old lists) and allocates when the content outgrows the buffers. */
+int ivr_ivfpq_set_lists(ivr_ivfpq *idx, const uint8_t *codes /*DEV [n][M]*/, const int64_t *ids /*DEV [n]*/,
+                        const int64_t *list_off /*HOST [nlist + 1]*/, int64_t n, ivr_stream stream);
+/* the codes and / or labels of the list-ordered rows [start, start + n) as they were set; start + n <= ntotal */
+int ivr_ivfpq_get_codes(ivr_ivfpq *idx, int64_t start, int64_t n, uint8_t *codes /*DEV [n][M] or NULL*/, int64_t *ids /*DEV [n] or NULL*/,
+                        ivr_stream stream);
+/* Table-lookup top k over the lists each query probes.  assign[i] names the lists of query i in ASCENDING order: an entry outside
+ * [0, nlist) is skipped, a list named twice (adjacent entries) counts once, with the coarse score of its first entry.  The score of a
+ * row with code c in the list of entry j is (((coarse[i][j] + T[i][0][c0]) + T[i][1][c1]) + ...): plain float32 additions, coarse
+ * first, then ascending m (coarse == NULL: +0.0).  D / I under the contract of ivr_index_search: score descending (-0.0 counts and is
+ * reported as +0.0), equal scores the row in the lower list first and inside a list the row set earlier, I the row's label, unused
+ * slots -FLT_MAX / -1.  T: DEV float32 [nq][M][256], 16-byte aligned, finite.  1 <= k <= IVR_MAX_K, nq >= 1, p >= 1.  Per chunk of
+ * queries three launches on `stream`, no host round trip: the probe table (one wave per query), the scan (a workgroup of 8 waves
+ * keeps ONE query's table in LDS, M KiB, and scores a share of the 64-row groups of that query's lists into 64-bit keys) and
+ * select_topk.  Scratch per chunk (at most 2^25 key slots, one query's at least): 8 bytes per row, pads included, of the p longest
+ * lists per query, and 4 p + 4 bytes per query; grow-only.  Enqueue-only once the scratch has grown (a call that grows it allocates
+ * and cannot be captured into a hipGraph). */
+int ivr_ivfpq_search(ivr_ivfpq *idx, const float *T /*DEV [nq][M][256]*/, const float *coarse /*DEV [nq][p] or NULL*/,
+                     const int64_t *assign /*DEV [nq][p]*/, int nq, int p, int k, float *D /*DEV [nq][k]*/, int64_t *I /*DEV [nq][k]*/,
+                     ivr_stream stream);
+
 /* ---- scalar quantisation (faiss IndexScalarQuantizer, QT_8bit, inner product) ------------------------------------
  * The reference's _create_index never builds an IndexScalarQuantizer; it is here as the compressed base between the flat index and
  * the 32 - 64 byte codes: a row is stored as d bytes, byte j = the bucket of coordinate j between vmin[j] and vmin[j] + vdiff[j], and

@@ -356,6 +356,18 @@ class IVFFlatIndex:
                 x.close()
 
 
+def check_quantizer(quantizer, d, nlist, who):
+    """What an inverted-file index asks of the FlatIPIndex that is its coarse quantizer (the factories check the type first, as the
+    first of their refusals): plain (not id-mapped), of dimension d, holding 0 or exactly nlist rows.  ValueError otherwise, under
+    the name `who`."""
+    if quantizer.d != d:
+        raise ValueError(f"{who}: the quantizer has dimension {quantizer.d}, expected {d}")
+    if quantizer.has_ids:
+        raise ValueError(f"{who}: the quantizer must not be id-mapped")
+    if quantizer.ntotal not in (0, nlist):
+        raise ValueError(f"{who}: the quantizer holds {quantizer.ntotal} rows, expected 0 or nlist={nlist}")
+
+
 def IndexIVFFlat(quantizer, d, nlist, metric=METRIC_INNER_PRODUCT):
     """faiss.IndexIVFFlat(quantizer, d, nlist, faiss.METRIC_INNER_PRODUCT) drop-in.  quantizer: a plain (not id-mapped) FlatIPIndex of
     dimension d holding 0 rows (train() fills it) or exactly nlist rows (the centroids; train() then only sets is_trained).
@@ -365,10 +377,5 @@ def IndexIVFFlat(quantizer, d, nlist, metric=METRIC_INNER_PRODUCT):
     if metric != METRIC_INNER_PRODUCT:
         raise ValueError(f"IndexIVFFlat: only METRIC_INNER_PRODUCT ({METRIC_INNER_PRODUCT}) is supported, got {metric}")
     d, nlist = int(d), int(nlist)
-    if quantizer.d != d:
-        raise ValueError(f"IndexIVFFlat: the quantizer has dimension {quantizer.d}, expected {d}")
-    if quantizer.has_ids:
-        raise ValueError("IndexIVFFlat: the quantizer must not be id-mapped")
-    if quantizer.ntotal not in (0, nlist):
-        raise ValueError(f"IndexIVFFlat: the quantizer holds {quantizer.ntotal} rows, expected 0 or nlist={nlist}")
+    check_quantizer(quantizer, d, nlist, "IndexIVFFlat")
     return IVFFlatIndex(d, nlist, _quantizer=quantizer)

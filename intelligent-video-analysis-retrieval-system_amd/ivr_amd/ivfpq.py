@@ -1,0 +1,495 @@
+"""FAISS-shaped inverted-file index over product-quantised codes (IndexIVFPQ, inner product, 8-bit codes) resident in MI355X HBM.
+
+The reference's `_create_index` (`core.py:1198-1230`) never builds an `IndexIVFPQ`; it is here because it is the compressed index
+faiss users deploy at scale, and the base `IndexRefineFlat` is usually paired with.  It joins the coarse quantizer of `IVFFlatIndex`
+(a `FlatIPIndex` of `nlist` centroids, the same k-means, the same `assign`) with the codes of `PQIndex`: a row is stored in the list of
+its best centroid as the `M`-byte code of its residual against that centroid (`by_residual`, the default, as in faiss) or of the row
+itself, and a search scores only the rows of the `nprobe` lists whose centroids score best against the query.
+
+With the inner product residual coding costs nothing at search time: `<q, c_l + r> = <q, c_l> + <q, r>`, so the `M x 256` lookup
+table of a query (`PQIndex.compute_tables_device`, unchanged) serves every list, and the only per-list term is the coarse score the
+coarse search has produced already.  `ivfpq_scan_ref` below states the scan to the bit; the list store, the probe table and the scan
+are HIP kernels of libivr_hip.so (csrc/search_ivfpq.hip), the encoder and the table builder are those of `PQIndex`; torch stages
+arrays, subtracts centroids and orders rows by list.
+
+Tie rule: equal scores rank the row in the LOWER LIST first, and within a list the row ADDED EARLIER, as on `IVFFlatIndex`: a result
+does not depend on the order in which lists were probed.
+"""
+import numpy as np
+import torch
+
+from . import _ffi, _staging
+from ._coded import ENCODE_CHUNK
+from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product, search_numpy, to_numpy, typed_params
+from ._staging import dev_f32 as _dev_f32
+from .index import FlatIPIndex, _ids_i64
+from .ivf import IVFFlatIndex, SearchParametersIVF, _nearest, check_quantizer
+from .pq import KSUB, PQIndex
+
+
+# -- pure numpy definitions (no GPU) -------------------------------------------------------------------------------------------
+def _words(M):
+    """16-byte words per stored row: 1, 2, 3, 4 or 8 (the word counts of the binary store)."""
+    w = (int(M) + 15) // 16
+    return w if w <= 4 else 8
+
+
+def _check_off(list_off, n):
+    off = np.asarray(list_off, np.int64).reshape(-1)
+    if len(off) < 2 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+        raise ValueError(f"list_off must ascend from 0 to n={n}")
+    return off
+
+
+def ivfpq_positions_ref(list_off):
+    """The packed position of every list-ordered row: list l starts at group goff[l] = sum over the lists below it of
+    ceil(size / 64), and its row i sits at 64 goff[l] + i.  -> (pos int64 [n], goff int64 [nlist + 1])."""
+    off = np.asarray(list_off, np.int64).reshape(-1)
+    sizes = np.diff(off)
+    goff = np.concatenate([[0], np.cumsum((sizes + 63) // 64)]).astype(np.int64)
+    pos = np.concatenate([64 * goff[l] + np.arange(sizes[l], dtype=np.int64) for l in range(len(sizes))] + [np.zeros(0, np.int64)])
+    return pos, goff
+
+
+def ivfpq_pack_ref(codes, list_off):
+    """The device layout of list-ordered codes: uint8 [n,M] -> uint8 [groups, W, 64, 16].  Every list is padded to whole 64-row
+    groups; inside a group lane i holds row i of the group, and bytes 16 w .. 16 w + 15 of its code are word w (W = 1, 2, 3, 4 or 8
+    words: M bytes rounded up).  Pad bytes and pad rows are zero."""
+    codes = np.asarray(codes)
+    if codes.ndim != 2 or codes.dtype != np.uint8:
+        raise ValueError(f"ivfpq_pack_ref: codes must be uint8 [n,M], got {codes.dtype} {codes.shape}")
+    n, M = codes.shape
+    pos, goff = ivfpq_positions_ref(_check_off(list_off, n))
+    W = _words(M)
+    padded = np.zeros((int(goff[-1]) * 64, W * 16), np.uint8)
+    padded[pos, :M] = codes
+    return np.ascontiguousarray(padded.reshape(int(goff[-1]), 64, W, 16).transpose(0, 2, 1, 3))
+
+
+def ivfpq_unpack_ref(packed, list_off, M):
+    """The inverse of ivfpq_pack_ref: uint8 [groups, W, 64, 16] -> the list-ordered codes uint8 [n,M]."""
+    packed = np.asarray(packed)
+    M = int(M)
+    if packed.ndim != 4 or packed.dtype != np.uint8 or packed.shape[1:] != (_words(M), 64, 16):
+        raise ValueError(f"ivfpq_unpack_ref: packed must be uint8 [groups,{_words(M)},64,16], got {packed.dtype} {packed.shape}")
+    off = np.asarray(list_off, np.int64).reshape(-1)
+    pos, goff = ivfpq_positions_ref(_check_off(off, off[-1]))
+    if goff[-1] != packed.shape[0]:
+        raise ValueError(f"ivfpq_unpack_ref: list_off asks for {goff[-1]} groups, packed holds {packed.shape[0]}")
+    rows = packed.transpose(0, 2, 1, 3).reshape(packed.shape[0] * 64, -1)
+    return np.ascontiguousarray(rows[pos, :M])
+
+
+def ivfpq_scan_ref(T, coarse, assign, list_off, codes, ids, k):
+    """The search, to the bit.  T float32 [nq,M,256] (finite), coarse float32 [nq,p], assign int64 [nq,p], codes uint8 [n,M] in list
+    order (list l = rows list_off[l] .. list_off[l + 1]), ids int64 [n] -> (D float32 [nq,k], I int64 [nq,k]).
+
+    Query i probes the lists assign[i] names: -1 entries are skipped, and a list named twice counts once, with the coarse score of its
+    first mention after an ascending STABLE sort of the row.  The score of row r of a list probed through entry j is
+    ((coarse[i,j] + T[i,0,codes[r,0]]) + T[i,1,codes[r,1]]) + ...: plain float32 additions, coarse first, then ascending m (without
+    by_residual the caller passes coarse = +0.0).  (D, I) is the ordering of refine_order_ref over the probed rows: score descending,
+    -0.0 counted and reported as +0.0, equal scores the row in the lower list first and within a list the row added earlier; I holds
+    ids[r].  Unused slots hold (-FLT_MAX, -1), as those of IVFFlatIndex.search do.  ValueError for an entry below -1 or >= nlist."""
+    from .refine import refine_order_ref
+    T = np.asarray(T, np.float32)
+    codes = np.asarray(codes)
+    assign = np.asarray(assign).astype(np.int64)
+    coarse = np.asarray(coarse, np.float32)
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    if T.ndim != 3 or T.shape[2] != KSUB or codes.ndim != 2 or codes.shape[1] != T.shape[1] or codes.dtype != np.uint8:
+        raise ValueError(f"ivfpq_scan_ref: T {T.shape} must be [nq,M,{KSUB}] and codes {codes.shape} uint8 [n,M]")
+    nq, M, _ = T.shape
+    n, k = len(codes), int(k)
+    off = _check_off(list_off, n)
+    nlist = len(off) - 1
+    if assign.ndim != 2 or assign.shape[0] != nq or assign.shape[1] < 1 or coarse.shape != assign.shape or len(ids) != n:
+        raise ValueError(f"ivfpq_scan_ref: assign {assign.shape} and coarse {coarse.shape} must be [{nq},p], ids [{n}]")
+    if assign.size and (assign.min() < -1 or assign.max() >= nlist):
+        raise ValueError(f"ivfpq_scan_ref: assign entries must lie in [-1, {nlist})")
+    if k < 1:
+        raise ValueError(f"ivfpq_scan_ref: k={k} < 1")
+    D = np.full((nq, k), -FLT_MAX, np.float32)
+    I = np.full((nq, k), -1, np.int64)
+    for i in range(nq):
+        order = np.argsort(assign[i], kind="stable")
+        a, c = assign[i, order], coarse[i, order]
+        rows, base = [np.zeros(0, np.int64)], [np.zeros(0, np.float32)]
+        for j, l in enumerate(a):
+            if l < 0 or (j > 0 and a[j - 1] == l):
+                continue
+            rows.append(np.arange(off[l], off[l + 1], dtype=np.int64))
+            base.append(np.full(off[l + 1] - off[l], c[j], np.float32))
+        rows, S = np.concatenate(rows), np.concatenate(base)
+        if len(rows) == 0:
+            continue
+        for m in range(M):
+            S = S + T[i, m, codes[rows, m]]        # float32 + float32, rounded once: the kernel's addition
+        kk = min(k, len(rows))
+        Di, Ri = refine_order_ref(S[None], rows[None], kk)
+        D[i, :kk], I[i, :kk] = Di[0], ids[Ri[0]]
+    return D, I
+
+
+class _CodebookPQ(PQIndex):
+    """The PQIndex an IVFPQIndex holds for its codebooks, encoder, tables and decoder.  Its own row store stays empty; the rows its
+    codebooks are bound to are the owner's, so that is what `centroids` and `train` ask about."""
+    _owner = None
+
+    def _require_empty(self, what, noun):
+        n = self._owner.ntotal if self._owner is not None else 0
+        if n:
+            raise RuntimeError(f"{what}: the index holds {n} rows encoded with the current {noun}")
+
+
+class _Lists(_ffi.Handle):
+    """The list store of an IVFPQIndex on the device (ivr_ivfpq of csrc/search_ivfpq.hip)."""
+    _DESTROY = "ivr_ivfpq_destroy"
+
+    def __init__(self, M, nlist, device):
+        self._open("ivr_ivfpq_create", device, int(M), int(nlist))
+
+
+class IVFPQIndex:
+    """Inverted-file index over product-quantised codes (FAISS IndexIVFPQ contract, METRIC_INNER_PRODUCT, nbits = 8) on one GPU.
+
+    search(x, k) looks at the rows of the nprobe lists nearest to each query and returns (D, I) as ivfpq_scan_ref defines them over
+    the tables pq.compute_tables_device(x) and the quantizer's float32 scores of the probed centroids: float32 descending, int64
+    labels, (-FLT_MAX, -1) padding.  Equal scores rank the row in the lower list first, and within a list the row added earlier.
+    Every add() call regroups the whole index by list (one pass over all stored codes): add in large batches."""
+
+    def __init__(self, d, nlist, M, device=None, _quantizer=None):
+        self.pq = _CodebookPQ(d, M, device=device if _quantizer is None else _quantizer.device.index)
+        self.pq._owner = self
+        self._coarse = IVFFlatIndex(d, nlist, device=device, _quantizer=_quantizer)      # the coarse part; its own row store stays empty
+        self.d, self.nlist, self.M = self._coarse.d, self._coarse.nlist, self.pq.M
+        self.quantizer = self._coarse.quantizer
+        self.device = self.quantizer.device
+        self.code_size = self.M
+        self.nbits = 8
+        self.metric_type = METRIC_INNER_PRODUCT
+        self._by_residual = True
+        self._nprobe = 1
+        self._cent_dev = None
+        self._lists = _Lists(self.M, self.nlist, self.device.index)
+        self._off_host = np.zeros(self.nlist + 1, np.int64)
+        self._off = torch.from_numpy(self._off_host).to(self.device)
+
+    # -- attributes ------------------------------------------------------------------------------
+    @property
+    def ntotal(self):
+        return int(self._off_host[-1])
+
+    @property
+    def is_trained(self):
+        return bool(self.pq.is_trained and (self._coarse.is_trained or self.quantizer.ntotal == self.nlist))
+
+    @property
+    def nprobe(self):
+        return self._nprobe
+
+    @nprobe.setter
+    def nprobe(self, v):
+        if int(v) < 1:
+            raise ValueError(f"nprobe={v} < 1")
+        self._nprobe = int(v)
+
+    @property
+    def by_residual(self):
+        """True (faiss's default): a row is coded as its residual against its list's centroid.  Assignable only while the index is
+        empty and untrained: the codebooks are trained on what is coded."""
+        return self._by_residual
+
+    @by_residual.setter
+    def by_residual(self, v):
+        if self.ntotal or self.is_trained:
+            raise RuntimeError("by_residual: the index is trained or holds rows coded with the current setting")
+        self._by_residual = bool(v)
+
+    @property
+    def centroids(self):
+        """numpy float32 [nlist,d]: quantizer.reconstruct_n()."""
+        return self.quantizer.reconstruct_n()
+
+    def _centroids_device(self):
+        if self._cent_dev is None:
+            self._cent_dev = self.quantizer.gather_device(torch.arange(self.nlist, dtype=torch.int64, device=self.device))
+        return self._cent_dev
+
+    def _require_trained(self, what):
+        if not self.is_trained:
+            raise RuntimeError(f"{what}: the index is not trained")
+
+    def _check_list(self, l):
+        l = int(l)
+        if not 0 <= l < self.nlist:
+            raise ValueError(f"list {l} outside [0, {self.nlist})")
+        return int(self._off_host[l]), int(self._off_host[l + 1])
+
+    def list_sizes(self):
+        """int64 [nlist]: rows per list."""
+        return np.diff(self._off_host)
+
+    def list_ids(self, l):
+        """The labels of list l in stored order (numpy int64)."""
+        a, b = self._check_list(l)
+        return self._rows_device(a, b - a, codes=False)[1].cpu().numpy()
+
+    def list_codes(self, l):
+        """The codes of list l in stored order (numpy uint8 [size, M])."""
+        a, b = self._check_list(l)
+        return self._rows_device(a, b - a, ids=False)[0].cpu().numpy()
+
+    def _rows_device(self, start=0, n=None, codes=True, ids=True):
+        """(codes uint8 CUDA [n,M], ids int64 CUDA [n]) of the list-ordered rows [start, start + n); None for the half not asked for."""
+        n = self.ntotal - start if n is None else n
+        c = torch.empty((n, self.M), dtype=torch.uint8, device=self.device) if codes else None
+        i = torch.empty(n, dtype=torch.int64, device=self.device) if ids else None
+        if n:
+            self._lists._call("ivr_ivfpq_get_codes", int(start), int(n), c, i)
+        return c, i
+
+    def _set_lists(self, codes, ids, off_host):
+        self._lists._call("ivr_ivfpq_set_lists", codes, ids, off_host.ctypes.data, len(codes))
+        torch.cuda.current_stream(self.device).synchronize()      # codes and ids may be temporaries
+        self._off_host = off_host
+        self._off = torch.from_numpy(off_host).to(self.device)
+
+    # -- training --------------------------------------------------------------------------------
+    def train(self, x, niter=10, seed=1234, max_points_per_centroid=256, spherical=True):
+        """Train the quantizer exactly as IVFFlatIndex.train does (same arguments; a quantizer that already holds nlist rows is taken
+        as it is), form the training residuals x_i - centroids[assign(x_i)] (one float32 subtraction per coordinate; x itself without
+        by_residual) and call pq.train on them with PQIndex.train's own defaults."""
+        if self.ntotal:
+            raise RuntimeError(f"train: the index holds {self.ntotal} rows encoded with the current codebooks")
+        _staging.check_rows(x, self.d, "train")
+        self._coarse.train(x, niter=niter, seed=seed, max_points_per_centroid=max_points_per_centroid, spherical=spherical)
+        self._cent_dev = None
+        with torch.cuda.device(self.device):
+            t = _dev_f32(x, self.device)
+            self.pq.train(self._residuals(t, _nearest(self.quantizer, t).clamp_(0, self.nlist - 1)) if self._by_residual else t)
+
+    def _residuals(self, t, lists):
+        return t - self._centroids_device()[lists]
+
+    # -- adding ----------------------------------------------------------------------------------
+    def assign(self, x):
+        """The list of each row of x (numpy int64 [n]): the quantizer's own search(x, 1), so equal scores pick the lower list."""
+        self._require_trained("assign")
+        return self.quantizer.search(x, 1)[1][:, 0]
+
+    def add(self, x):
+        """Append rows labelled ntotal, ntotal + 1, ... as faiss does.  See add_with_ids."""
+        n = len(x) if isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim == 2 else 0
+        self.add_with_ids(x, np.arange(self.ntotal, self.ntotal + n, dtype=np.int64), _what="add")
+
+    def add_with_ids(self, x, ids, _what="add_with_ids"):
+        """Append rows under caller-chosen int64 labels (>= 0, duplicates allowed).  Each row goes to the list of its best centroid
+        and only its code is kept: pq's encoder applied to its residual against that centroid (to the row itself without
+        by_residual).  The whole index is regrouped by list in every call: one pass over all stored codes (unpack, a stable argsort
+        of the list numbers, pack), so add in large batches.  RuntimeError while untrained."""
+        self._require_trained(_what)
+        _staging.check_rows(x, self.d, _what)
+        n = len(x)
+        ids = _ids_i64(ids, n, _what)
+        if n and int(ids.min()) < 0:
+            raise ValueError(f"{_what}: negative id {int(ids.min())} (-1 labels an unused result slot)")
+        if n == 0:
+            return
+        with torch.cuda.device(self.device):
+            codes, lists = [], []
+            for i in range(0, n, ENCODE_CHUNK):
+                t = _dev_f32(x[i:i + ENCODE_CHUNK], self.device)
+                l = _nearest(self.quantizer, t).clamp_(0, self.nlist - 1)
+                codes.append(self.pq._encode_device(self._residuals(t, l) if self._by_residual else t))
+                lists.append(l)
+            codes, lists = torch.cat(codes), torch.cat(lists)
+            new_ids = torch.from_numpy(np.ascontiguousarray(ids)).to(self.device)
+            if self.ntotal:
+                old_codes, old_ids = self._rows_device()
+                sizes = torch.from_numpy(self.list_sizes()).to(self.device)
+                codes = torch.cat([old_codes, codes])
+                new_ids = torch.cat([old_ids, new_ids])
+                lists = torch.cat([torch.repeat_interleave(torch.arange(self.nlist, device=self.device), sizes), lists])
+            order = torch.argsort(lists, stable=True)
+            off = np.concatenate([[0], np.cumsum(torch.bincount(lists, minlength=self.nlist).cpu().numpy())]).astype(np.int64)
+            self._set_lists(codes[order].contiguous(), new_ids[order].contiguous(), off)
+
+    # -- search ----------------------------------------------------------------------------------
+    def compute_tables_device(self, x):
+        """pq.compute_tables_device(x): float32 CUDA [nq,M,256], the same for every list."""
+        return self.pq.compute_tables_device(x)
+
+    def _queries(self, x, k, what):
+        t, staged = _staging.queries_f32(_staging.as_rows(x), self.d, self.device)
+        k = _staging.check_k(k, _ffi.IVR_MAX_K)
+        self._require_trained(what)
+        _staging.check_nq(t.shape[0])
+        return t, k, staged
+
+    def _coarse_scores(self, t, assign):
+        """float32 CUDA [nq,p]: the quantizer's inner product of query i with centroid assign[i,j], with the bits its search reports
+        (-FLT_MAX for a -1 entry, which the scan skips)."""
+        step = _ffi.IVR_MAX_K
+        return torch.cat([self.quantizer.rescore_device(t, assign[:, j:j + step].contiguous())[0] for j in range(0, assign.shape[1], step)], dim=1)
+
+    def search(self, x, k, params=None):
+        """(D, I) numpy arrays, over the rows of the nprobe lists nearest to each query.  params = SearchParametersIVF(nprobe=...)
+        overrides nprobe for this call; a selector raises ValueError."""
+        params = typed_params(params, SearchParametersIVF, "IVFPQIndex")
+        return search_numpy(self, x, k, nprobe=None if params is None else params.nprobe)
+
+    def search_device(self, x, k, nprobe=None):
+        """Device-resident search: CUDA tensors, no host synchronisation (unless x had to be staged).  nprobe (default: the attribute)
+        is clipped to nlist; below nlist it is the k of the coarse search and so at most IVR_MAX_K.  With nprobe >= nlist there is no
+        coarse search: every list is probed, with the coarse scores search_preassigned computes."""
+        t, k, staged = self._queries(x, k, "search")
+        nprobe = min(self.nprobe if nprobe is None else int(nprobe), self.nlist)
+        if nprobe < 1:
+            raise ValueError(f"nprobe={nprobe} < 1")
+        with torch.cuda.device(self.device):
+            coarse = None
+            if nprobe >= self.nlist:
+                assign = torch.arange(self.nlist, dtype=torch.int64, device=self.device).expand(t.shape[0], -1).contiguous()
+                if self._by_residual:
+                    coarse = self._coarse_scores(t, assign)
+            else:
+                if nprobe > _ffi.IVR_MAX_K:
+                    raise ValueError(f"nprobe={nprobe} outside [1,{_ffi.IVR_MAX_K}] (or >= nlist)")
+                coarse, assign = self.quantizer.search_device(t, nprobe)
+                if not self._by_residual:
+                    coarse = None
+            out = self._scan(self.pq.compute_tables_device(t), coarse, assign, k)
+            _staging.sync_if_staged(staged, self.device)
+            return out
+
+    def search_preassigned(self, x, k, assign, coarse_dis=None):
+        """faiss search_preassigned: assign int64 [nq,p] (numpy or CUDA tensor) names the lists to scan for each query; -1 entries
+        are skipped and a list named twice is scanned once.  coarse_dis float32 [nq,p]: the coarse score that goes with each entry;
+        when omitted it is the quantizer's float32 inner product for exactly the named lists (the bits its search reports).  Without
+        by_residual it is not used.  ValueError for an entry >= nlist or < -1.  Returns (D, I) numpy arrays."""
+        return to_numpy(self.search_preassigned_device(x, k, assign, coarse_dis))
+
+    def search_preassigned_device(self, x, k, assign, coarse_dis=None):
+        """search_preassigned returning CUDA tensors; the range check of assign synchronises once."""
+        t, k, staged = self._queries(x, k, "search_preassigned")
+        with torch.cuda.device(self.device):
+            assign = self._assign(assign, t.shape[0], "search_preassigned")
+            coarse = None
+            if self._by_residual:
+                coarse = self._coarse_scores(t, assign) if coarse_dis is None else self._coarse_arg(coarse_dis, assign, "search_preassigned")
+            out = self._scan(self.pq.compute_tables_device(t), coarse, assign, k)
+            _staging.sync_if_staged(staged, self.device)
+            return out
+
+    def search_tables_preassigned_device(self, T, coarse, assign, k):
+        """The scan alone on caller-supplied tables: T float32 [nq,M,256] (finite), coarse float32 [nq,p] or None (+0.0), assign
+        int64 [nq,p] -> (D, I) CUDA tensors, ivfpq_scan_ref(T, coarse, assign, list offsets, stored codes, stored ids, k) to the
+        bit, whatever by_residual says."""
+        self._require_trained("search")
+        t = _dev_f32(T, self.device)
+        if t.dim() != 3 or tuple(t.shape[1:]) != (self.M, KSUB):
+            raise ValueError(f"search_tables_preassigned expects T [nq,{self.M},{KSUB}], got {tuple(t.shape)}")
+        k = _staging.check_k(k, _ffi.IVR_MAX_K)
+        _staging.check_nq(t.shape[0])
+        with torch.cuda.device(self.device):
+            assign = self._assign(assign, t.shape[0], "search_tables_preassigned")
+            out = self._scan(t, None if coarse is None else self._coarse_arg(coarse, assign, "search_tables_preassigned"), assign, k)
+            _staging.sync_if_staged(True, self.device)       # T, coarse and assign may all be staged copies
+            return out
+
+    def _assign(self, assign, nq, what):
+        assign = _staging.int_tensor(assign, f"{what}: assign", np_dtype=np.int64)
+        if assign.dim() != 2 or assign.shape[0] != nq or assign.shape[1] < 1:
+            raise ValueError(f"{what}: assign must be [{nq},p] with p >= 1, got {tuple(assign.shape)}")
+        assign = assign.to(device=self.device, dtype=torch.int64)
+        _staging.check_entries(assign, self.nlist, f"{what}: assign entries")
+        return assign
+
+    def _coarse_arg(self, coarse, assign, what):
+        c = _dev_f32(coarse, self.device)
+        if tuple(c.shape) != tuple(assign.shape):
+            raise ValueError(f"{what}: the coarse scores must be float32 {tuple(assign.shape)}, got {tuple(c.shape)}")
+        return c
+
+    def _scan(self, T, coarse, assign, k):
+        """assign: int64 CUDA [nq,p], entries in [-1, nlist).  The kernel wants every row ascending (a repeated list is then adjacent);
+        the sort is stable, so the first mention of a list keeps its coarse score."""
+        nq, p = assign.shape
+        assign, order = torch.sort(assign, dim=1, stable=True)
+        if coarse is not None:
+            coarse = torch.gather(coarse, 1, order).contiguous()
+        D, I = _staging.alloc_DI(nq, k, self.device)
+        self._lists._call("ivr_ivfpq_search", T, coarse, assign.contiguous(), nq, p, k, D, I)
+        return D, I
+
+    # -- reconstruction --------------------------------------------------------------------------
+    def reconstruct_batch(self, ids):
+        """numpy float32 [n,d]: for every label centroids[l] + pq.sa_decode(code) of the row stored under it, one float32 addition per
+        coordinate (the decode alone without by_residual); the lowest stored position on duplicate labels.  RuntimeError when a label
+        names no row.  Reads every stored label and code once per call."""
+        keys = _ids_i64(np.atleast_1d(ids) if not isinstance(ids, torch.Tensor) else ids, None, "reconstruct_batch")
+        miss, out = self._reconstruct(keys)
+        if len(miss):
+            raise RuntimeError(f"reconstruct_batch: key {int(keys[miss[0]])} is not in the index ({len(miss)} of {len(keys)} missing)")
+        return out
+
+    def reconstruct(self, i):
+        """The decoded row stored under label i (the lowest stored position on duplicates); RuntimeError when none is."""
+        miss, out = self._reconstruct(np.array([int(i)], np.int64))
+        if len(miss):
+            raise RuntimeError(f"reconstruct: id {int(i)} is not in the index")
+        return out[0]
+
+    def _reconstruct(self, keys):
+        """keys int64 numpy [n] -> (the positions in keys of the labels that name no row, the decoded rows [n,d] or None when one is
+        missing)."""
+        if len(keys) == 0:
+            return np.zeros(0, np.int64), np.zeros((0, self.d), np.float32)
+        if self.ntotal == 0:
+            return np.arange(len(keys)), None
+        with torch.cuda.device(self.device):
+            codes, stored = self._rows_device()
+            k = torch.from_numpy(np.ascontiguousarray(keys)).to(self.device)
+            sorted_ids, perm = torch.sort(stored, stable=True)
+            at = torch.searchsorted(sorted_ids, k).clamp_(max=self.ntotal - 1)
+            miss = np.flatnonzero((sorted_ids[at] != k).cpu().numpy())
+            if len(miss):
+                return miss, None
+            rows = perm[at]
+            out = self.pq.sa_decode_device(codes[rows].contiguous())
+            if self._by_residual:
+                out = self._centroids_device()[torch.searchsorted(self._off, rows, right=True) - 1] + out
+            return miss, out.cpu().numpy()
+
+    # -- maintenance -----------------------------------------------------------------------------
+    def reset(self):
+        """Drop the rows; the trained quantizer and codebooks stay."""
+        self._lists._call("ivr_ivfpq_reset")
+        self._off_host = np.zeros(self.nlist + 1, np.int64)
+        self._off = torch.from_numpy(self._off_host).to(self.device)
+
+    def close(self):
+        """Release the index (lists, codebook holder and quantizer)."""
+        for x in (getattr(self, "_lists", None), getattr(self, "pq", None), getattr(self, "_coarse", None)):
+            if x is not None:
+                x.close()
+
+
+def IndexIVFPQ(quantizer, d, nlist, M, nbits=8, metric=METRIC_INNER_PRODUCT):
+    """faiss.IndexIVFPQ(quantizer, d, nlist, M, nbits, faiss.METRIC_INNER_PRODUCT) drop-in.  ValueError for nbits other than 8, for a
+    metric other than inner product, for M outside [1, IVR_PQ_MAX_M] or not dividing d, and for a quantizer IndexIVFFlat refuses: it
+    must be a plain (not id-mapped) FlatIPIndex of dimension d holding 0 rows (train() fills it) or exactly nlist rows."""
+    if int(nbits) != 8:
+        raise ValueError(f"IndexIVFPQ: only nbits=8 is supported, got {nbits}")
+    require_inner_product(metric, "IndexIVFPQ")
+    d, nlist, M = int(d), int(nlist), int(M)
+    if M < 1 or M > _ffi.IVR_PQ_MAX_M:
+        raise ValueError(f"IndexIVFPQ: M={M} outside [1,{_ffi.IVR_PQ_MAX_M}]")
+    if d < 1 or d > 65536 or d % M != 0:
+        raise ValueError(f"IndexIVFPQ: d={d} outside [1,65536] or not a multiple of M={M}")
+    if nlist < 1:
+        raise ValueError(f"IndexIVFPQ: nlist={nlist} < 1")
+    if not isinstance(quantizer, FlatIPIndex):
+        raise ValueError(f"IndexIVFPQ: the quantizer must be a FlatIPIndex, got {type(quantizer).__name__}")
+    check_quantizer(quantizer, d, nlist, "IndexIVFPQ")
+    return IVFPQIndex(d, nlist, M, _quantizer=quantizer)
