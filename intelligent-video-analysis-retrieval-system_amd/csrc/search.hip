@@ -426,7 +426,7 @@ __global__ __launch_bounds__(256) void rescore_groups_kernel(const float *__rest
             const int rl = (lane >> 4) * 4 + r;
             const int64_t row = (int64_t)g * kRows + t * 16 + rl;
             uint64_t key = 0;
-            if (MASK ? ((mw >> rl) & 1ull) != 0 : row < ntotal) key = ((uint64_t)ivr_f2ord(acc[r]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)row);
+            if (MASK ? ((mw >> rl) & 1ull) != 0 : row < ntotal) key = ivr_key(acc[r], (uint32_t)row);
             out[rl] = key;
         }
     }

@@ -96,15 +96,6 @@ __device__ __forceinline__ uint32_t bin_dist(const uint4 (&row)[W], const uint4 
     return d;
 }
 
-__device__ __forceinline__ uint32_t bin_wave_incl_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // Pass 1.  hist[q][dist] += 1 for every stored row.  A workgroup walks the 256-row blocks blockIdx.x, + gridDim.x, ... and keeps the
 // histograms of the chunk's queries in LDS; the bins that can matter go to the global histogram at the end.
 template <int W>
@@ -139,7 +130,7 @@ __global__ __launch_bounds__(256) void bin_hist_kernel(const uint4 *__restrict__
         for (int base = 0; base < nbins && below < (uint32_t)k; base += 64) {
             const int i = base + lane;
             const uint32_t c = i < nbins ? h[i] : 0u;
-            const uint32_t incl = below + bin_wave_incl_scan(c);
+            const uint32_t incl = below + ivr_wave_incl_scan(c);
             if (c && incl - c < (uint32_t)k) atomicAdd(&hist[qi * nbins + i], c);
             below = __shfl(incl, 63, 64);
         }
@@ -153,7 +144,7 @@ __global__ __launch_bounds__(64) void bin_thresh_kernel(const uint32_t *__restri
     uint32_t below = 0, t = (uint32_t)nbins, need = 0;
     for (int base = 0; base < nbins; base += 64) {
         const uint32_t c = base + lane < nbins ? h[base + lane] : 0u;
-        const uint32_t incl = below + bin_wave_incl_scan(c);
+        const uint32_t incl = below + ivr_wave_incl_scan(c);
         const uint64_t hit = __ballot(incl >= (uint32_t)k);
         if (hit) {
             const int first = __ffsll((unsigned long long)hit) - 1;
@@ -218,7 +209,7 @@ __global__ __launch_bounds__(256) void bin_scan_kernel(uint32_t *__restrict__ a,
             v[e] = buf[tid * (E + 1) + e];
             sum += v[e];
         }
-        const uint32_t incl = bin_wave_incl_scan(sum);
+        const uint32_t incl = ivr_wave_incl_scan(sum);
         if (lane == 63) ws[wave] = incl;
         __syncthreads();
         uint32_t woff = 0, tot = 0;

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void graph_search_kernel(GraphSearch a) {
             }
             for (; kc < kchunks; ++kc) mfma_chunk4(acc, qs[kc * 4 + g], pr ? pr[kc * 4] : zero);
             // every A row is the query: acc[0] of lane l < 16 = <query, survivor 16 wave + l>
-            if (lane < 16 && idx < nnew) s_new[idx] = ((uint64_t)ivr_f2ord(acc[0]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)s_row[idx]);
+            if (lane < 16 && idx < nnew) s_new[idx] = ivr_key(acc[0], (uint32_t)s_row[idx]);
         }
         __syncthreads();
         const int nbuf = buf ^ 1;

@@ -232,12 +232,7 @@ __device__ __forceinline__ uint32_t kept_before(const RemovePlan &p, int64_t g) 
 // exclusive prefix sum over the 256 threads of a block, and the block's total; wsum: LDS [4]
 __device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t *wsum, uint32_t &total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
+    const uint32_t inc = ivr_wave_incl_scan(v, lane);
     if (lane == 63) wsum[w] = inc;
     __syncthreads();
     uint32_t base = 0;

@@ -3,7 +3,8 @@
 // id table of an id-mapped index).  It holds what more
 // than one of them needs: the index object with the plan of a search, the view a search scans, the row mask of a filtered search, and
 // the launchers that are defined in one file and called from another.  search_rows.hip (gather / scatter of rows by position) uses it
-// too, and so do search_binary.hip, search_pq.hip and search_sq.hip for the coded-index structs at its end.  Not part of the C ABI.
+// too, and so do search_binary.hip, search_pq.hip and search_sq.hip for the coded-index structs at its end.  It also holds the device
+// helpers that every search file spells the same way: ivr_key, ivr_wave_incl_scan, ivr_last_le and probe_valid.  Not part of the C ABI.
 #pragma once
 #include "ivr_common.h"
 
@@ -99,6 +100,43 @@ __device__ __forceinline__ float4 ivr_load_quad(const float *__restrict__ row, i
     v.z = k0 + 2 < d ? row[k0 + 2] : 0.f;
     v.w = k0 + 3 < d ? row[k0 + 3] : 0.f;
     return v;
+}
+
+// The 64-bit result key of every top-k of the project: (ordered score, ~position).  The larger key ranks first, so equal scores rank
+// the LOWER position first; 0 is below every key and stands for "no row".
+__device__ __forceinline__ uint64_t ivr_key(float score, uint32_t pos) {
+    return ((uint64_t)ivr_f2ord(score) << 32) | (uint32_t)(0xFFFFFFFFu - pos);
+}
+
+// inclusive prefix sum over the 64 lanes of a wave (lane = threadIdx.x & 63, which most callers hold already)
+template <typename T>
+__device__ __forceinline__ T ivr_wave_incl_scan(T v, int lane = threadIdx.x & 63) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// the last i in [0, n) with off[i] <= v (off ascending, off[0] <= v): with empty runs (equal neighbours) that is the one run that
+// holds v
+__device__ __forceinline__ int ivr_last_le(const int64_t *off, int n, int64_t v) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= v) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// An inverted-file search names its lists in assign [nq][p], every row ascending (so a list named twice sits in adjacent entries and
+// counts once); entries outside [0, nlist) are skipped.  true: entry j of row a is the first mention of a valid list
+__device__ __forceinline__ bool probe_valid(const int64_t *__restrict__ a, int j, int p, int nlist) {
+    if (j >= p) return false;
+    const int64_t l = a[j];
+    return l >= 0 && l < nlist && (j == 0 || a[j - 1] != l);
 }
 
 // Grow-only device buffer: DevMem owns the block and frees it in its destructor, DevBuf<T> is the same block read as a T *.  Grown

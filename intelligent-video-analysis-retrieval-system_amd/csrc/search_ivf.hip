@@ -29,13 +29,6 @@ constexpr int64_t kIvfChunkSlots = 1ll << 25;
 // pairs of a chunk: bounds the pair tables (20 bytes per pair) at 80 MiB
 constexpr int64_t kIvfChunkPairs = 1ll << 22;
 
-// assign: [nq][p], every row ascending (so a list named twice sits in adjacent entries and counts once); entries outside [0, nlist)
-// are skipped.  true: entry j of row a is the first mention of a valid list
-__device__ __forceinline__ bool probe_valid(const int64_t *__restrict__ a, int j, int p, int nlist) {
-    if (j >= p) return false;
-    const int64_t l = a[j];
-    return l >= 0 && l < nlist && (j == 0 || a[j - 1] != l);
-}
 // rows of list l, clipped to the stored rows
 __device__ __forceinline__ void list_run(const int64_t *__restrict__ list_off, int64_t l, int64_t ntotal, int64_t &r0, int64_t &r1) {
     r0 = min(max(list_off[l], (int64_t)0), ntotal);
@@ -218,7 +211,7 @@ __global__ __launch_bounds__(256) void list_scan_kernel(ListScan a) {
             const int64_t row = t * 16 + (lane >> 4) * 4 + r;
             if (row < r0 || row >= r1) continue;
             const int64_t s = s_slot[col] + (row - r0);
-            if (s >= 0 && s < a.nkeys) a.keys[s] = ((uint64_t)ivr_f2ord(acc[r]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)row);
+            if (s >= 0 && s < a.nkeys) a.keys[s] = ivr_key(acc[r], (uint32_t)row);
         }
     }
 }

@@ -43,18 +43,6 @@ int ivfpq_words(int M) {
     return w <= 4 ? w : 8;
 }
 
-// the last l in [0, n) with off[l] <= v (off ascending, off[0] <= v): with empty lists (equal neighbours) that is the one list whose
-// run holds v
-__device__ __forceinline__ int ivfpq_find(const int64_t *__restrict__ off, int n, int64_t v) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= v) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // bytes [b0, b0 + 4) of a code as one little-endian word, zero past M
 __device__ __forceinline__ uint32_t ivfpq_code_word(const uint8_t *__restrict__ p, int b0, int M, bool vec) {
     if (vec && b0 + 4 <= M) return *reinterpret_cast<const uint32_t *>(p + b0);
@@ -76,7 +64,7 @@ __global__ __launch_bounds__(256) void ivfpq_pack_kernel(const uint8_t *__restri
     const int w = (int)(gw % w16);
     const int64_t g = gw / w16;
     if (g >= ngroups) return;
-    const int l = ivfpq_find(goff, nlist, g);
+    const int l = ivr_last_le(goff, nlist, g);
     const int64_t i = (g - goff[l]) * 64 + lane, r = list_off[l] + i;
     const bool valid = r < list_off[l + 1];
     uint4 v = uint4{0u, 0u, 0u, 0u};
@@ -102,7 +90,7 @@ __global__ __launch_bounds__(256) void ivfpq_unpack_kernel(const uint32_t *__res
     const int j = (int)(t % c4);
     if (i >= n) return;
     const int64_t r = start + i;
-    const int l = ivfpq_find(list_off, nlist, r);
+    const int l = ivr_last_le(list_off, nlist, r);
     const int64_t pos = goff[l] * 64 + (r - list_off[l]);
     if (out_codes) {
         const uint32_t x = data[((pos >> 6) * w16 * 64 + (int64_t)(j >> 2) * 64 + (pos & 63)) * 4 + (j & 3)];
@@ -110,14 +98,6 @@ __global__ __launch_bounds__(256) void ivfpq_unpack_kernel(const uint32_t *__res
             if (4 * j + b < M) out_codes[i * M + 4 * j + b] = (uint8_t)(x >> (8 * b));
     }
     if (out_ids && j == 0) out_ids[i] = ids[pos];
-}
-
-// assign: [nq][p], every row ascending (a list named twice sits in adjacent entries and counts once); entries outside [0, nlist) are
-// skipped.  true: entry j of row a is the first mention of a valid list
-__device__ __forceinline__ bool ivfpq_probe_valid(const int64_t *__restrict__ a, int j, int p, int nlist) {
-    if (j >= p) return false;
-    const int64_t l = a[j];
-    return l >= 0 && l < nlist && (j == 0 || a[j - 1] != l);
 }
 
 // One wave per query of the chunk.  A query whose lists hold more than max_groups groups (the caller's bound is wrong) probes
@@ -133,7 +113,7 @@ __global__ __launch_bounds__(64 * kIvfpqProbeQueries) void ivfpq_probe_kernel(co
     for (int j0 = 0; j0 < p; j0 += 64) {
         const int j = j0 + lane;
         int64_t size = 0;
-        if (ivfpq_probe_valid(a, j, p, nlist)) size = goff[a[j] + 1] - goff[a[j]];
+        if (probe_valid(a, j, p, nlist)) size = goff[a[j] + 1] - goff[a[j]];
         int64_t inc = size;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -243,7 +223,7 @@ __global__ __launch_bounds__(kIvfpqScanThreads) void ivfpq_scan_kernel(IvfpqScan
             bin_load_row<W>(a.data, g, row);
             const int64_t pos = g * 64 + lane;
             const float s = ivfpq_score_row<W>(row, lt, a.M, a.coarse ? a.coarse[(int64_t)q * a.p + j] : 0.f);
-            if (a.ids[pos] >= 0) key = ((uint64_t)ivr_f2ord(s) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)pos);
+            if (a.ids[pos] >= 0) key = ivr_key(s, (uint32_t)pos);
         }
         a.keys[(int64_t)q * a.qstride + (int64_t)u * 64 + lane] = key;
     }

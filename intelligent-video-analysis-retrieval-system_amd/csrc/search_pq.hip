@@ -44,7 +44,7 @@ struct SrcPqGroups {   // the group maxima of query q
     int64_t mstride;
     int64_t n;
     __device__ uint64_t key(int q, int64_t i) const {
-        return ((uint64_t)ivr_f2ord(gmax[(int64_t)q * mstride + i]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
+        return ivr_key(gmax[(int64_t)q * mstride + i], (uint32_t)i);
     }
 };
 struct SrcPqKeys {     // the re-scored rows of the selected groups
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void pq_keys_kernel(const uint4 *__restrict__ 
         float s[1];
         pq_score_rows<W, 1>(row, T + (p / ksel) * ((int64_t)M * kPqKsub), M, s);
         const int64_t r = (int64_t)g * 64 + lane;
-        if (r < ntotal) key = ((uint64_t)ivr_f2ord(s[0]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)r);
+        if (r < ntotal) key = ivr_key(s[0], (uint32_t)r);
     }
     keys[p * 64 + lane] = key;
 }

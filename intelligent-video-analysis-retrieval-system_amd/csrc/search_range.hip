@@ -80,17 +80,6 @@ __device__ __forceinline__ void range_pair_prefix(const uint32_t *__restrict__ n
     }
 }
 
-// query of flat pair p (pre[0] <= p < pre[nqc]): the largest q with pre[q] <= p
-__device__ __forceinline__ int range_pair_query(const int64_t *pre, int nqc, int64_t p) {
-    int lo = 0, hi = nqc - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pre[mid] <= p) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // One 16-row tile against the query column (lane & 15) of a tiled query tile with rescore_groups_kernel's accumulator sequence
 // (ascending K, x y z w per chunk): each score is bit-identical to the one ivr_index_search reports for that row.
 __device__ __forceinline__ f32x4 range_score_tile(const float4 *__restrict__ a, const float4 *__restrict__ b, int kchunks) {
@@ -168,7 +157,7 @@ __global__ __launch_bounds__(256) void range_rescore_kernel(const float *__restr
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t npairs = pre[nqc];
     for (int64_t p = (int64_t)blockIdx.x * 4 + wave; p < npairs; p += (int64_t)gridDim.x * 4) {
-        const int q = range_pair_query(pre, nqc, p);
+        const int q = ivr_last_le(pre, nqc, p);
         const int64_t at = (int64_t)q * cstride + (p - pre[q]);
         f32x4 acc[4];
         const uint64_t m = range_group_scores<MASK>(data, qtile, dp4, ntotal, cand[at], q, radius, acc, rm...);
@@ -233,7 +222,7 @@ __global__ __launch_bounds__(256) void range_write_kernel(const float *__restric
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t npairs = pre[nqc];
     for (int64_t p = (int64_t)blockIdx.x * 4 + wave; p < npairs; p += (int64_t)gridDim.x * 4) {
-        const int q = range_pair_query(pre, nqc, p);
+        const int q = ivr_last_le(pre, nqc, p);
         const int64_t at = (int64_t)q * cstride + (p - pre[q]);
         const uint64_t m = mask[at];
         if (m == 0) continue;

@@ -4,6 +4,7 @@
 // The unnamed namespace keeps them private to their file; tools/isa_compare.py reports an instantiation that two objects emit.
 #pragma once
 #include "ivr_common.h"
+#include "search_internal.h"
 
 #include <cfloat>
 
@@ -50,8 +51,7 @@ struct SrcGroupMax {   // pass 2: keys from the group-maximum column of query q
     int64_t mstride;
     int64_t n;
     __device__ uint64_t key(int q, int64_t i) const {
-        return ((uint64_t)ivr_f2ord(gmax[(int64_t)q * mstride + i]) << 32) |
-               (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
+        return ivr_key(gmax[(int64_t)q * mstride + i], (uint32_t)i);
     }
 };
 struct SrcTilesOf {    // large-batch scan, second level: the 16-row tile maxima of the 128-row blocks selected at the first level
@@ -66,7 +66,7 @@ struct SrcTilesOf {    // large-batch scan, second level: the 16-row tile maxima
         if (b == 0xFFFFFFFFu) return 0;
         const int64_t t = (int64_t)b * 8 + (i & 7);
         if (t >= ntiles) return 0;
-        return ((uint64_t)ivr_f2ord(tmax[(int64_t)q * tstride + t]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)t);
+        return ivr_key(tmax[(int64_t)q * tstride + t], (uint32_t)t);
     }
 };
 struct SrcKeys {       // pass 4: keys already materialised
@@ -83,7 +83,7 @@ struct SrcParts {      // shard merge: candidate p = part*k + j; ties resolve to
         const int64_t part = p / k, j = p % k;
         const int64_t off = (part * nq + q) * k + j;
         if (I[off] < 0) return 0;
-        return ((uint64_t)ivr_f2ord(D[off]) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)p);
+        return ivr_key(D[off], (uint32_t)p);
     }
 };
 
@@ -95,7 +95,7 @@ struct SrcPacked {     // shard merge straight from the all-gather buffer: candi
     __device__ uint64_t key(int q, int64_t p) const {
         const int32_t *c = at(q, p);
         if (c[2] < 0) return 0;                       // id -1: unused slot
-        return ((uint64_t)ivr_f2ord(__int_as_float(c[0])) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)p);
+        return ivr_key(__int_as_float(c[0]), (uint32_t)p);
     }
 };
 

@@ -1,10 +1,10 @@
 """FAISS-shaped inverted-file index over product-quantised codes (IndexIVFPQ, inner product, 8-bit codes) resident in MI355X HBM.
 
 The reference's `_create_index` (`core.py:1198-1230`) never builds an `IndexIVFPQ`; it is here because it is the compressed index
-faiss users deploy at scale, and the base `IndexRefineFlat` is usually paired with.  It joins the coarse quantizer of `IVFFlatIndex`
-(a `FlatIPIndex` of `nlist` centroids, the same k-means, the same `assign`) with the codes of `PQIndex`: a row is stored in the list of
-its best centroid as the `M`-byte code of its residual against that centroid (`by_residual`, the default, as in faiss) or of the row
-itself, and a search scores only the rows of the `nprobe` lists whose centroids score best against the query.
+faiss users deploy at scale, and the base `IndexRefineFlat` is usually paired with.  It joins the coarse side of `InvertedFileIndex`
+(`_ivf.py`, shared with `IVFFlatIndex`: quantizer, k-means, offsets, probe step) with the codes of `PQIndex`: a row is stored in the
+list of its best centroid as the `M`-byte code of its residual against that centroid (`by_residual`, the default, as in faiss) or of
+the row itself, and a search scores only the rows of the `nprobe` lists whose centroids score best against the query.
 
 With the inner product residual coding costs nothing at search time: `<q, c_l + r> = <q, c_l> + <q, r>`, so the `M x 256` lookup
 table of a query (`PQIndex.compute_tables_device`, unchanged) serves every list, and the only per-list term is the coarse score the
@@ -20,10 +20,10 @@ import torch
 
 from . import _ffi, _staging
 from ._coded import ENCODE_CHUNK
-from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product, search_numpy, to_numpy, typed_params
+from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product, to_numpy
+from ._ivf import InvertedFileIndex, check_quantizer
 from ._staging import dev_f32 as _dev_f32
 from .index import FlatIPIndex, _ids_i64
-from .ivf import IVFFlatIndex, SearchParametersIVF, _nearest, check_quantizer
 from .pq import KSUB, PQIndex
 
 
@@ -149,30 +149,25 @@ class _Lists(_ffi.Handle):
         self._open("ivr_ivfpq_create", device, int(M), int(nlist))
 
 
-class IVFPQIndex:
+class IVFPQIndex(InvertedFileIndex):
     """Inverted-file index over product-quantised codes (FAISS IndexIVFPQ contract, METRIC_INNER_PRODUCT, nbits = 8) on one GPU.
 
     search(x, k) looks at the rows of the nprobe lists nearest to each query and returns (D, I) as ivfpq_scan_ref defines them over
     the tables pq.compute_tables_device(x) and the quantizer's float32 scores of the probed centroids: float32 descending, int64
     labels, (-FLT_MAX, -1) padding.  Equal scores rank the row in the lower list first, and within a list the row added earlier.
     Every add() call regroups the whole index by list (one pass over all stored codes): add in large batches."""
+    _PARTS = ("_lists", "pq", "quantizer")
 
     def __init__(self, d, nlist, M, device=None, _quantizer=None):
         self.pq = _CodebookPQ(d, M, device=device if _quantizer is None else _quantizer.device.index)
         self.pq._owner = self
-        self._coarse = IVFFlatIndex(d, nlist, device=device, _quantizer=_quantizer)      # the coarse part; its own row store stays empty
-        self.d, self.nlist, self.M = self._coarse.d, self._coarse.nlist, self.pq.M
-        self.quantizer = self._coarse.quantizer
-        self.device = self.quantizer.device
-        self.code_size = self.M
+        super().__init__(d, nlist, device, _quantizer)
+        self.M = self.code_size = self.pq.M
         self.nbits = 8
-        self.metric_type = METRIC_INNER_PRODUCT
         self._by_residual = True
-        self._nprobe = 1
+        self._coarse_trained = False
         self._cent_dev = None
         self._lists = _Lists(self.M, self.nlist, self.device.index)
-        self._off_host = np.zeros(self.nlist + 1, np.int64)
-        self._off = torch.from_numpy(self._off_host).to(self.device)
 
     # -- attributes ------------------------------------------------------------------------------
     @property
@@ -181,17 +176,7 @@ class IVFPQIndex:
 
     @property
     def is_trained(self):
-        return bool(self.pq.is_trained and (self._coarse.is_trained or self.quantizer.ntotal == self.nlist))
-
-    @property
-    def nprobe(self):
-        return self._nprobe
-
-    @nprobe.setter
-    def nprobe(self, v):
-        if int(v) < 1:
-            raise ValueError(f"nprobe={v} < 1")
-        self._nprobe = int(v)
+        return bool(self.pq.is_trained and (self._coarse_trained or self.quantizer.ntotal == self.nlist))
 
     @property
     def by_residual(self):
@@ -205,34 +190,10 @@ class IVFPQIndex:
             raise RuntimeError("by_residual: the index is trained or holds rows coded with the current setting")
         self._by_residual = bool(v)
 
-    @property
-    def centroids(self):
-        """numpy float32 [nlist,d]: quantizer.reconstruct_n()."""
-        return self.quantizer.reconstruct_n()
-
     def _centroids_device(self):
         if self._cent_dev is None:
             self._cent_dev = self.quantizer.gather_device(torch.arange(self.nlist, dtype=torch.int64, device=self.device))
         return self._cent_dev
-
-    def _require_trained(self, what):
-        if not self.is_trained:
-            raise RuntimeError(f"{what}: the index is not trained")
-
-    def _check_list(self, l):
-        l = int(l)
-        if not 0 <= l < self.nlist:
-            raise ValueError(f"list {l} outside [0, {self.nlist})")
-        return int(self._off_host[l]), int(self._off_host[l + 1])
-
-    def list_sizes(self):
-        """int64 [nlist]: rows per list."""
-        return np.diff(self._off_host)
-
-    def list_ids(self, l):
-        """The labels of list l in stored order (numpy int64)."""
-        a, b = self._check_list(l)
-        return self._rows_device(a, b - a, codes=False)[1].cpu().numpy()
 
     def list_codes(self, l):
         """The codes of list l in stored order (numpy uint8 [size, M])."""
@@ -248,11 +209,13 @@ class IVFPQIndex:
             self._lists._call("ivr_ivfpq_get_codes", int(start), int(n), c, i)
         return c, i
 
+    def _ids_device(self, start=0, n=None):
+        return self._rows_device(start, n, codes=False)[1]
+
     def _set_lists(self, codes, ids, off_host):
         self._lists._call("ivr_ivfpq_set_lists", codes, ids, off_host.ctypes.data, len(codes))
         torch.cuda.current_stream(self.device).synchronize()      # codes and ids may be temporaries
-        self._off_host = off_host
-        self._off = torch.from_numpy(off_host).to(self.device)
+        self._set_offsets(off_host)
 
     # -- training --------------------------------------------------------------------------------
     def train(self, x, niter=10, seed=1234, max_points_per_centroid=256, spherical=True):
@@ -262,44 +225,30 @@ class IVFPQIndex:
         if self.ntotal:
             raise RuntimeError(f"train: the index holds {self.ntotal} rows encoded with the current codebooks")
         _staging.check_rows(x, self.d, "train")
-        self._coarse.train(x, niter=niter, seed=seed, max_points_per_centroid=max_points_per_centroid, spherical=spherical)
+        self._train_quantizer(x, niter, seed, max_points_per_centroid, spherical)
+        self._coarse_trained = True
         self._cent_dev = None
         with torch.cuda.device(self.device):
             t = _dev_f32(x, self.device)
-            self.pq.train(self._residuals(t, _nearest(self.quantizer, t).clamp_(0, self.nlist - 1)) if self._by_residual else t)
+            self.pq.train(self._residuals(t, self._assign_device(t)) if self._by_residual else t)
 
     def _residuals(self, t, lists):
         return t - self._centroids_device()[lists]
 
     # -- adding ----------------------------------------------------------------------------------
-    def assign(self, x):
-        """The list of each row of x (numpy int64 [n]): the quantizer's own search(x, 1), so equal scores pick the lower list."""
-        self._require_trained("assign")
-        return self.quantizer.search(x, 1)[1][:, 0]
-
-    def add(self, x):
-        """Append rows labelled ntotal, ntotal + 1, ... as faiss does.  See add_with_ids."""
-        n = len(x) if isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim == 2 else 0
-        self.add_with_ids(x, np.arange(self.ntotal, self.ntotal + n, dtype=np.int64), _what="add")
-
-    def add_with_ids(self, x, ids, _what="add_with_ids"):
+    def add_with_ids(self, x, ids, *, _what="add_with_ids"):
         """Append rows under caller-chosen int64 labels (>= 0, duplicates allowed).  Each row goes to the list of its best centroid
         and only its code is kept: pq's encoder applied to its residual against that centroid (to the row itself without
         by_residual).  The whole index is regrouped by list in every call: one pass over all stored codes (unpack, a stable argsort
         of the list numbers, pack), so add in large batches.  RuntimeError while untrained."""
-        self._require_trained(_what)
-        _staging.check_rows(x, self.d, _what)
-        n = len(x)
-        ids = _ids_i64(ids, n, _what)
-        if n and int(ids.min()) < 0:
-            raise ValueError(f"{_what}: negative id {int(ids.min())} (-1 labels an unused result slot)")
-        if n == 0:
+        ids = self._new_ids(x, ids, _what)
+        if len(ids) == 0:
             return
         with torch.cuda.device(self.device):
             codes, lists = [], []
-            for i in range(0, n, ENCODE_CHUNK):
+            for i in range(0, len(ids), ENCODE_CHUNK):
                 t = _dev_f32(x[i:i + ENCODE_CHUNK], self.device)
-                l = _nearest(self.quantizer, t).clamp_(0, self.nlist - 1)
+                l = self._assign_device(t)
                 codes.append(self.pq._encode_device(self._residuals(t, l) if self._by_residual else t))
                 lists.append(l)
             codes, lists = torch.cat(codes), torch.cat(lists)
@@ -310,8 +259,7 @@ class IVFPQIndex:
                 codes = torch.cat([old_codes, codes])
                 new_ids = torch.cat([old_ids, new_ids])
                 lists = torch.cat([torch.repeat_interleave(torch.arange(self.nlist, device=self.device), sizes), lists])
-            order = torch.argsort(lists, stable=True)
-            off = np.concatenate([[0], np.cumsum(torch.bincount(lists, minlength=self.nlist).cpu().numpy())]).astype(np.int64)
+            order, off = self._regroup(lists)
             self._set_lists(codes[order].contiguous(), new_ids[order].contiguous(), off)
 
     # -- search ----------------------------------------------------------------------------------
@@ -319,45 +267,24 @@ class IVFPQIndex:
         """pq.compute_tables_device(x): float32 CUDA [nq,M,256], the same for every list."""
         return self.pq.compute_tables_device(x)
 
-    def _queries(self, x, k, what):
-        t, staged = _staging.queries_f32(_staging.as_rows(x), self.d, self.device)
-        k = _staging.check_k(k, _ffi.IVR_MAX_K)
-        self._require_trained(what)
-        _staging.check_nq(t.shape[0])
-        return t, k, staged
-
     def _coarse_scores(self, t, assign):
         """float32 CUDA [nq,p]: the quantizer's inner product of query i with centroid assign[i,j], with the bits its search reports
         (-FLT_MAX for a -1 entry, which the scan skips)."""
         step = _ffi.IVR_MAX_K
         return torch.cat([self.quantizer.rescore_device(t, assign[:, j:j + step].contiguous())[0] for j in range(0, assign.shape[1], step)], dim=1)
 
-    def search(self, x, k, params=None):
-        """(D, I) numpy arrays, over the rows of the nprobe lists nearest to each query.  params = SearchParametersIVF(nprobe=...)
-        overrides nprobe for this call; a selector raises ValueError."""
-        params = typed_params(params, SearchParametersIVF, "IVFPQIndex")
-        return search_numpy(self, x, k, nprobe=None if params is None else params.nprobe)
-
     def search_device(self, x, k, nprobe=None):
         """Device-resident search: CUDA tensors, no host synchronisation (unless x had to be staged).  nprobe (default: the attribute)
         is clipped to nlist; below nlist it is the k of the coarse search and so at most IVR_MAX_K.  With nprobe >= nlist there is no
         coarse search: every list is probed, with the coarse scores search_preassigned computes."""
         t, k, staged = self._queries(x, k, "search")
-        nprobe = min(self.nprobe if nprobe is None else int(nprobe), self.nlist)
-        if nprobe < 1:
-            raise ValueError(f"nprobe={nprobe} < 1")
+        _staging.check_nq(t.shape[0])
         with torch.cuda.device(self.device):
-            coarse = None
-            if nprobe >= self.nlist:
-                assign = torch.arange(self.nlist, dtype=torch.int64, device=self.device).expand(t.shape[0], -1).contiguous()
-                if self._by_residual:
-                    coarse = self._coarse_scores(t, assign)
-            else:
-                if nprobe > _ffi.IVR_MAX_K:
-                    raise ValueError(f"nprobe={nprobe} outside [1,{_ffi.IVR_MAX_K}] (or >= nlist)")
-                coarse, assign = self.quantizer.search_device(t, nprobe)
-                if not self._by_residual:
-                    coarse = None
+            coarse, assign = self._probe(t, nprobe)
+            if not self._by_residual:
+                coarse = None
+            elif coarse is None:         # every list: the scores search_preassigned computes
+                coarse = self._coarse_scores(t, assign)
             out = self._scan(self.pq.compute_tables_device(t), coarse, assign, k)
             _staging.sync_if_staged(staged, self.device)
             return out
@@ -372,8 +299,9 @@ class IVFPQIndex:
     def search_preassigned_device(self, x, k, assign, coarse_dis=None):
         """search_preassigned returning CUDA tensors; the range check of assign synchronises once."""
         t, k, staged = self._queries(x, k, "search_preassigned")
+        _staging.check_nq(t.shape[0])
         with torch.cuda.device(self.device):
-            assign = self._assign(assign, t.shape[0], "search_preassigned")
+            assign = self._assign_arg(assign, t.shape[0], "search_preassigned")
             coarse = None
             if self._by_residual:
                 coarse = self._coarse_scores(t, assign) if coarse_dis is None else self._coarse_arg(coarse_dis, assign, "search_preassigned")
@@ -392,18 +320,10 @@ class IVFPQIndex:
         k = _staging.check_k(k, _ffi.IVR_MAX_K)
         _staging.check_nq(t.shape[0])
         with torch.cuda.device(self.device):
-            assign = self._assign(assign, t.shape[0], "search_tables_preassigned")
+            assign = self._assign_arg(assign, t.shape[0], "search_tables_preassigned")
             out = self._scan(t, None if coarse is None else self._coarse_arg(coarse, assign, "search_tables_preassigned"), assign, k)
             _staging.sync_if_staged(True, self.device)       # T, coarse and assign may all be staged copies
             return out
-
-    def _assign(self, assign, nq, what):
-        assign = _staging.int_tensor(assign, f"{what}: assign", np_dtype=np.int64)
-        if assign.dim() != 2 or assign.shape[0] != nq or assign.shape[1] < 1:
-            raise ValueError(f"{what}: assign must be [{nq},p] with p >= 1, got {tuple(assign.shape)}")
-        assign = assign.to(device=self.device, dtype=torch.int64)
-        _staging.check_entries(assign, self.nlist, f"{what}: assign entries")
-        return assign
 
     def _coarse_arg(self, coarse, assign, what):
         c = _dev_f32(coarse, self.device)
@@ -415,11 +335,9 @@ class IVFPQIndex:
         """assign: int64 CUDA [nq,p], entries in [-1, nlist).  The kernel wants every row ascending (a repeated list is then adjacent);
         the sort is stable, so the first mention of a list keeps its coarse score."""
         nq, p = assign.shape
-        assign, order = torch.sort(assign, dim=1, stable=True)
-        if coarse is not None:
-            coarse = torch.gather(coarse, 1, order).contiguous()
+        assign, coarse = self._ascending(assign, coarse, stable=True)
         D, I = _staging.alloc_DI(nq, k, self.device)
-        self._lists._call("ivr_ivfpq_search", T, coarse, assign.contiguous(), nq, p, k, D, I)
+        self._lists._call("ivr_ivfpq_search", T, coarse, assign, nq, p, k, D, I)
         return D, I
 
     # -- reconstruction --------------------------------------------------------------------------
@@ -465,14 +383,7 @@ class IVFPQIndex:
     def reset(self):
         """Drop the rows; the trained quantizer and codebooks stay."""
         self._lists._call("ivr_ivfpq_reset")
-        self._off_host = np.zeros(self.nlist + 1, np.int64)
-        self._off = torch.from_numpy(self._off_host).to(self.device)
-
-    def close(self):
-        """Release the index (lists, codebook holder and quantizer)."""
-        for x in (getattr(self, "_lists", None), getattr(self, "pq", None), getattr(self, "_coarse", None)):
-            if x is not None:
-                x.close()
+        self._set_offsets(np.zeros(self.nlist + 1, np.int64))
 
 
 def IndexIVFPQ(quantizer, d, nlist, M, nbits=8, metric=METRIC_INNER_PRODUCT):

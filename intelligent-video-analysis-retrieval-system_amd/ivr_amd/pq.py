@@ -5,7 +5,8 @@ The reference's `_create_index` (`core.py:1198-1230`) never builds an `IndexPQ`;
 of the codebook of slice `m` (coordinates `m * dsub .. (m + 1) * dsub`, `dsub = d / M`), and a search ranks the rows by a sum of `M`
 table lookups: the asymmetric (query-to-code) inner product.  The encoder, the table builder and the scan are HIP kernels of
 libivr_hip.so (csrc/search_pq.hip); the codes live in a `BinaryFlatIndex` of `8 * M` bits, as those of `IndexLSH` do; torch stages
-arrays, orders the rows of a k-means step and gathers codebook rows for `sa_decode`.
+arrays, orders the rows of a k-means step and gathers codebook rows for `sa_decode`.  The k-means around the encoder's assignment (sample,
+segment means, repair of empty clusters) is `_kmeans.py`'s, shared with the coarse quantizer of the inverted-file indexes.
 
 What the kernels are pinned to is stated by the numpy functions below: `pq_encode_ref`, `pq_tables_ref` (float64 references with the
 tolerances in their docstrings) and `pq_scan_ref` (the float32 additions of the scan, which numpy reproduces to the bit).
@@ -17,12 +18,11 @@ to the rounding stated in `pq_encode_ref`.
 import numpy as np
 import torch
 
-from . import _ffi, _staging
+from . import _ffi, _kmeans, _staging
 from ._coded import DecodableIndex
 from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
 from ._staging import dev_f32 as _dev_f32, dev_u8 as _dev_u8
 from .binary import BinaryFlatIndex
-from .ivf import kmeans_sample, split_empty_clusters
 
 KSUB = 256                    # centroids per slice: nbits = 8
 
@@ -158,50 +158,31 @@ class PQIndex(DecodableIndex):
     # -- training --------------------------------------------------------------------------------
     def train(self, x, niter=25, seed=1234, max_points_per_centroid=256):
         """Make the M codebooks by k-means on x [n,d], n >= 256 (ValueError otherwise):
-          sample   kmeans_sample(n, 256, max_points_per_centroid, seed): one sample serves all slices, and the initial codebook of
+          sample   _kmeans.kmeans_sample(n, 256, max_points_per_centroid, seed): one sample serves all slices, and the initial codebook of
                    slice m is slice m of its first 256 rows
           iterate  niter times: assign every sampled row's slices with the encoder (ivr_pq_encode: equal distances pick the lower
                    centroid), order the rows of each slice by code (stable), take the mean of every run (ivr_segment_mean with
                    spherical=False: fixed summation order, so a seed gives the same bits every time), repair empty clusters
-                   (split_empty_clusters, per slice)."""
+                   (split_empty_clusters, per slice).  The loop's shared halves are those of _kmeans.py."""
         self._require_empty("train", "codebooks")
         _staging.check_rows(x, self.d, "train")
         n = len(x)
         if n < KSUB:
             raise ValueError(f"train: {n} training rows for {KSUB} centroids per slice")
-        niter = int(niter)
-        if niter < 0:
-            raise ValueError(f"train: niter={niter} < 0")
+        niter = _kmeans.check_niter(niter)
         with torch.cuda.device(self.device):
-            sample = torch.from_numpy(kmeans_sample(n, KSUB, max_points_per_centroid, seed))
-            if isinstance(x, torch.Tensor) and x.is_cuda:
-                xs = _dev_f32(x, self.device)[sample.to(self.device)].contiguous()
-            else:       # only the sample travels to the device
-                xs = _dev_f32(x[sample.numpy()] if isinstance(x, np.ndarray) else x[sample], self.device)
+            xs = _kmeans.sample_rows(x, KSUB, max_points_per_centroid, seed, self.device)
             cent = xs[:KSUB].reshape(KSUB, self.M, self.dsub).permute(1, 0, 2).contiguous()
             for _ in range(niter):
                 cent = self._kmeans_step(xs, cent)
             self._set_centroids(cent.cpu().numpy(), cent)
 
     def _kmeans_step(self, xs, cent):
-        ns = len(xs)
         a = self._encode_device(xs, cent).t().contiguous().to(torch.int64)        # [M, ns]
-        order = torch.argsort(a, dim=1, stable=True)
-        zero = torch.zeros(1, dtype=torch.int64, device=self.device)
+        order = torch.argsort(a, dim=1, stable=True)        # one batched sort for all slices
         out = torch.empty_like(cent)
-        counts = []
-        for m in range(self.M):
-            rows = xs[order[m], m * self.dsub:(m + 1) * self.dsub].contiguous()
-            counts.append(torch.bincount(a[m], minlength=KSUB))
-            off = torch.cat([zero, torch.cumsum(counts[m], 0)]).contiguous()
-            _ffi.call("ivr_segment_mean", _ffi.CTX, rows, ns, off, KSUB, self.dsub, False, out[m], device=self.device)
-        counts = torch.stack(counts).cpu().numpy()
-        if (counts == 0).any():
-            c = out.cpu().numpy()
-            for m in np.flatnonzero((counts == 0).any(axis=1)):
-                split_empty_clusters(c[m], counts[m])
-            out = torch.from_numpy(c).to(self.device)
-        return out
+        counts = [_kmeans.segment_means(xs[:, m * self.dsub:(m + 1) * self.dsub], a[m], KSUB, out[m], order=order[m]) for m in range(self.M)]
+        return _kmeans.repair_empty_clusters(out, torch.stack(counts).cpu().numpy())
 
     # -- FAISS surface ---------------------------------------------------------------------------
     def compute_tables_device(self, x):

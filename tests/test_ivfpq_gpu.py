@@ -263,6 +263,70 @@ def test_lists_after_add_hold_the_encoder_codes_of_the_residuals(M, by_residual)
     idx.close()
 
 
+# -- the shared layer ----------------------------------------------------------------------------------------------------------
+def test_an_index_holds_no_row_store_but_its_own():
+    """A constructed IVFPQIndex reaches, through its instance attributes, no IVFFlatIndex and no FlatIPIndex other than its quantizer:
+    the coarse side is the shared layer's, not a second index with an empty row store."""
+    from ivr_amd.index import FlatIPIndex
+    from ivr_amd.ivf import IVFFlatIndex
+    from ivr_amd.ivfpq import IVFPQIndex
+    idx = IVFPQIndex(32, 4, 4)
+    seen, stack, found = set(), [idx], []
+    while stack:
+        o = stack.pop()
+        if id(o) in seen:
+            continue
+        seen.add(id(o))
+        if isinstance(o, (IVFFlatIndex, FlatIPIndex)):
+            found.append(o)
+        if isinstance(o, dict):
+            stack.extend(o.values())
+        elif isinstance(o, (list, tuple, set)):
+            stack.extend(o)
+        elif type(o).__module__.startswith("ivr_amd"):
+            stack.extend(vars(o).values())
+    assert len(found) == 1 and found[0] is idx.quantizer
+    idx.close()
+    idx.close()                                                    # harmless
+
+
+@pytest.mark.parametrize("spherical, by_residual, repair", [(True, True, False), (False, False, False), (True, False, True), (False, True, True)])
+def test_training_is_the_coarse_training_then_the_pq_training(monkeypatch, spherical, by_residual, repair):
+    """IVFPQIndex.train leaves the quantizer with the bits IVFFlatIndex.train gives on the same rows and arguments, and the codebooks
+    with the bits PQIndex.train gives on the float32 residuals x - centroids[assign(x)] (on x without by_residual).  repair: two
+    sampled rows are equal, so an initial centroid and (same permutation, same rows or residuals) an initial codebook entry of every
+    slice start empty and both trainings go through the repair of empty clusters, which the test watches being called."""
+    from ivr_amd import _kmeans
+    from ivr_amd.ivf import IVFFlatIndex, kmeans_sample
+    from ivr_amd.ivfpq import IVFPQIndex
+    from ivr_amd.pq import PQIndex
+    n, d, nlist, M = 2048, 32, 8, 4
+    x = unit_rows(np.random.default_rng(77), n, d)
+    if repair:
+        first = kmeans_sample(n, nlist)[:nlist]
+        x[first[1]] = x[first[0]]
+    split, repaired = _kmeans.split_empty_clusters, []              # the shapes of the centroid sets that had an empty cluster
+    monkeypatch.setattr(_kmeans, "split_empty_clusters", lambda c, n: repaired.append(c.shape) or split(c, n))
+    idx = IVFPQIndex(d, nlist, M)
+    idx.by_residual = by_residual
+    idx.train(x, spherical=spherical)
+    if repair:
+        assert (nlist, d) in repaired and (256, d // M) in repaired
+    del repaired[:]
+    flat = IVFFlatIndex(d, nlist)
+    flat.train(x, spherical=spherical)
+    assert ((nlist, d) in repaired) == repair
+    cent = flat.centroids
+    assert np.isfinite(cent).all() and np.array_equal(bits(idx.centroids), bits(cent))
+    pq = PQIndex(d, M)
+    del repaired[:]
+    pq.train(x - cent[idx.assign(x)] if by_residual else x)
+    assert not repair or (256, d // M) in repaired
+    assert np.isfinite(pq.centroids).all() and np.array_equal(bits(idx.pq.centroids), bits(pq.centroids))
+    for i in (idx, flat, pq):
+        i.close()
+
+
 # -- end to end ----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def trained_rows():
