@@ -571,6 +571,50 @@ int ivr_sq_index_search(ivr_sq_index *idx, const int16_t *t /*DEV [nq][d]*/, con
                         const float *bias /*DEV [nq]*/, int nq, int k, float *D /*DEV [nq][k]*/, int64_t *I /*DEV [nq][k]*/,
                         ivr_stream stream);
 
+/* ---- inverted lists over scalar-quantiser codes (faiss IndexIVFScalarQuantizer, QT_8bit, inner product) -----------------
+ * The coarse quantizer of the inverted-file index joined with the codes of the scalar quantiser ("inverted
+ * lists over SQ codes"; the definitions are the numpy functions ivfsq_pack_ref, ivfsq_unpack_ref and ivfsq_scan_ref of
+ * ivr_amd/ivfsq.py).  The object mirrors ivr_ivfpq entry for entry.  It stores d-byte codes ordered by list, every list padded to
+ * whole 64-row groups; over the packed positions (64 goff[l] + i for row i of list l, goff = the groups in front of the list) the
+ * layout is that of ivr_sq_index: signed c' = code - 128, K padded with zeros to a multiple of 64, tiled per 16 positions (pad bytes
+ * and pad rows zero), and the int64 label of every packed position (-1 on a pad row).  Training, the coarse assignment, the encoding
+ * of residuals and the integer form of the queries are the caller's (ivr_sq_encode, ivr_sq_query as they are).  Packed positions,
+ * pads included, stay below 2^32.  One stream at a time per handle. */
+#define IVR_SQ_MAX_D 1024
+typedef struct ivr_ivfsq ivr_ivfsq;
+int ivr_ivfsq_create(ivr_ctx *ctx, int d, int nlist, ivr_ivfsq **out);     /* 1 <= d <= IVR_SQ_MAX_D, nlist >= 1; holds no rows */
+int ivr_ivfsq_destroy(ivr_ivfsq *idx);
+int ivr_ivfsq_reset(ivr_ivfsq *idx);                         /* ntotal = 0, every list empty */
+int64_t ivr_ivfsq_ntotal(ivr_ivfsq *idx);
+/* Replace the content: n rows ordered by list, list l = rows [list_off[l], list_off[l + 1]) with list_off[0] = 0 and list_off[nlist]
+ * = n (IVR_ERR_INVALID otherwise, and for more than 2^32 packed positions).  codes as ivr_sq_encode makes them (unsigned).  Every
+ * label must be >= 0 (the labels live on the device and are not checked here).  list_off is read on the HOST during the call; codes
+ * and ids are packed by one kernel on `stream` and may be released once it has run.  When the call fails after its arguments were
+ * accepted (allocation, copy or launch), the object is left empty.  Synchronises the device first (a search in flight still reads the
+ * old lists) and allocates when the content outgrows the buffers. */
+int ivr_ivfsq_set_lists(ivr_ivfsq *idx, const uint8_t *codes /*DEV [n][d]*/, const int64_t *ids /*DEV [n]*/,
+                        const int64_t *list_off /*HOST [nlist + 1]*/, int64_t n, ivr_stream stream);
+/* the codes and / or labels of the list-ordered rows [start, start + n) as they were set; start + n <= ntotal */
+int ivr_ivfsq_get_codes(ivr_ivfsq *idx, int64_t start, int64_t n, uint8_t *codes /*DEV [n][d] or NULL*/, int64_t *ids /*DEV [n] or NULL*/,
+                        ivr_stream stream);
+/* Integer-scored top k over the lists each query probes.  assign[i] names the lists of query i in ASCENDING order: an entry outside
+ * [0, nlist) is skipped, a list named twice (adjacent entries) counts once, with the coarse score of its first entry.  For a row with
+ * stored bytes c' in the list of entry j, acc = sum_m t[i][m] * c'[m] exact in int32 (t as ivr_sq_query makes it; a |t| beyond 16256
+ * is clamped to it) and D = ((float(acc) * scale[i]) + bias[i]) + coarse[i][j]: one conversion to nearest-even, one float32
+ * multiplication and two float32 additions in this order, no fused multiply-add (coarse == NULL: +0.0).  D / I under the contract of
+ * ivr_index_search: D descending (-0.0 counts and is reported as +0.0), equal D the row in the lower list first and inside a list the
+ * row set earlier, I the row's label, unused slots -FLT_MAX / -1.  1 <= k <= IVR_MAX_K, nq >= 1, p >= 1.  The queries are staged
+ * once per call into their two int8 halves; then per chunk of queries, on `stream` and without a host round trip: the probe tables
+ * of ivr_index_search_lists (pairs grouped by list, 16-query pair tiles, one key slot per probed row), the list scan (a workgroup per
+ * (pair tile, 256-row split) gathers both halves of its up to 16 queries into LDS, 2 KiB per 64 coordinates, and reads every 16-row
+ * tile of its split once for two v_mfma_i32_16x16x64_i8 per K step) and select_topk.  Scratch: 2 ceil(d / 64) 64 bytes per query, and
+ * per chunk (at most 2^25 key slots, one query's at least, and 2^22 pairs) 8 bytes per row of the p longest lists per query and
+ * 20 p + 8 bytes per query; grow-only.  Enqueue-only once the scratch has grown (a call that grows it allocates and cannot be
+ * captured into a hipGraph). */
+int ivr_ivfsq_search(ivr_ivfsq *idx, const int16_t *t /*DEV [nq][d]*/, const float *scale /*DEV [nq]*/, const float *bias /*DEV [nq]*/,
+                     const float *coarse /*DEV [nq][p] or NULL*/, const int64_t *assign /*DEV [nq][p]*/, int nq, int p, int k,
+                     float *D /*DEV [nq][k]*/, int64_t *I /*DEV [nq][k]*/, ivr_stream stream);
+
 /* ---- graph index (in the place of faiss IndexHNSWFlat) ------------------------------------------------------
  * Stands in for faiss.IndexHNSWFlat(dimension, 32), the IndexHNSW type of _create_index (core.py:1213-1214).  It is NOT a port of
  * faiss's HNSW: one layer of fixed out-degree (2 M, HNSW's level-0 width), built in bulk from exact kNN lists, entered through

@@ -17,124 +17,13 @@
 //   probe_fill    one thread per pair: the pairs grouped by list
 //   list_scan     one workgroup per (pair tile, row split): scores -> keys
 //   select_topk   one workgroup per query
+// The four probe kernels, list_run and SrcSlots are in search_lists.h: search_ivfsq.hip builds the same tables.
 #include "ivr_common.h"
 #include "search_internal.h"
+#include "search_lists.h"
 #include "search_select.h"
 
 namespace {
-
-// keys of the scratch a chunk of queries may fill: 2^25 slots of 8 bytes = 256 MiB, plus one query's stretch when a single query
-// probes more rows than that (its stretch is never split)
-constexpr int64_t kIvfChunkSlots = 1ll << 25;
-// pairs of a chunk: bounds the pair tables (20 bytes per pair) at 80 MiB
-constexpr int64_t kIvfChunkPairs = 1ll << 22;
-
-// rows of list l, clipped to the stored rows
-__device__ __forceinline__ void list_run(const int64_t *__restrict__ list_off, int64_t l, int64_t ntotal, int64_t &r0, int64_t &r1) {
-    r0 = min(max(list_off[l], (int64_t)0), ntotal);
-    r1 = min(max(list_off[l + 1], r0), ntotal);
-}
-
-// One wave per query of the chunk.  slot[q][j] = first slot of entry j's list in the scratch (q * qstride + the rows of the query's
-// earlier lists), -1 for a skipped entry; qtotal[q] = the rows the query probes.  A query whose lists hold more than qstride rows
-// (the caller's bound is wrong) probes nothing rather than write past its stretch.
-__global__ __launch_bounds__(256) void probe_slots_kernel(const int64_t *__restrict__ assign, int p, int nqc, const int64_t *__restrict__ list_off,
-                                                          int nlist, int64_t ntotal, int64_t qstride, int64_t *__restrict__ slot,
-                                                          int64_t *__restrict__ qtotal) {
-    const int lane = threadIdx.x & 63;
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= nqc) return;
-    const int64_t *a = assign + (int64_t)q * p;
-    int64_t total = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        const bool fits = total <= qstride;          // pass 1 only: the total of pass 0
-        int64_t carry = 0;
-        for (int j0 = 0; j0 < p; j0 += 64) {
-            const int j = j0 + lane;
-            const bool valid = probe_valid(a, j, p, nlist);
-            int64_t size = 0;
-            if (valid) {
-                int64_t r0, r1;
-                list_run(list_off, a[j], ntotal, r0, r1);
-                size = r1 - r0;
-            }
-            int64_t inc = size;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int64_t t = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += t;
-            }
-            if (pass == 1 && j < p) slot[(int64_t)q * p + j] = valid && fits ? (int64_t)q * qstride + carry + inc - size : -1;
-            carry += __shfl(inc, 63, 64);
-        }
-        total = carry;
-    }
-    if (lane == 0) qtotal[q] = total <= qstride ? total : 0;
-}
-
-__global__ __launch_bounds__(256) void probe_count_kernel(const int64_t *__restrict__ assign, const int64_t *__restrict__ slot, int64_t npairs,
-                                                          int *__restrict__ count) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < npairs && slot[i] >= 0) atomicAdd(&count[assign[i]], 1);
-}
-
-// one workgroup of 256 threads: pair_off[l] = pairs of the lists below l, tile_off[l] = their 16-query pair tiles, l <= nlist; the
-// counts become the fill cursors (zero)
-__global__ __launch_bounds__(256) void probe_offsets_kernel(int *__restrict__ count, int nlist, int64_t *__restrict__ pair_off,
-                                                            int64_t *__restrict__ tile_off) {
-    __shared__ int64_t wp[4], wt[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int64_t cp = 0, ct = 0;                          // carried over the rounds
-    for (int l0 = 0; l0 <= nlist; l0 += 256) {
-        const int l = l0 + threadIdx.x;
-        const int64_t c = l < nlist ? count[l] : 0, t = (c + 15) >> 4;
-        if (l < nlist) count[l] = 0;
-        int64_t ip = c, it = t;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t a = __shfl_up(ip, o, 64), b = __shfl_up(it, o, 64);
-            if (lane >= o) {
-                ip += a;
-                it += b;
-            }
-        }
-        if (lane == 63) {
-            wp[w] = ip;
-            wt[w] = it;
-        }
-        __syncthreads();
-        int64_t bp = cp, bt = ct, tp = 0, tt = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (i < w) {
-                bp += wp[i];
-                bt += wt[i];
-            }
-            tp += wp[i];
-            tt += wt[i];
-        }
-        if (l <= nlist) {
-            pair_off[l] = bp + ip - c;
-            tile_off[l] = bt + it - t;
-        }
-        cp += tp;
-        ct += tt;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void probe_fill_kernel(const int64_t *__restrict__ assign, const int64_t *__restrict__ slot, int p, int64_t npairs,
-                                                         int *__restrict__ cursor, const int64_t *__restrict__ pair_off,
-                                                         int *__restrict__ pair_q, int64_t *__restrict__ pair_slot) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= npairs) return;
-    const int64_t s = slot[i];
-    if (s < 0) return;
-    const int64_t l = assign[i];
-    const int64_t at = pair_off[l] + atomicAdd(&cursor[l], 1);      // the order of a list's queries does not reach the result
-    pair_q[at] = (int)(i / p);
-    pair_slot[at] = s;
-}
 
 struct ListScan {
     const float4 *data;          // the float32 tiles of the storage
@@ -215,14 +104,6 @@ __global__ __launch_bounds__(256) void list_scan_kernel(ListScan a) {
         }
     }
 }
-
-struct SrcSlots {      // the keys of query q: slots [q * qstride, q * qstride + qtotal[q]) of the scratch
-    const uint64_t *keys;
-    const int64_t *qtotal;
-    int64_t qstride;
-    int64_t n;         // the longest stretch a query of the launch may hold
-    __device__ uint64_t key(int q, int64_t i) const { return i < qtotal[q] ? keys[(int64_t)q * qstride + i] : 0; }
-};
 
 // ---------------------------------------------------------------------------------------------
 // ivr_segment_mean

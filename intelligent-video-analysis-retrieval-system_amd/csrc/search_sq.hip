@@ -21,9 +21,11 @@
 //               (ivr_ord2f, a bijection of 32-bit patterns)
 //   sq_finish   D = float(acc) * scale + bias from that word: one conversion, one multiplication, one addition
 // Scratch (grow-only, on the index object): both halves of the staged queries and, in its GroupTopK, 4 bytes per (query, group) and
-// 520 per (query, selected group) of a chunk.
+// 520 per (query, selected group) of a chunk.  sq_stage_kernel, sq_frag, sq_combine and SQ_NO_CONTRACT are in search_lists.h:
+// search_ivfsq.hip stages its queries and combines its halves the same way.
 #include "ivr_common.h"
 #include "search_internal.h"
+#include "search_lists.h"
 #include "search_select.h"
 
 #include <cfloat>
@@ -39,8 +41,6 @@ struct ivr_sq_index : CodeRows {         // data: [cap / 16][ksteps][64], group_
 };
 
 namespace {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSqMaxD = 1024;                // 16256 * 128 * d fits int32 up to here
 constexpr float kSqTMax = 16256.f;           // 127 * 128: the largest |t|
@@ -61,15 +61,6 @@ struct SrcSqKeys {     // the re-scored rows of the selected groups
     int64_t n;
     __device__ uint64_t key(int q, int64_t i) const { return keys[(int64_t)q * n + i]; }
 };
-
-// The definitions count float32 roundings.  The build contracts a * b + c into one fused multiply-add, and __fmul_rn / __fadd_rn are
-// the plain operators in this toolchain's headers, so the kernels that evaluate a definition turn contraction off for their body and write the operators out (the pragma is lexical: it
-// does not reach into an inlined function).  Division is correctly rounded by default
-#define SQ_NO_CONTRACT _Pragma("clang fp contract(off)")
-
-__device__ __forceinline__ i32x4 sq_frag(const uint4 &v) { return __builtin_bit_cast(i32x4, v); }
-// 128 acc_h + acc_l; unsigned so that an intermediate beyond int32 wraps (the sum itself always fits)
-__device__ __forceinline__ int32_t sq_combine(int h, int l) { return (int32_t)(128u * (uint32_t)h + (uint32_t)l); }
 
 // gmax[q][g] = the best acc of the stored rows of group g for the 32 queries of pass blockIdx.y.  Wave w of workgroup b takes the
 // groups b * 4 + w, + gridDim.x * 4, ...  In an accumulator tile lane l holds query l & 15 and rows 4 (l >> 4) + reg.
@@ -193,33 +184,6 @@ __global__ __launch_bounds__(256) void sq_absent_kernel(int64_t n, float *__rest
         D[i] = -FLT_MAX;
         I[i] = -1;
     }
-}
-
-// t int16 [nq][d] -> both halves, tiled: one thread per (query tile, K step, lane); zeros past d and past nq.  |t| is clamped to
-// 16256 so that h stays an int8 whatever the caller supplies
-__global__ __launch_bounds__(256) void sq_stage_kernel(const int16_t *__restrict__ t, int nq, int d, int ksteps, int64_t nwords,
-                                                       uint4 *__restrict__ qh, uint4 *__restrict__ ql) {
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nwords) return;
-    const int lane = (int)(w & 63);
-    const int s = (int)((w >> 6) % ksteps);
-    const int64_t q = ((w >> 6) / ksteps) * 16 + (lane & 15);
-    const int k0 = 64 * s + 16 * (lane >> 4);
-    uint32_t h[4] = {0u, 0u, 0u, 0u}, l[4] = {0u, 0u, 0u, 0u};
-    if (q < nq) {
-        const int16_t *tp = t + q * d;
-#pragma unroll
-        for (int b = 0; b < 16; ++b) {
-            if (k0 + b < d) {
-                const int v = min(max((int)tp[k0 + b], -16256), 16256);
-                const int lo = ((v + 64) & 127) - 64, hi = (v - lo) >> 7;
-                h[b >> 2] |= (uint32_t)(hi & 255) << (8 * (b & 3));
-                l[b >> 2] |= (uint32_t)(lo & 255) << (8 * (b & 3));
-            }
-        }
-    }
-    qh[w] = uint4{h[0], h[1], h[2], h[3]};
-    ql[w] = uint4{l[0], l[1], l[2], l[3]};
 }
 
 // caller bytes [n][d] (unsigned codes) -> rows start .. start + n of the tiled layout (signed, zero past d): one thread per (row, 16

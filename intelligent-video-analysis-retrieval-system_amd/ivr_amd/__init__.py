@@ -1,5 +1,5 @@
 """ivr_amd: the HIP-backed pieces of the retrieval system.  The submodules are imported by name (ivr_amd.index, ivr_amd.tower, ...);
-the inverted-file indexes (flat rows and product-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index and the product- and scalar-quantisation indexes
+the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index and the product- and scalar-quantisation indexes
 are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
 _IVF = ("IVFFlatIndex", "IndexIVFFlat", "SearchParametersIVF", "METRIC_INNER_PRODUCT", "METRIC_L2")
 _BINARY = ("BinaryFlatIndex", "IndexBinaryFlat", "IndexLSH", "lsh_rotation")
@@ -9,7 +9,8 @@ _REFINE = ("RefineFlatIndex", "IndexRefineFlat", "IndexRefineSearchParameters", 
 _PQ = ("PQIndex", "IndexPQ", "pq_encode_ref", "pq_tables_ref", "pq_scan_ref")
 _SQ = ("SQIndex", "IndexScalarQuantizer", "ScalarQuantizer", "sq_encode_ref", "sq_decode_ref", "sq_query_ref", "sq_scan_ref")
 _IVFPQ = ("IVFPQIndex", "IndexIVFPQ", "ivfpq_scan_ref", "ivfpq_pack_ref", "ivfpq_unpack_ref")
-__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _SQ + _IVFPQ)
+_IVFSQ = ("IVFSQIndex", "IndexIVFScalarQuantizer", "ivfsq_scan_ref", "ivfsq_pack_ref", "ivfsq_unpack_ref", "ivfsq_score_bound")
+__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _SQ + _IVFPQ + _IVFSQ)
 
 
 def __getattr__(name):
@@ -34,4 +35,7 @@ def __getattr__(name):
     if name in _IVFPQ:
         from . import ivfpq
         return getattr(ivfpq, name)
+    if name in _IVFSQ:
+        from . import ivfsq
+        return getattr(ivfsq, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -125,6 +125,13 @@ _SIGS = {
     "ivr_ivfpq_set_lists": (_i, [_p, _p, _p, _p, _i64, _p]),
     "ivr_ivfpq_get_codes": (_i, [_p, _i64, _i64, _p, _p, _p]),
     "ivr_ivfpq_search": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    "ivr_ivfsq_create": (_i, [_p, _i, _i, C.POINTER(_p)]),
+    "ivr_ivfsq_destroy": (_i, [_p]),
+    "ivr_ivfsq_reset": (_i, [_p]),
+    "ivr_ivfsq_ntotal": (_i64, [_p]),
+    "ivr_ivfsq_set_lists": (_i, [_p, _p, _p, _p, _i64, _p]),
+    "ivr_ivfsq_get_codes": (_i, [_p, _i64, _i64, _p, _p, _p]),
+    "ivr_ivfsq_search": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_sq_encode": (_i, [_p, _p, _i64, _i, _p, _p, _p, _p]),
     "ivr_sq_query": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "ivr_sq_index_create": (_i, [_p, _i, C.POINTER(_p)]),
@@ -159,7 +166,7 @@ EXPORTS = tuple(_SIGS)
 _VALUE = frozenset(("ivr_api_version", "ivr_last_error", "ivr_preprocess_scratch_bytes", "ivr_tower_workspace_bytes", "ivr_index_ntotal",
                     "ivr_index_dim", "ivr_index_capacity", "ivr_index_has_ids", "ivr_bin_index_ntotal", "ivr_bin_index_block_rows",
                     "ivr_graph_max_ef", "ivr_graph_max_cand", "ivr_graph_ntotal", "ivr_frame_quality_scratch_bytes",
-                    "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries"))
+                    "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries", "ivr_ivfsq_ntotal"))
 # the slot of the ivr_stream argument (the last one wherever there is one): call() fills it when the caller leaves it out
 _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_release_stream_scratch", "ivr_preprocess", "ivr_tower_encode_image", "ivr_tower_encode_text", "ivr_tower_debug_hidden",
@@ -169,7 +176,7 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_index_get_ids", "ivr_index_find_ids", "ivr_index_gather", "ivr_index_scatter", "ivr_index_search_reconstruct",
     "ivr_index_search_lists", "ivr_segment_mean", "ivr_index_rescore", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
     "ivr_sign_encode", "ivr_pq_encode", "ivr_pq_tables", "ivr_bin_index_search_pq", "ivr_ivfpq_set_lists", "ivr_ivfpq_get_codes",
-    "ivr_ivfpq_search", "ivr_sq_encode", "ivr_sq_query", "ivr_sq_index_add",
+    "ivr_ivfpq_search", "ivr_ivfsq_set_lists", "ivr_ivfsq_get_codes", "ivr_ivfsq_search", "ivr_sq_encode", "ivr_sq_query", "ivr_sq_index_add",
     "ivr_sq_index_get_codes", "ivr_sq_index_search", "ivr_graph_set_rows", "ivr_graph_prune",
     "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",

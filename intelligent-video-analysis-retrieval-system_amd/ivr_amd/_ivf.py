@@ -1,16 +1,18 @@
-"""What the inverted-file indexes (IVFFlatIndex, IVFPQIndex) share: a coarse quantizer (a `FlatIPIndex` of `nlist` centroids) assigns
+"""What the inverted-file indexes (IVFFlatIndex, IVFPQIndex, IVFSQIndex) share: a coarse quantizer (a `FlatIPIndex` of `nlist` centroids) assigns
 every row to the list of its best centroid, the rows are kept ordered by list (list l is the run `off[l] .. off[l+1]`), and a search
 scans only the lists whose centroids score best against the query.
 `InvertedFileIndex` owns the coarse side and the list bookkeeping: the quantizer and its k-means training (`_kmeans.py`), `nprobe`,
 the offsets `_off_host` / `_off` (written by `_set_offsets` only), the checks of what is added and the probe step of a search.  A
 subclass supplies `ntotal`, `is_trained`, `train`, its row store (named in `_PARTS`) with `add_with_ids` (around `_new_ids`,
-`_assign_device` and `_regroup`), `_ids_device(start, n)`, its scan and `reset`.
+`_assign_device` and `_regroup`), `_ids_device(start, n)`, its scan and `reset`.  `CodedInvertedFileIndex` below is that subclass for the two indexes that keep codes
+in a list store of the library: everything but the coder, the query form and the scan call.
 """
 import numpy as np
 import torch
 
 from . import _ffi, _kmeans, _staging
-from ._faiss import METRIC_INNER_PRODUCT, search_numpy, typed_params
+from ._coded import ENCODE_CHUNK
+from ._faiss import METRIC_INNER_PRODUCT, search_numpy, to_numpy, typed_params
 from .index import FlatIPIndex, _ids_i64, normalize_L2
 
 _ASSIGN_BLOCK = 1 << 16       # rows per coarse search when whole matrices are assigned: bounds the query workspace of the quantizer
@@ -148,7 +150,7 @@ class InvertedFileIndex:
         return self.quantizer.search(x, 1)[1][:, 0]
 
     def add(self, x, *args, **kw):
-        """add(x, normalize=False) on IVFFlatIndex, add(x) on IVFPQIndex: rows labelled ntotal, ntotal + 1, ... (see add_with_ids)."""
+        """add(x, normalize=False) on IVFFlatIndex, add(x) on IVFPQIndex and IVFSQIndex: rows labelled ntotal, ntotal + 1, ... (see add_with_ids)."""
         n = len(x) if isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim == 2 else 0
         self.add_with_ids(x, np.arange(self.ntotal, self.ntotal + n, dtype=np.int64), *args, _what="add", **kw)
 
@@ -222,3 +224,219 @@ class InvertedFileIndex:
         for x in (getattr(self, name, None) for name in self._PARTS):
             if x is not None:
                 x.close()
+
+
+class _ListStore(_ffi.Handle):
+    """The list store of a coded inverted-file index on the device: the object behind the exports `abi`_create / _destroy /
+    _set_lists / _get_codes / _reset / _search (ivr_ivfpq of csrc/search_ivfpq.hip, ivr_ivfsq of csrc/search_ivfsq.hip)."""
+
+    def __init__(self, abi, code_size, nlist, device):
+        self._DESTROY = abi + "_destroy"
+        self._open(abi + "_create", device, int(code_size), int(nlist))
+
+
+class CodedInvertedFileIndex(InvertedFileIndex):
+    """What the inverted-file indexes over codes (IVFPQIndex, IVFSQIndex) share: a row is stored in the list of its best centroid as
+    the code of its residual against that centroid (`by_residual`, the default, as in faiss) or of the row itself; the codes live in
+    a list store of the library (`_ABI` names its exports) and a search scans the probed lists with one query form that serves
+    every list, the coarse score being the only per-list term.  The coder (a PQIndex / SQIndex whose own row store stays empty and
+    whose tables are bound to the owner's rows) is handed to the constructor; a subclass supplies `_ABI`, `_NOUN`, `train` (around
+    `_train`), `_query_form(t)` and `_scan(form, coarse, assign, k)`."""
+    _ABI = None
+    _NOUN = "tables"
+
+    def __init__(self, d, nlist, coder, device=None, _quantizer=None):
+        self._coder = coder
+        coder._owner = self
+        super().__init__(d, nlist, device, _quantizer)
+        self.code_size = coder.code_size
+        self._by_residual = True
+        self._coarse_trained = False
+        self._cent_dev = None
+        self._lists = _ListStore(self._ABI, self.code_size, self.nlist, self.device.index)
+
+    # -- attributes ------------------------------------------------------------------------------
+    @property
+    def ntotal(self):
+        return int(self._off_host[-1])
+
+    @property
+    def is_trained(self):
+        return bool(self._coder.is_trained and (self._coarse_trained or self.quantizer.ntotal == self.nlist))
+
+    @property
+    def by_residual(self):
+        """True (faiss's default): a row is coded as its residual against its list's centroid.  Assignable only while the index is
+        empty and untrained: the coder is trained on what is coded."""
+        return self._by_residual
+
+    @by_residual.setter
+    def by_residual(self, v):
+        if self.ntotal or self.is_trained:
+            raise RuntimeError("by_residual: the index is trained or holds rows coded with the current setting")
+        self._by_residual = bool(v)
+
+    def _centroids_device(self):
+        if self._cent_dev is None:
+            self._cent_dev = self.quantizer.gather_device(torch.arange(self.nlist, dtype=torch.int64, device=self.device))
+        return self._cent_dev
+
+    def list_codes(self, l):
+        """The codes of list l in stored order (numpy uint8 [size, code_size])."""
+        a, b = self._check_list(l)
+        return self._rows_device(a, b - a, ids=False)[0].cpu().numpy()
+
+    def _rows_device(self, start=0, n=None, codes=True, ids=True):
+        """(codes uint8 CUDA [n,code_size], ids int64 CUDA [n]) of the list-ordered rows [start, start + n); None for the half not asked for."""
+        n = self.ntotal - start if n is None else n
+        c = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device) if codes else None
+        i = torch.empty(n, dtype=torch.int64, device=self.device) if ids else None
+        if n:
+            self._lists._call(self._ABI + "_get_codes", int(start), int(n), c, i)
+        return c, i
+
+    def _ids_device(self, start=0, n=None):
+        return self._rows_device(start, n, codes=False)[1]
+
+    def _set_lists(self, codes, ids, off_host):
+        self._lists._call(self._ABI + "_set_lists", codes, ids, off_host.ctypes.data, len(codes))
+        torch.cuda.current_stream(self.device).synchronize()      # codes and ids may be temporaries
+        self._set_offsets(off_host)
+
+    # -- training --------------------------------------------------------------------------------
+    def _train(self, x, niter, seed, max_points_per_centroid, spherical):
+        """Train the quantizer as IVFFlatIndex.train does (a quantizer that already holds nlist rows is taken as it is), then the
+        coder on the residuals x_i - centroids[assign(x_i)] (one float32 subtraction per coordinate; x itself without by_residual)."""
+        if self.ntotal:
+            raise RuntimeError(f"train: the index holds {self.ntotal} rows encoded with the current {self._NOUN}")
+        _staging.check_rows(x, self.d, "train")
+        self._train_quantizer(x, niter, seed, max_points_per_centroid, spherical)
+        self._coarse_trained = True
+        self._cent_dev = None
+        with torch.cuda.device(self.device):
+            t = _staging.dev_f32(x, self.device)
+            self._coder.train(self._residuals(t, self._assign_device(t)) if self._by_residual else t)
+
+    def _residuals(self, t, lists):
+        return t - self._centroids_device()[lists]
+
+    # -- adding ----------------------------------------------------------------------------------
+    def add_with_ids(self, x, ids, *, _what="add_with_ids"):
+        """Append rows under caller-chosen int64 labels (>= 0, duplicates allowed).  Each row goes to the list of its best centroid
+        and only its code is kept: the coder's encoder applied to its residual against that centroid (to the row itself without
+        by_residual).  The whole index is regrouped by list in every call: one pass over all stored codes (unpack, a stable argsort
+        of the list numbers, pack), so add in large batches.  RuntimeError while untrained."""
+        ids = self._new_ids(x, ids, _what)
+        if len(ids) == 0:
+            return
+        with torch.cuda.device(self.device):
+            codes, lists = [], []
+            for i in range(0, len(ids), ENCODE_CHUNK):
+                t = _staging.dev_f32(x[i:i + ENCODE_CHUNK], self.device)
+                l = self._assign_device(t)
+                codes.append(self._coder._encode_device(self._residuals(t, l) if self._by_residual else t))
+                lists.append(l)
+            codes, lists = torch.cat(codes), torch.cat(lists)
+            new_ids = torch.from_numpy(np.ascontiguousarray(ids)).to(self.device)
+            if self.ntotal:
+                old_codes, old_ids = self._rows_device()
+                sizes = torch.from_numpy(self.list_sizes()).to(self.device)
+                codes = torch.cat([old_codes, codes])
+                new_ids = torch.cat([old_ids, new_ids])
+                lists = torch.cat([torch.repeat_interleave(torch.arange(self.nlist, device=self.device), sizes), lists])
+            order, off = self._regroup(lists)
+            self._set_lists(codes[order].contiguous(), new_ids[order].contiguous(), off)
+
+    # -- search ----------------------------------------------------------------------------------
+    def _coarse_scores(self, t, assign):
+        """float32 CUDA [nq,p]: the quantizer's inner product of query i with centroid assign[i,j], with the bits its search reports
+        (-FLT_MAX for a -1 entry, which the scan skips)."""
+        step = _ffi.IVR_MAX_K
+        return torch.cat([self.quantizer.rescore_device(t, assign[:, j:j + step].contiguous())[0] for j in range(0, assign.shape[1], step)], dim=1)
+
+    def search_device(self, x, k, nprobe=None):
+        """Device-resident search: CUDA tensors, no host synchronisation (unless x had to be staged).  nprobe (default: the attribute)
+        is clipped to nlist; below nlist it is the k of the coarse search and so at most IVR_MAX_K.  With nprobe >= nlist there is no
+        coarse search: every list is probed, with the coarse scores search_preassigned computes."""
+        t, k, staged = self._queries(x, k, "search")
+        _staging.check_nq(t.shape[0])
+        with torch.cuda.device(self.device):
+            coarse, assign = self._probe(t, nprobe)
+            if not self._by_residual:
+                coarse = None
+            elif coarse is None:         # every list: the scores search_preassigned computes
+                coarse = self._coarse_scores(t, assign)
+            out = self._scan(self._query_form(t), coarse, assign, k)
+            _staging.sync_if_staged(staged, self.device)
+            return out
+
+    def search_preassigned(self, x, k, assign, coarse_dis=None):
+        """faiss search_preassigned: assign int64 [nq,p] (numpy or CUDA tensor) names the lists to scan for each query; -1 entries
+        are skipped and a list named twice is scanned once.  coarse_dis float32 [nq,p]: the coarse score that goes with each entry;
+        when omitted it is the quantizer's float32 inner product for exactly the named lists (the bits its search reports).  Without
+        by_residual it is not used.  ValueError for an entry >= nlist or < -1.  Returns (D, I) numpy arrays."""
+        return to_numpy(self.search_preassigned_device(x, k, assign, coarse_dis))
+
+    def search_preassigned_device(self, x, k, assign, coarse_dis=None):
+        """search_preassigned returning CUDA tensors; the range check of assign synchronises once."""
+        t, k, staged = self._queries(x, k, "search_preassigned")
+        _staging.check_nq(t.shape[0])
+        with torch.cuda.device(self.device):
+            assign = self._assign_arg(assign, t.shape[0], "search_preassigned")
+            coarse = None
+            if self._by_residual:
+                coarse = self._coarse_scores(t, assign) if coarse_dis is None else self._coarse_arg(coarse_dis, assign, "search_preassigned")
+            out = self._scan(self._query_form(t), coarse, assign, k)
+            _staging.sync_if_staged(staged, self.device)
+            return out
+
+    def _coarse_arg(self, coarse, assign, what):
+        c = _staging.dev_f32(coarse, self.device)
+        if tuple(c.shape) != tuple(assign.shape):
+            raise ValueError(f"{what}: the coarse scores must be float32 {tuple(assign.shape)}, got {tuple(c.shape)}")
+        return c
+
+    # -- reconstruction --------------------------------------------------------------------------
+    def reconstruct_batch(self, ids):
+        """numpy float32 [n,d]: for every label centroids[l] + the coder's sa_decode(code) of the row stored under it, one float32 addition per
+        coordinate (the decode alone without by_residual); the lowest stored position on duplicate labels.  RuntimeError when a label
+        names no row.  Reads every stored label and code once per call."""
+        keys = _ids_i64(np.atleast_1d(ids) if not isinstance(ids, torch.Tensor) else ids, None, "reconstruct_batch")
+        miss, out = self._reconstruct(keys)
+        if len(miss):
+            raise RuntimeError(f"reconstruct_batch: key {int(keys[miss[0]])} is not in the index ({len(miss)} of {len(keys)} missing)")
+        return out
+
+    def reconstruct(self, i):
+        """The decoded row stored under label i (the lowest stored position on duplicates); RuntimeError when none is."""
+        miss, out = self._reconstruct(np.array([int(i)], np.int64))
+        if len(miss):
+            raise RuntimeError(f"reconstruct: id {int(i)} is not in the index")
+        return out[0]
+
+    def _reconstruct(self, keys):
+        """keys int64 numpy [n] -> (the positions in keys of the labels that name no row, the decoded rows [n,d] or None when one is
+        missing)."""
+        if len(keys) == 0:
+            return np.zeros(0, np.int64), np.zeros((0, self.d), np.float32)
+        if self.ntotal == 0:
+            return np.arange(len(keys)), None
+        with torch.cuda.device(self.device):
+            codes, stored = self._rows_device()
+            k = torch.from_numpy(np.ascontiguousarray(keys)).to(self.device)
+            sorted_ids, perm = torch.sort(stored, stable=True)
+            at = torch.searchsorted(sorted_ids, k).clamp_(max=self.ntotal - 1)
+            miss = np.flatnonzero((sorted_ids[at] != k).cpu().numpy())
+            if len(miss):
+                return miss, None
+            rows = perm[at]
+            out = self._coder.sa_decode_device(codes[rows].contiguous())
+            if self._by_residual:
+                out = self._centroids_device()[torch.searchsorted(self._off, rows, right=True) - 1] + out
+            return miss, out.cpu().numpy()
+
+    # -- maintenance -----------------------------------------------------------------------------
+    def reset(self):
+        """Drop the rows; the trained quantizer and coder stay."""
+        self._lists._call(self._ABI + "_reset")
+        self._set_offsets(np.zeros(self.nlist + 1, np.int64))

@@ -19,11 +19,10 @@ import numpy as np
 import torch
 
 from . import _ffi, _staging
-from ._coded import ENCODE_CHUNK
-from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product, to_numpy
-from ._ivf import InvertedFileIndex, check_quantizer
+from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
+from ._ivf import CodedInvertedFileIndex, check_quantizer
 from ._staging import dev_f32 as _dev_f32
-from .index import FlatIPIndex, _ids_i64
+from .index import FlatIPIndex
 from .pq import KSUB, PQIndex
 
 
@@ -141,173 +140,37 @@ class _CodebookPQ(PQIndex):
             raise RuntimeError(f"{what}: the index holds {n} rows encoded with the current {noun}")
 
 
-class _Lists(_ffi.Handle):
-    """The list store of an IVFPQIndex on the device (ivr_ivfpq of csrc/search_ivfpq.hip)."""
-    _DESTROY = "ivr_ivfpq_destroy"
-
-    def __init__(self, M, nlist, device):
-        self._open("ivr_ivfpq_create", device, int(M), int(nlist))
-
-
-class IVFPQIndex(InvertedFileIndex):
+class IVFPQIndex(CodedInvertedFileIndex):
     """Inverted-file index over product-quantised codes (FAISS IndexIVFPQ contract, METRIC_INNER_PRODUCT, nbits = 8) on one GPU.
 
     search(x, k) looks at the rows of the nprobe lists nearest to each query and returns (D, I) as ivfpq_scan_ref defines them over
     the tables pq.compute_tables_device(x) and the quantizer's float32 scores of the probed centroids: float32 descending, int64
     labels, (-FLT_MAX, -1) padding.  Equal scores rank the row in the lower list first, and within a list the row added earlier.
-    Every add() call regroups the whole index by list (one pass over all stored codes): add in large batches."""
+    Every add() call regroups the whole index by list (one pass over all stored codes): add in large batches.  The store, the
+    adding, the search surface and the reconstruction are CodedInvertedFileIndex's (_ivf.py)."""
     _PARTS = ("_lists", "pq", "quantizer")
+    _ABI = "ivr_ivfpq"
+    _NOUN = "codebooks"
 
     def __init__(self, d, nlist, M, device=None, _quantizer=None):
         self.pq = _CodebookPQ(d, M, device=device if _quantizer is None else _quantizer.device.index)
-        self.pq._owner = self
-        super().__init__(d, nlist, device, _quantizer)
-        self.M = self.code_size = self.pq.M
+        super().__init__(d, nlist, self.pq, device, _quantizer)
+        self.M = self.pq.M
         self.nbits = 8
-        self._by_residual = True
-        self._coarse_trained = False
-        self._cent_dev = None
-        self._lists = _Lists(self.M, self.nlist, self.device.index)
-
-    # -- attributes ------------------------------------------------------------------------------
-    @property
-    def ntotal(self):
-        return int(self._off_host[-1])
-
-    @property
-    def is_trained(self):
-        return bool(self.pq.is_trained and (self._coarse_trained or self.quantizer.ntotal == self.nlist))
-
-    @property
-    def by_residual(self):
-        """True (faiss's default): a row is coded as its residual against its list's centroid.  Assignable only while the index is
-        empty and untrained: the codebooks are trained on what is coded."""
-        return self._by_residual
-
-    @by_residual.setter
-    def by_residual(self, v):
-        if self.ntotal or self.is_trained:
-            raise RuntimeError("by_residual: the index is trained or holds rows coded with the current setting")
-        self._by_residual = bool(v)
-
-    def _centroids_device(self):
-        if self._cent_dev is None:
-            self._cent_dev = self.quantizer.gather_device(torch.arange(self.nlist, dtype=torch.int64, device=self.device))
-        return self._cent_dev
-
-    def list_codes(self, l):
-        """The codes of list l in stored order (numpy uint8 [size, M])."""
-        a, b = self._check_list(l)
-        return self._rows_device(a, b - a, ids=False)[0].cpu().numpy()
-
-    def _rows_device(self, start=0, n=None, codes=True, ids=True):
-        """(codes uint8 CUDA [n,M], ids int64 CUDA [n]) of the list-ordered rows [start, start + n); None for the half not asked for."""
-        n = self.ntotal - start if n is None else n
-        c = torch.empty((n, self.M), dtype=torch.uint8, device=self.device) if codes else None
-        i = torch.empty(n, dtype=torch.int64, device=self.device) if ids else None
-        if n:
-            self._lists._call("ivr_ivfpq_get_codes", int(start), int(n), c, i)
-        return c, i
-
-    def _ids_device(self, start=0, n=None):
-        return self._rows_device(start, n, codes=False)[1]
-
-    def _set_lists(self, codes, ids, off_host):
-        self._lists._call("ivr_ivfpq_set_lists", codes, ids, off_host.ctypes.data, len(codes))
-        torch.cuda.current_stream(self.device).synchronize()      # codes and ids may be temporaries
-        self._set_offsets(off_host)
 
     # -- training --------------------------------------------------------------------------------
     def train(self, x, niter=10, seed=1234, max_points_per_centroid=256, spherical=True):
         """Train the quantizer exactly as IVFFlatIndex.train does (same arguments; a quantizer that already holds nlist rows is taken
         as it is), form the training residuals x_i - centroids[assign(x_i)] (one float32 subtraction per coordinate; x itself without
         by_residual) and call pq.train on them with PQIndex.train's own defaults."""
-        if self.ntotal:
-            raise RuntimeError(f"train: the index holds {self.ntotal} rows encoded with the current codebooks")
-        _staging.check_rows(x, self.d, "train")
-        self._train_quantizer(x, niter, seed, max_points_per_centroid, spherical)
-        self._coarse_trained = True
-        self._cent_dev = None
-        with torch.cuda.device(self.device):
-            t = _dev_f32(x, self.device)
-            self.pq.train(self._residuals(t, self._assign_device(t)) if self._by_residual else t)
-
-    def _residuals(self, t, lists):
-        return t - self._centroids_device()[lists]
-
-    # -- adding ----------------------------------------------------------------------------------
-    def add_with_ids(self, x, ids, *, _what="add_with_ids"):
-        """Append rows under caller-chosen int64 labels (>= 0, duplicates allowed).  Each row goes to the list of its best centroid
-        and only its code is kept: pq's encoder applied to its residual against that centroid (to the row itself without
-        by_residual).  The whole index is regrouped by list in every call: one pass over all stored codes (unpack, a stable argsort
-        of the list numbers, pack), so add in large batches.  RuntimeError while untrained."""
-        ids = self._new_ids(x, ids, _what)
-        if len(ids) == 0:
-            return
-        with torch.cuda.device(self.device):
-            codes, lists = [], []
-            for i in range(0, len(ids), ENCODE_CHUNK):
-                t = _dev_f32(x[i:i + ENCODE_CHUNK], self.device)
-                l = self._assign_device(t)
-                codes.append(self.pq._encode_device(self._residuals(t, l) if self._by_residual else t))
-                lists.append(l)
-            codes, lists = torch.cat(codes), torch.cat(lists)
-            new_ids = torch.from_numpy(np.ascontiguousarray(ids)).to(self.device)
-            if self.ntotal:
-                old_codes, old_ids = self._rows_device()
-                sizes = torch.from_numpy(self.list_sizes()).to(self.device)
-                codes = torch.cat([old_codes, codes])
-                new_ids = torch.cat([old_ids, new_ids])
-                lists = torch.cat([torch.repeat_interleave(torch.arange(self.nlist, device=self.device), sizes), lists])
-            order, off = self._regroup(lists)
-            self._set_lists(codes[order].contiguous(), new_ids[order].contiguous(), off)
+        self._train(x, niter, seed, max_points_per_centroid, spherical)
 
     # -- search ----------------------------------------------------------------------------------
     def compute_tables_device(self, x):
         """pq.compute_tables_device(x): float32 CUDA [nq,M,256], the same for every list."""
         return self.pq.compute_tables_device(x)
 
-    def _coarse_scores(self, t, assign):
-        """float32 CUDA [nq,p]: the quantizer's inner product of query i with centroid assign[i,j], with the bits its search reports
-        (-FLT_MAX for a -1 entry, which the scan skips)."""
-        step = _ffi.IVR_MAX_K
-        return torch.cat([self.quantizer.rescore_device(t, assign[:, j:j + step].contiguous())[0] for j in range(0, assign.shape[1], step)], dim=1)
-
-    def search_device(self, x, k, nprobe=None):
-        """Device-resident search: CUDA tensors, no host synchronisation (unless x had to be staged).  nprobe (default: the attribute)
-        is clipped to nlist; below nlist it is the k of the coarse search and so at most IVR_MAX_K.  With nprobe >= nlist there is no
-        coarse search: every list is probed, with the coarse scores search_preassigned computes."""
-        t, k, staged = self._queries(x, k, "search")
-        _staging.check_nq(t.shape[0])
-        with torch.cuda.device(self.device):
-            coarse, assign = self._probe(t, nprobe)
-            if not self._by_residual:
-                coarse = None
-            elif coarse is None:         # every list: the scores search_preassigned computes
-                coarse = self._coarse_scores(t, assign)
-            out = self._scan(self.pq.compute_tables_device(t), coarse, assign, k)
-            _staging.sync_if_staged(staged, self.device)
-            return out
-
-    def search_preassigned(self, x, k, assign, coarse_dis=None):
-        """faiss search_preassigned: assign int64 [nq,p] (numpy or CUDA tensor) names the lists to scan for each query; -1 entries
-        are skipped and a list named twice is scanned once.  coarse_dis float32 [nq,p]: the coarse score that goes with each entry;
-        when omitted it is the quantizer's float32 inner product for exactly the named lists (the bits its search reports).  Without
-        by_residual it is not used.  ValueError for an entry >= nlist or < -1.  Returns (D, I) numpy arrays."""
-        return to_numpy(self.search_preassigned_device(x, k, assign, coarse_dis))
-
-    def search_preassigned_device(self, x, k, assign, coarse_dis=None):
-        """search_preassigned returning CUDA tensors; the range check of assign synchronises once."""
-        t, k, staged = self._queries(x, k, "search_preassigned")
-        _staging.check_nq(t.shape[0])
-        with torch.cuda.device(self.device):
-            assign = self._assign_arg(assign, t.shape[0], "search_preassigned")
-            coarse = None
-            if self._by_residual:
-                coarse = self._coarse_scores(t, assign) if coarse_dis is None else self._coarse_arg(coarse_dis, assign, "search_preassigned")
-            out = self._scan(self.pq.compute_tables_device(t), coarse, assign, k)
-            _staging.sync_if_staged(staged, self.device)
-            return out
+    _query_form = compute_tables_device
 
     def search_tables_preassigned_device(self, T, coarse, assign, k):
         """The scan alone on caller-supplied tables: T float32 [nq,M,256] (finite), coarse float32 [nq,p] or None (+0.0), assign
@@ -325,12 +188,6 @@ class IVFPQIndex(InvertedFileIndex):
             _staging.sync_if_staged(True, self.device)       # T, coarse and assign may all be staged copies
             return out
 
-    def _coarse_arg(self, coarse, assign, what):
-        c = _dev_f32(coarse, self.device)
-        if tuple(c.shape) != tuple(assign.shape):
-            raise ValueError(f"{what}: the coarse scores must be float32 {tuple(assign.shape)}, got {tuple(c.shape)}")
-        return c
-
     def _scan(self, T, coarse, assign, k):
         """assign: int64 CUDA [nq,p], entries in [-1, nlist).  The kernel wants every row ascending (a repeated list is then adjacent);
         the sort is stable, so the first mention of a list keeps its coarse score."""
@@ -339,51 +196,6 @@ class IVFPQIndex(InvertedFileIndex):
         D, I = _staging.alloc_DI(nq, k, self.device)
         self._lists._call("ivr_ivfpq_search", T, coarse, assign, nq, p, k, D, I)
         return D, I
-
-    # -- reconstruction --------------------------------------------------------------------------
-    def reconstruct_batch(self, ids):
-        """numpy float32 [n,d]: for every label centroids[l] + pq.sa_decode(code) of the row stored under it, one float32 addition per
-        coordinate (the decode alone without by_residual); the lowest stored position on duplicate labels.  RuntimeError when a label
-        names no row.  Reads every stored label and code once per call."""
-        keys = _ids_i64(np.atleast_1d(ids) if not isinstance(ids, torch.Tensor) else ids, None, "reconstruct_batch")
-        miss, out = self._reconstruct(keys)
-        if len(miss):
-            raise RuntimeError(f"reconstruct_batch: key {int(keys[miss[0]])} is not in the index ({len(miss)} of {len(keys)} missing)")
-        return out
-
-    def reconstruct(self, i):
-        """The decoded row stored under label i (the lowest stored position on duplicates); RuntimeError when none is."""
-        miss, out = self._reconstruct(np.array([int(i)], np.int64))
-        if len(miss):
-            raise RuntimeError(f"reconstruct: id {int(i)} is not in the index")
-        return out[0]
-
-    def _reconstruct(self, keys):
-        """keys int64 numpy [n] -> (the positions in keys of the labels that name no row, the decoded rows [n,d] or None when one is
-        missing)."""
-        if len(keys) == 0:
-            return np.zeros(0, np.int64), np.zeros((0, self.d), np.float32)
-        if self.ntotal == 0:
-            return np.arange(len(keys)), None
-        with torch.cuda.device(self.device):
-            codes, stored = self._rows_device()
-            k = torch.from_numpy(np.ascontiguousarray(keys)).to(self.device)
-            sorted_ids, perm = torch.sort(stored, stable=True)
-            at = torch.searchsorted(sorted_ids, k).clamp_(max=self.ntotal - 1)
-            miss = np.flatnonzero((sorted_ids[at] != k).cpu().numpy())
-            if len(miss):
-                return miss, None
-            rows = perm[at]
-            out = self.pq.sa_decode_device(codes[rows].contiguous())
-            if self._by_residual:
-                out = self._centroids_device()[torch.searchsorted(self._off, rows, right=True) - 1] + out
-            return miss, out.cpu().numpy()
-
-    # -- maintenance -----------------------------------------------------------------------------
-    def reset(self):
-        """Drop the rows; the trained quantizer and codebooks stay."""
-        self._lists._call("ivr_ivfpq_reset")
-        self._set_offsets(np.zeros(self.nlist + 1, np.int64))
 
 
 def IndexIVFPQ(quantizer, d, nlist, M, nbits=8, metric=METRIC_INNER_PRODUCT):

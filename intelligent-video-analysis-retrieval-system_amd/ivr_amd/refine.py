@@ -2,7 +2,7 @@
 over the same rows scores exactly those and returns the best k.
 
 Stands in for `faiss.IndexRefineFlat(base)`.  The base is one of the approximate indexes of this package (`IndexLSH`, `PQIndex`,
-`SQIndex`, `IVFFlatIndex`, `IVFPQIndex`, `GraphFlatIndex`) or a plain `FlatIPIndex`; the refine index is a plain `FlatIPIndex` that receives every row the
+`SQIndex`, `IVFFlatIndex`, `IVFPQIndex`, `IVFSQIndex`, `GraphFlatIndex`) or a plain `FlatIPIndex`; the refine index is a plain `FlatIPIndex` that receives every row the
 base receives, in the same order, so a base label is a row of the refine index (there is no add_with_ids, as in faiss).  The base's
 labels never leave the device: they go straight into `FlatIPIndex.rescore_device` (ivr_index_rescore, csrc/search_refine.hip), whose
 scores carry the bits of `FlatIPIndex.search` and whose ordering is pinned to `refine_order_ref` below.
@@ -17,6 +17,7 @@ from .graph import GraphFlatIndex, SearchParametersHNSW
 from .index import FlatIPIndex, SearchParameters, _selector
 from .ivf import IVFFlatIndex, SearchParametersIVF
 from .ivfpq import IVFPQIndex
+from .ivfsq import IVFSQIndex
 
 
 def _ordered(s):
@@ -55,7 +56,7 @@ def refine_order_ref(S, cand, k, ntotal=None):
 
 class IndexRefineSearchParameters:
     """faiss.IndexRefineSearchParameters(k_factor=..., base_index_params=...): k_factor overrides the index attribute for one call,
-    base_index_params is what the base index's own search() takes as params (SearchParametersIVF for IVFFlatIndex and IVFPQIndex,
+    base_index_params is what the base index's own search() takes as params (SearchParametersIVF for IVFFlatIndex, IVFPQIndex and IVFSQIndex,
     SearchParametersHNSW, or
     SearchParameters(sel=...) for a flat base; None for IndexLSH, PQIndex and SQIndex).  A selector on the refine level is not supported: search raises
     ValueError when sel is set."""
@@ -79,7 +80,7 @@ def _base_kwargs(base, params):
         if params is not None:
             raise ValueError(f"base_index_params must be None for {type(base).__name__}, got {type(params).__name__}")
         return {}
-    if isinstance(base, (IVFFlatIndex, IVFPQIndex)):
+    if isinstance(base, (IVFFlatIndex, IVFPQIndex, IVFSQIndex)):
         params = typed_params(params, SearchParametersIVF, type(base).__name__)
         return {} if params is None else {"nprobe": params.nprobe}
     if isinstance(base, GraphFlatIndex):
@@ -99,8 +100,8 @@ class RefineFlatIndex:
     padding.  The base must be empty when it is wrapped and receives its rows through add() of this object only."""
 
     def __init__(self, base_index, device=None):
-        if not isinstance(base_index, (CodedIndex, IVFFlatIndex, IVFPQIndex, GraphFlatIndex, FlatIPIndex)):
-            raise ValueError(f"RefineFlatIndex: the base must be an IndexLSH, PQIndex, SQIndex, IVFFlatIndex, IVFPQIndex, GraphFlatIndex or FlatIPIndex, "
+        if not isinstance(base_index, (CodedIndex, IVFFlatIndex, IVFPQIndex, IVFSQIndex, GraphFlatIndex, FlatIPIndex)):
+            raise ValueError(f"RefineFlatIndex: the base must be an IndexLSH, PQIndex, SQIndex, IVFFlatIndex, IVFPQIndex, IVFSQIndex, GraphFlatIndex or FlatIPIndex, "
                              f"got {type(base_index).__name__}")
         if isinstance(base_index, FlatIPIndex) and base_index.has_ids:
             raise ValueError("RefineFlatIndex: a flat base must be a plain index, this one is id-mapped")
@@ -194,7 +195,7 @@ class RefineFlatIndex:
 
 
 def IndexRefineFlat(base_index):
-    """faiss.IndexRefineFlat(base_index) drop-in: base_index is an EMPTY IndexLSH, PQIndex, SQIndex, IVFFlatIndex, IVFPQIndex, GraphFlatIndex or plain
+    """faiss.IndexRefineFlat(base_index) drop-in: base_index is an EMPTY IndexLSH, PQIndex, SQIndex, IVFFlatIndex, IVFPQIndex, IVFSQIndex, GraphFlatIndex or plain
     FlatIPIndex
     (ValueError otherwise)."""
     return RefineFlatIndex(base_index)
