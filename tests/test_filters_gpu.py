@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import reduce_cases as C
 from oracle import search_ref as S
 
 pytestmark = pytest.mark.gpu
@@ -58,3 +59,10 @@ def test_scene_filter_is_one_launch_and_handles_edge_rules():
             cfg = {"enable_similarity_filtering": True, "similarity_threshold": thr, "min_frame_distance": dist}
             idxs = list(range(100, 100 + len(E)))
             assert F.filter_similar_frames_in_scene(E, idxs, cfg) == S.filter_similar_frames_in_scene(E, idxs, cfg), (len(E), thr, dist)
+
+
+@pytest.mark.parametrize("d,n", C.SCENE_CASES)
+def test_scene_filter_in_chunks_against_the_chain_reference(d, n):
+    """d = 2048 (4 rows per LDS chunk) and d = 1000 (8 rows), min_frame_distance 1, 3, 5, 9 (longer than a chunk) against
+    oracle.reduce_ref.keep_chain_ref; every decision clears the threshold by four times the bound of its cosine."""
+    print(f"\nd={d} n={n}: kept {C.check_scene_filter(C.Gpu, d, n)}")

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import reduce_cases as C
 from conftest import smooth_frames, synth_frames
 from oracle import quality_ref as Q
 from oracle import search_ref as S
@@ -45,6 +46,18 @@ def test_window_keep_mask_matches_oracle(n, d, window):
     assert got == ref
     assert 1 < len(ref) < n or n <= 2
     assert filter_similar_frames_advanced(torch.from_numpy(e).cuda(), list(range(n)), dict(cfg, enable_similarity_filtering=False)) == list(range(n))
+
+
+@pytest.mark.parametrize("n,d,window", C.WINDOW_CASES)
+def test_window_keep_mask_against_the_window_reference(n, d, window):
+    """d = 1, partly filled registers, d = 2048, windows of n, n - 1 and beyond n, zero rows inside the window; against
+    oracle.reduce_ref.keep_window_ref with the margin derived from the cosine bound."""
+    print(f"\nn={n} d={d} window={window}: kept {C.check_window_filter(C.Gpu, n, d, window)}")
+
+
+def test_window_only_kept_frames_block():
+    """The only frame at or above the threshold inside the window was itself dropped: the frame stays."""
+    C.check_window_dropped_blocker(C.Gpu)
 
 
 def _video(seed, n, h, w):
