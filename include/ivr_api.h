@@ -422,6 +422,42 @@ int ivr_index_rescore(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, con
                       int normalize_q, float *D_all /*DEV [nq][kc] or NULL*/, float *D /*DEV [nq][k] or NULL*/,
                       int64_t *I /*DEV [nq][k] or NULL*/, ivr_stream stream);
 
+/* ---- clip search: sliding-window sequence match over the flat index ----------------------------------
+ * Where in the stored rows does a run of L consecutive query frames occur?  The reference's TemporalAnalyzer.find_similar_sequences
+ * (core.py:3644-3702) without its three Python loops.  q: DEV float32 [T,d] query frames, 1 <= L <= IVR_SEQ_MAX_LEN, T >= L.
+ *   frame score   S[t, s] = the float32 inner product ivr_index_search reports for (query frame t, stored row s), to the bit
+ *   window score  W[t, s] = (((S[t, s] + S[t+1, s+1]) + ...) + S[t+L-1, s+L-1]) / (float)L for target window t in [0, T - L] and start
+ *                 row s in [0, ntotal - L]: L - 1 float32 additions in ascending order, each rounded on its own, then one correctly
+ *                 rounded float32 division.  With unit rows and normalize_q that is the mean frame-wise cosine of the two runs.
+ *   segments      seg_off: DEV int64 [nseg + 1], ascending, or NULL (then nseg is not read and the whole index is one segment).  A start
+ *                 s is a candidate only when [s, s + L) lies inside one segment [seg_off[j], seg_off[j + 1]): a match never straddles
+ *                 two videos.  Rows outside [seg_off[0], seg_off[nseg]) start nothing, empty segments are allowed, and fewer stored rows
+ *                 than L give no candidate at all.
+ * Both calls are positional like ivr_index_rescore and label a result with its start row, or with the stored id of that row on an
+ * id-mapped index.  Scores are written as every search writes them (-0.0 as +0.0).
+ *
+ * ivr_index_search_sequences: D / I DEV [T - L + 1][k], per target window the k best starts by W, descending, equal scores the lower
+ * start ROW first; unused slots (-FLT_MAX, -1).  1 <= k <= IVR_MAX_K.
+ * ivr_index_range_search_sequences: every candidate with W >= threshold.  The test is >= because the reference's is (core.py:3687),
+ * unlike the strict > of ivr_index_range_search.  Output as there: lims DEV int64 [T - L + 2], lims[0] = 0, the results of window t at
+ * [lims[t], lims[t + 1]) in ascending start row; D / I DEV with room for `cap` entries, entries at positions >= cap are counted in
+ * lims but not written (the caller re-calls with cap >= lims[T - L + 1]).  A NaN score matches nothing; a NaN threshold is
+ * IVR_ERR_INVALID (+-inf are allowed).
+ *
+ * The windows are worked off in chunks.  Scratch on the index, grow-only: 8 bytes per (window of a chunk, start) with at most
+ * IVR_SEQ_CHUNK_SLOTS slots per chunk (environment, read by ivr_index_create; default 2^25 = 256 MiB) or one window's ntotal - L + 1 when
+ * that is more, and 4 bytes per (frame of a chunk rounded up to whole 16-frame tiles plus one tile, stored row).  The frames of
+ * consecutive chunks overlap by L - 1 and are scored again.  The range call carries its running total from chunk to chunk on the
+ * device.  Enqueue-only, no host synchronisation, once the scratch has grown (a call that grows it allocates); not graph-capturable
+ * then. */
+#define IVR_SEQ_MAX_LEN 64
+int ivr_index_search_sequences(ivr_index *idx, const float *q /*DEV [T,d]*/, int T, int L, const int64_t *seg_off /*DEV [nseg+1] or NULL*/,
+                               int nseg, int k, int normalize_q, float *D /*DEV [T-L+1,k]*/, int64_t *I /*DEV [T-L+1,k]*/, ivr_stream stream);
+int ivr_index_range_search_sequences(ivr_index *idx, const float *q /*DEV [T,d]*/, int T, int L,
+                                     const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, float threshold, int normalize_q,
+                                     int64_t *lims /*DEV [T-L+2]*/, float *D /*DEV [cap]*/, int64_t *I /*DEV [cap]*/, int64_t cap,
+                                     ivr_stream stream);
+
 /* ---- binary codes (faiss IndexBinaryFlat, and the sign-bit encoder of IndexLSH) --------------------------
  * Stands in for faiss.IndexLSH(dimension, 256), one of the index types of _create_index (core.py:1198-1230): a row is stored as
  * nbits sign bits (32 bytes at 256 bits, where the flat index stores 2-4.6 KB) and ranked by Hamming distance.

@@ -606,6 +606,10 @@ int ivr_index_create(ivr_ctx *ctx, int d, int64_t capacity_rows, ivr_index **out
         const char *rc = getenv("IVR_REMOVE_CHUNK_ROWS");
         const long long rows = rc ? atoll(rc) : 0;
         if (rows > 0) x->remove_chunk = ivr_round_up(std::min<long long>(rows, 1ll << 22), kGroupRows);
+        // ivr_index_search_sequences: key slots per chunk of target windows (one window's stretch at least), at most 2^30
+        const char *sq = getenv("IVR_SEQ_CHUNK_SLOTS");
+        const long long slots = sq ? atoll(sq) : 0;
+        if (slots > 0) x->seq_chunk_slots = std::min<long long>(slots, 1ll << 30);
         // ivr_index_find_ids: lookups of at least this many keys go through the hash table (0: always, a huge value: never)
         const char *ft = getenv("IVR_FIND_TABLE_MIN_KEYS");
         x->find_table_min = ft && ft[0] ? std::max<long long>(0, atoll(ft)) : kFindTableMinKeys;

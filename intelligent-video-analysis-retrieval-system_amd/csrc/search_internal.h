@@ -232,6 +232,12 @@ struct ivr_index {
     DevBuf<int64_t> ivf_pair_slot;   // ... and its first key slot for that list
     // exact re-ranking of candidate lists (ivr_index_rescore, search_refine.hip); grow-only
     DevBuf<uint64_t> refine_keys;    // DEV [nq][kc]: (ordered score, ~row) of every candidate, 0 for an absent one
+    // clip search (ivr_index_search_sequences, search_seq.hip), one chunk of target windows; grow-only
+    int64_t seq_chunk_slots = 1ll << 25;     // IVR_SEQ_CHUNK_SLOTS: key slots of a chunk of windows (one window's stretch at least; read at creation)
+    DevBuf<float> seq_scores;        // DEV [frames of a chunk, whole 16-frame tiles][stored rows rounded up to 16]: frame scores S
+    DevBuf<uint64_t> seq_keys;       // DEV [windows of a chunk][N - L + 1]: (ordered window score, ~start row), 0 for a start that is no candidate
+    DevBuf<int64_t> seq_off;         // DEV [windows of a chunk][4096-key blocks of a stretch]: hits of each block, then their output positions
+    DevBuf<int64_t> seq_total;       // DEV [1]: the running total of the range call, carried from chunk to chunk
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

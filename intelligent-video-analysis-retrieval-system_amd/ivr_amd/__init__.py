@@ -1,6 +1,6 @@
 """ivr_amd: the HIP-backed pieces of the retrieval system.  The submodules are imported by name (ivr_amd.index, ivr_amd.tower, ...);
-the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index and the product- and scalar-quantisation indexes
-are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
+the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index, the product- and scalar-quantisation indexes
+and the clip search are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
 _IVF = ("IVFFlatIndex", "IndexIVFFlat", "SearchParametersIVF", "METRIC_INNER_PRODUCT", "METRIC_L2")
 _BINARY = ("BinaryFlatIndex", "IndexBinaryFlat", "IndexLSH", "lsh_rotation")
 _GRAPH = ("GraphFlatIndex", "IndexHNSWFlat", "SearchParametersHNSW", "graph_prune_ref", "graph_link_ref", "graph_build_ref",
@@ -10,7 +10,9 @@ _PQ = ("PQIndex", "IndexPQ", "pq_encode_ref", "pq_tables_ref", "pq_scan_ref")
 _SQ = ("SQIndex", "IndexScalarQuantizer", "ScalarQuantizer", "sq_encode_ref", "sq_decode_ref", "sq_query_ref", "sq_scan_ref")
 _IVFPQ = ("IVFPQIndex", "IndexIVFPQ", "ivfpq_scan_ref", "ivfpq_pack_ref", "ivfpq_unpack_ref")
 _IVFSQ = ("IVFSQIndex", "IndexIVFScalarQuantizer", "ivfsq_scan_ref", "ivfsq_pack_ref", "ivfsq_unpack_ref", "ivfsq_score_bound")
-__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _SQ + _IVFPQ + _IVFSQ)
+_TEMPORAL = ("TemporalAnalyzer", "sequence_search", "sequence_search_device", "sequence_range_search", "sequence_range_search_device",
+             "sequence_scores_ref", "sequence_search_ref", "sequence_range_ref")
+__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL)
 
 
 def __getattr__(name):
@@ -38,4 +40,7 @@ def __getattr__(name):
     if name in _IVFSQ:
         from . import ivfsq
         return getattr(ivfsq, name)
+    if name in _TEMPORAL:
+        from . import temporal
+        return getattr(temporal, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -18,6 +18,7 @@ IVR_MAX_K = 2048
 IVR_GRAPH_MAX_EF, IVR_GRAPH_MAX_CAND, IVR_GRAPH_MAX_DEGREE = 256, 64, 64       # include/ivr_api.h
 IVR_PQ_MAX_M = 128
 IVR_SQ_MAX_D = 1024
+IVR_SEQ_MAX_LEN = 64
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -105,6 +106,8 @@ _SIGS = {
     "ivr_index_search_lists": (_i, [_p, _p, _i, _p, _i, _p, _i, _i64, _i, _i, _p, _p, _p]),
     "ivr_segment_mean": (_i, [_p, _p, _i64, _p, _i, _i, _i, _p, _p]),
     "ivr_index_rescore": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "ivr_index_search_sequences": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
+    "ivr_index_range_search_sequences": (_i, [_p, _p, _i, _i, _p, _i, _f, _i, _p, _p, _p, _i64, _p]),
     "ivr_bin_index_create": (_i, [_p, _i, _i64, C.POINTER(_p)]),
     "ivr_bin_index_destroy": (_i, [_p]),
     "ivr_bin_index_reset": (_i, [_p]),
@@ -174,7 +177,8 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_index_add", "ivr_index_write", "ivr_index_write_ring", "ivr_index_reconstruct", "ivr_index_search", "ivr_index_range_search",
     "ivr_index_search_filtered", "ivr_index_range_search_filtered", "ivr_index_remove_ids", "ivr_index_add_with_ids",
     "ivr_index_get_ids", "ivr_index_find_ids", "ivr_index_gather", "ivr_index_scatter", "ivr_index_search_reconstruct",
-    "ivr_index_search_lists", "ivr_segment_mean", "ivr_index_rescore", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
+    "ivr_index_search_lists", "ivr_segment_mean", "ivr_index_rescore", "ivr_index_search_sequences",
+    "ivr_index_range_search_sequences", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
     "ivr_sign_encode", "ivr_pq_encode", "ivr_pq_tables", "ivr_bin_index_search_pq", "ivr_ivfpq_set_lists", "ivr_ivfpq_get_codes",
     "ivr_ivfpq_search", "ivr_ivfsq_set_lists", "ivr_ivfsq_get_codes", "ivr_ivfsq_search", "ivr_sq_encode", "ivr_sq_query", "ivr_sq_index_add",
     "ivr_sq_index_get_codes", "ivr_sq_index_search", "ivr_graph_set_rows", "ivr_graph_prune",

@@ -81,6 +81,18 @@ def check_nq(nq, what="search"):
         raise ValueError(f"{what}: no queries")
 
 
+def check_window(L, T, lmax, what):
+    """The window length of a clip search over T frames: an integer in [1, lmax], at most T."""
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)):
+        raise ValueError(f"{what}: L must be an integer, got {type(L).__name__}")
+    L = int(L)
+    if L < 1 or L > lmax:
+        raise ValueError(f"{what}: L={L} outside [1,{lmax}]")
+    if T < L:
+        raise ValueError(f"{what}: T={T} frames < L={L}")
+    return L
+
+
 def alloc_DI(nq, k, device, dtype=torch.float32):
     """The (D, I) pair of a search: D `dtype` [nq,k], I int64 [nq,k]."""
     return torch.empty((nq, k), dtype=dtype, device=device), torch.empty((nq, k), dtype=torch.int64, device=device)
@@ -97,6 +109,21 @@ def int_tensor(a, name, verb="be", np_dtype=None):
     if not isinstance(a, torch.Tensor) or a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool:
         raise ValueError(f"{name} must be an integer numpy array or torch tensor")
     return a
+
+
+def segment_offsets(seg_off, device, what):
+    """Segment offsets (integers [nseg+1], nseg >= 1, ascending) -> (contiguous int64 tensor on `device`, is_staged).  The order is
+    checked on a host array; a CUDA tensor is taken as it is (no host sync)."""
+    t = int_tensor(seg_off, f"{what}: seg_off")
+    if t.dim() != 1 or t.shape[0] < 2:
+        raise ValueError(f"{what}: seg_off must be [nseg+1] with nseg >= 1, got {tuple(t.shape)}")
+    if not t.is_cuda and t.shape[0] > 1:
+        bad = torch.nonzero(t[1:] < t[:-1])
+        if len(bad):
+            i = int(bad[0])
+            raise ValueError(f"{what}: seg_off must ascend, got seg_off[{i}]={int(t[i])} > seg_off[{i + 1}]={int(t[i + 1])}")
+    d = t.to(device=device, dtype=torch.int64).contiguous()
+    return d, is_staged(d, seg_off)
 
 
 def check_entries(t, n, name):
