@@ -651,6 +651,54 @@ int ivr_ivfsq_search(ivr_ivfsq *idx, const int16_t *t /*DEV [nq][d]*/, const flo
                      const float *coarse /*DEV [nq][p] or NULL*/, const int64_t *assign /*DEV [nq][p]*/, int nq, int p, int k,
                      float *D /*DEV [nq][k]*/, int64_t *I /*DEV [nq][k]*/, ivr_stream stream);
 
+/* ---- 4-bit product quantisation (faiss IndexPQFastScan, inner product) --------------------------------------------------
+ * M sub-quantizers of 16 centroids each: a row is M / 2 bytes, byte j = code[2 j] | code[2 j + 1] << 4 (faiss's packing), and is
+ * ranked by a sum of M lookups in 16-entry tables of 8-bit values that the scan holds in registers ("4-bit
+ * product quantisation"; the definitions are the numpy functions pqfs_encode_ref, pqfs_tables_ref, pqfs_quantize_ref and
+ * pqfs_scan_ref of ivr_amd/pqfs.py).  M even, 2 <= M <= IVR_PQFS_MAX_M, d % M == 0, IVR_ERR_INVALID otherwise: 255 M fits the
+ * unsigned 16-bit accumulator of the scan.  centroids: DEV float32 [M][16][d / M]. */
+#define IVR_PQFS_MAX_M 256
+int ivr_pqfs_pass_queries(void);        /* queries that share one pass over the stored codes */
+/* codes[i][j] = c(2 j) | c(2 j + 1) << 4 with c(m) the centroid of slice m nearest to slice m of x[i]: sum_t (x_t - c_t)^2 in float32,
+ * ascending t, equal distances the lower centroid (pqfs_encode_ref states the tolerance).  n == 0 is a no-op.  Enqueue-only. */
+int ivr_pqfs_encode(ivr_ctx *ctx, const float *x /*DEV [n][d]*/, int64_t n, int d, const float *centroids, int M,
+                    uint8_t *codes /*DEV [n][M / 2]*/, ivr_stream stream);
+/* The tables of a batch of queries in one call.  T[i][m][j] = <slice m of q[i], centroids[m][j]>, float32 from zero in ascending
+ * coordinate order (within (d / M + 2) 2^-24 sum |q_t c_t| of the exact sum); written when T != NULL.  From those floats, every
+ * step one float32 rounding and no fused multiply-add: lo[m] = min_j T[m][j], span = max_m (max_j T[m][j] - lo[m]), a = 255 / span,
+ * U[m][j] = clamp(rint((T[m][j] - lo[m]) * a), 0, 255) (ties to even), scale = span / 255, bias = ((lo[0] + lo[1]) + ...) in
+ * ascending m; a = 0, U = 0 and scale = 0 when span == 0 or 255 / span is not finite.  q must be finite.  nq >= 1.  Enqueue-only. */
+int ivr_pqfs_tables(ivr_ctx *ctx, const float *q /*DEV [nq][d]*/, int nq, int d, const float *centroids, int M,
+                    float *T /*DEV [nq][M][16] or NULL*/, uint8_t *U /*DEV [nq][M][16]*/, float *scale /*DEV [nq]*/,
+                    float *bias /*DEV [nq]*/, ivr_stream stream);
+/* the quantiser of ivr_pqfs_tables alone, on caller-supplied finite float tables */
+int ivr_pqfs_quantize(ivr_ctx *ctx, const float *T /*DEV [nq][M][16]*/, int nq, int M, uint8_t *U /*DEV [nq][M][16]*/,
+                      float *scale /*DEV [nq]*/, float *bias /*DEV [nq]*/, ivr_stream stream);
+/* The stored codes, per block of 256 rows: lane l of a wave holds rows l, l + 64, l + 128 and l + 192, dword j of the lane is byte j
+ * of those four rows, and 8 sub-quantizers (4 dwords) are one 16-byte word per lane, 1 KiB contiguous per wave; the sub-quantizers
+ * behind M hold code 0.  Rows are allocated by the first add, in whole blocks; capacity below 2^31 rows. */
+typedef struct ivr_pqfs_index ivr_pqfs_index;
+int ivr_pqfs_index_create(ivr_ctx *ctx, int M, ivr_pqfs_index **out);
+int ivr_pqfs_index_destroy(ivr_pqfs_index *idx);            /* IVR_ERR_INVALID for NULL, as every entry of this section */
+int ivr_pqfs_index_reset(ivr_pqfs_index *idx);              /* ntotal = 0; the bytes stay and are never read as rows */
+int64_t ivr_pqfs_index_ntotal(ivr_pqfs_index *idx);         /* -1 for NULL */
+/* append n codes as ivr_pqfs_encode makes them; writes the new rows only */
+int ivr_pqfs_index_add(ivr_pqfs_index *idx, const uint8_t *codes /*DEV [n][M / 2]*/, int64_t n, ivr_stream stream);
+/* codes of rows [start, start + n) as they were added; start + n <= ntotal */
+int ivr_pqfs_index_get_codes(ivr_pqfs_index *idx, int64_t start, int64_t n, uint8_t *out /*DEV [n][M / 2]*/, ivr_stream stream);
+/* Integer top k.  acc of row r for query i = sum_m U[i][m][code[r][m]], exact (at most 255 M <= 65280).  Rows are ranked by (acc
+ * descending, row ascending): integers only.  D = float(acc) * scale[i] + bias[i]: one conversion, one float32 multiplication, one
+ * float32 addition; I the row number; unused slots (k > ntotal, empty index) -FLT_MAX / -1.  Exact: the best acc of every 64-row
+ * group is written, the best k groups are selected, their rows re-scored into 64-bit keys (acc ^ 0x80000000) << 32 | ~row and the
+ * best k keys selected.  U 16-byte aligned.  1 <= k <= IVR_MAX_K, nq >= 1.  The codes are read once per ivr_pqfs_pass_queries()
+ * queries; a table reaches the lookups through a wave-uniform (scalar) load, and a lookup of four rows is two v_perm_b32 and a
+ * v_bfi_b32.  Scratch: 128 ceil(M / 8) bytes per query, and per chunk of queries (at most 4096, fewer when k or the index is large)
+ * 4 bytes per (query, 64-row group) and 520 bytes per (query, selected group), grow-only.  Enqueue-only once the scratch has grown
+ * (a call that grows it allocates and cannot be captured into a hipGraph). */
+int ivr_pqfs_index_search(ivr_pqfs_index *idx, const uint8_t *U /*DEV [nq][M][16]*/, const float *scale /*DEV [nq]*/,
+                          const float *bias /*DEV [nq]*/, int nq, int k, float *D /*DEV [nq][k]*/, int64_t *I /*DEV [nq][k]*/,
+                          ivr_stream stream);
+
 /* ---- graph index (in the place of faiss IndexHNSWFlat) ------------------------------------------------------
  * Stands in for faiss.IndexHNSWFlat(dimension, 32), the IndexHNSW type of _create_index (core.py:1213-1214).  It is NOT a port of
  * faiss's HNSW: one layer of fixed out-degree (2 M, HNSW's level-0 width), built in bulk from exact kNN lists, entered through

@@ -1,5 +1,5 @@
 """ivr_amd: the HIP-backed pieces of the retrieval system.  The submodules are imported by name (ivr_amd.index, ivr_amd.tower, ...);
-the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index, the product- and scalar-quantisation indexes
+the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index, the product-quantisation (8- and 4-bit codes) and scalar-quantisation indexes
 and the clip search are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
 _IVF = ("IVFFlatIndex", "IndexIVFFlat", "SearchParametersIVF", "METRIC_INNER_PRODUCT", "METRIC_L2")
 _BINARY = ("BinaryFlatIndex", "IndexBinaryFlat", "IndexLSH", "lsh_rotation")
@@ -7,12 +7,14 @@ _GRAPH = ("GraphFlatIndex", "IndexHNSWFlat", "SearchParametersHNSW", "graph_prun
           "graph_search_ref")
 _REFINE = ("RefineFlatIndex", "IndexRefineFlat", "IndexRefineSearchParameters", "refine_order_ref")
 _PQ = ("PQIndex", "IndexPQ", "pq_encode_ref", "pq_tables_ref", "pq_scan_ref")
+_PQFS = ("PQFastScanIndex", "IndexPQFastScan", "pqfs_pack_ref", "pqfs_unpack_ref", "pqfs_encode_ref", "pqfs_tables_ref",
+         "pqfs_quantize_ref", "pqfs_scan_ref", "pqfs_score_bound")
 _SQ = ("SQIndex", "IndexScalarQuantizer", "ScalarQuantizer", "sq_encode_ref", "sq_decode_ref", "sq_query_ref", "sq_scan_ref")
 _IVFPQ = ("IVFPQIndex", "IndexIVFPQ", "ivfpq_scan_ref", "ivfpq_pack_ref", "ivfpq_unpack_ref")
 _IVFSQ = ("IVFSQIndex", "IndexIVFScalarQuantizer", "ivfsq_scan_ref", "ivfsq_pack_ref", "ivfsq_unpack_ref", "ivfsq_score_bound")
 _TEMPORAL = ("TemporalAnalyzer", "sequence_search", "sequence_search_device", "sequence_range_search", "sequence_range_search_device",
              "sequence_scores_ref", "sequence_search_ref", "sequence_range_ref")
-__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL)
+__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _PQFS + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL)
 
 
 def __getattr__(name):
@@ -31,6 +33,9 @@ def __getattr__(name):
     if name in _PQ:
         from . import pq
         return getattr(pq, name)
+    if name in _PQFS:
+        from . import pqfs
+        return getattr(pqfs, name)
     if name in _SQ:
         from . import sq
         return getattr(sq, name)

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("IVR_LIB") or os.path.join(os.path.dirname(_HERE), "li
 IVR_MAX_K = 2048
 IVR_GRAPH_MAX_EF, IVR_GRAPH_MAX_CAND, IVR_GRAPH_MAX_DEGREE = 256, 64, 64       # include/ivr_api.h
 IVR_PQ_MAX_M = 128
+IVR_PQFS_MAX_M = 256
 IVR_SQ_MAX_D = 1024
 IVR_SEQ_MAX_LEN = 64
 # flags of ivr_preprocess
@@ -144,6 +145,17 @@ _SIGS = {
     "ivr_sq_index_add": (_i, [_p, _p, _i64, _p]),
     "ivr_sq_index_get_codes": (_i, [_p, _i64, _i64, _p, _p]),
     "ivr_sq_index_search": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "ivr_pqfs_pass_queries": (_i, []),
+    "ivr_pqfs_encode": (_i, [_p, _p, _i64, _i, _p, _i, _p, _p]),
+    "ivr_pqfs_tables": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
+    "ivr_pqfs_quantize": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
+    "ivr_pqfs_index_create": (_i, [_p, _i, C.POINTER(_p)]),
+    "ivr_pqfs_index_destroy": (_i, [_p]),
+    "ivr_pqfs_index_reset": (_i, [_p]),
+    "ivr_pqfs_index_ntotal": (_i64, [_p]),
+    "ivr_pqfs_index_add": (_i, [_p, _p, _i64, _p]),
+    "ivr_pqfs_index_get_codes": (_i, [_p, _i64, _i64, _p, _p]),
+    "ivr_pqfs_index_search": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "ivr_graph_max_ef": (_i, []),
     "ivr_graph_max_cand": (_i, []),
     "ivr_graph_create": (_i, [_p, _i, _i, C.POINTER(_p)]),
@@ -169,7 +181,8 @@ EXPORTS = tuple(_SIGS)
 _VALUE = frozenset(("ivr_api_version", "ivr_last_error", "ivr_preprocess_scratch_bytes", "ivr_tower_workspace_bytes", "ivr_index_ntotal",
                     "ivr_index_dim", "ivr_index_capacity", "ivr_index_has_ids", "ivr_bin_index_ntotal", "ivr_bin_index_block_rows",
                     "ivr_graph_max_ef", "ivr_graph_max_cand", "ivr_graph_ntotal", "ivr_frame_quality_scratch_bytes",
-                    "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries", "ivr_ivfsq_ntotal"))
+                    "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries", "ivr_ivfsq_ntotal",
+                    "ivr_pqfs_pass_queries", "ivr_pqfs_index_ntotal"))
 # the slot of the ivr_stream argument (the last one wherever there is one): call() fills it when the caller leaves it out
 _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_release_stream_scratch", "ivr_preprocess", "ivr_tower_encode_image", "ivr_tower_encode_text", "ivr_tower_debug_hidden",
@@ -181,7 +194,8 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_index_range_search_sequences", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
     "ivr_sign_encode", "ivr_pq_encode", "ivr_pq_tables", "ivr_bin_index_search_pq", "ivr_ivfpq_set_lists", "ivr_ivfpq_get_codes",
     "ivr_ivfpq_search", "ivr_ivfsq_set_lists", "ivr_ivfsq_get_codes", "ivr_ivfsq_search", "ivr_sq_encode", "ivr_sq_query", "ivr_sq_index_add",
-    "ivr_sq_index_get_codes", "ivr_sq_index_search", "ivr_graph_set_rows", "ivr_graph_prune",
+    "ivr_sq_index_get_codes", "ivr_sq_index_search", "ivr_pqfs_encode", "ivr_pqfs_tables", "ivr_pqfs_quantize", "ivr_pqfs_index_add",
+    "ivr_pqfs_index_get_codes", "ivr_pqfs_index_search", "ivr_graph_set_rows", "ivr_graph_prune",
     "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
     "ivr_scene_keep_mask_window", "ivr_frame_quality")}
