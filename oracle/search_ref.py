@@ -90,6 +90,18 @@ def flat_ip_search(xb, xq, k, dtype=np.float32):
     return D, I
 
 
+def flat_ip_bound(X, Q):
+    """Every score of a flat inner-product index with its float32 error bound: (S float64 [nq,n], bound float64 [nq,n]) with
+    S = Q X^T in float64 and bound = (d + 8) 2^-24 sum_i |q_i x_i|, the bound of a float32 sum of d products accumulated one after
+    the other (each addition rounds once, unit roundoff 2^-24; the 8 covers the rounding of the products and of the result).  A
+    kernel that accumulates in any other order of the same length, or in wider steps, stays inside it."""
+    X = np.asarray(X, dtype=np.float64)
+    Q = np.asarray(Q, dtype=np.float64)
+    if Q.ndim == 1:
+        Q = Q.reshape(1, -1)
+    return Q @ X.T, (X.shape[1] + 8) * 2.0 ** -24 * (np.abs(Q) @ np.abs(X).T)
+
+
 def search_vectors_rows(D_row, I_row, has_metadata=None, filter_func=None):
     """unified_index.py:507-526 on one query's (D,I): list of (rank, similarity_score, index)."""
     out = []

@@ -59,6 +59,49 @@ def test_shapes_vs_oracle(n, d, nq, k):
     _check(X, Q, k, atol=1e-4 * np.sqrt(d))
 
 
+def _score_operands(kind, rng, n, d, nq=5):
+    X = rng.standard_normal((n, d))
+    Q = rng.standard_normal((nq, d))
+    if kind == "scaled":                       # every row at its own power of two over 2^-20 .. 2^20
+        X *= 2.0 ** rng.integers(-20, 21, (n, 1))
+    elif kind == "cancel":                     # pairs (a, -a + 2^-12 g) along K against pairwise equal query elements: |score| << sum|q_i x_i|
+        h = d // 2
+        X[:, 1:2 * h:2] = -X[:, 0:2 * h:2] + 2.0 ** -12 * rng.standard_normal((n, h))
+        Q[:, 1:2 * h:2] = Q[:, 0:2 * h:2]
+        X[:, 2 * h:] *= 2.0 ** -12               # odd d: the unpaired last element is as small as what the pairs leave
+    elif kind != "gauss":
+        raise ValueError(kind)
+    return X.astype(np.float32), Q.astype(np.float32)
+
+
+@pytest.mark.parametrize("d", [1, 3, 4, 7, 16, 17, 100, 250, 512, 2048])
+def test_every_score_within_the_float32_accumulation_bound(d):
+    """Every (query, row) score of the index - read through rescore_device with all rows as candidates, which reports the bits search()
+    reports - against float64, element by element: |got - ref| <= (d + 8) 2^-24 sum|q_i x_i| (oracle/search_ref.py flat_ip_bound).  The
+    bf16 candidate scan's error bounds are measured against this score."""
+    worst = 0.0
+    for n in (1, 63, 65, 1000):
+        for ki, kind in enumerate(("gauss", "scaled", "cancel")):
+            X, Q = _score_operands(kind, np.random.default_rng(d * 131 + n * 3 + ki), n, d)
+            idx = _index(X)
+            cand = torch.arange(n, dtype=torch.int64, device="cuda").repeat(len(Q), 1).contiguous()
+            D, I, D_all = idx.rescore_device(Q, cand, k=1, want_all=True)
+            got = D_all.cpu().numpy().astype(np.float64)
+            ref, bound = S.flat_ip_bound(X, Q)
+            assert got.shape == ref.shape and np.isfinite(got).all()
+            err = np.abs(got - ref)
+            assert (err[bound == 0] == 0).all()
+            r = float((err[bound > 0] / bound[bound > 0]).max(initial=0.0))
+            worst = max(worst, r)
+            assert r <= 1.0, (d, n, kind, r)
+            if kind == "cancel" and d >= 2:
+                assert np.abs(ref).max() < 1e-2 * (np.abs(Q.astype(np.float64)) @ np.abs(X.astype(np.float64)).T).max()
+            # the top score of search() carries the same bits
+            Ds, Is = idx.search_device(Q, 1)
+            assert torch.equal(Ds, D) and torch.equal(Is, I)
+    print(f"d={d}: largest |score - float64| / bound = {worst:.3f}")
+
+
 def test_k_larger_than_ntotal_and_empty():
     rng = np.random.default_rng(1)
     X = rng.standard_normal((5, 32), dtype=np.float32)
