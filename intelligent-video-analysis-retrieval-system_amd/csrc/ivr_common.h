@@ -54,6 +54,8 @@ int ivr_ctx_scratch(ivr_ctx *ctx, hipStream_t stream, size_t bytes, void **out);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel) and size: the opt-in is per device, and towers /
 // indexes of several devices may live in one process
 int ivr_func_max_lds(const void *fn, int bytes);
+// the environment variable `name` as a positive decimal integer; dflt when it is unset, empty, not a number or not positive
+long long ivr_env_positive(const char *name, long long dflt);
 
 // Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
 // `work` is the launch's algorithmic work: bytes for HBM-bound kernels, FLOP for MFMA-bound ones.

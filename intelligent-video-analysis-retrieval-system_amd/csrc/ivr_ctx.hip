@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -57,6 +58,14 @@ int ivr_func_max_lds(const void *fn, int bytes) {
         have = bytes;
     }
     return IVR_OK;
+}
+
+long long ivr_env_positive(const char *name, long long dflt) {
+    const char *e = std::getenv(name);
+    if (!e || !*e) return dflt;
+    char *end = nullptr;
+    const long long v = std::strtoll(e, &end, 10);
+    return end && *end == 0 && v > 0 ? v : dflt;
 }
 
 namespace {

@@ -610,6 +610,8 @@ int ivr_index_create(ivr_ctx *ctx, int d, int64_t capacity_rows, ivr_index **out
         const char *sq = getenv("IVR_SEQ_CHUNK_SLOTS");
         const long long slots = sq ? atoll(sq) : 0;
         if (slots > 0) x->seq_chunk_slots = std::min<long long>(slots, 1ll << 30);
+        // ivr_index_search_lists: key slots per chunk of queries (one query's stretch at least; tests force several chunks)
+        x->ivf.chunk_slots = ivr_env_positive("IVR_IVF_CHUNK_SLOTS", kIvfChunkSlots);
         // ivr_index_find_ids: lookups of at least this many keys go through the hash table (0: always, a huge value: never)
         const char *ft = getenv("IVR_FIND_TABLE_MIN_KEYS");
         x->find_table_min = ft && ft[0] ? std::max<long long>(0, atoll(ft)) : kFindTableMinKeys;

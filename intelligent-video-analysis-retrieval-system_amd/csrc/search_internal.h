@@ -4,7 +4,8 @@
 // than one of them needs: the index object with the plan of a search, the view a search scans, the row mask of a filtered search, and
 // the launchers that are defined in one file and called from another.  search_rows.hip (gather / scatter of rows by position) uses it
 // too, and so do search_binary.hip, search_pq.hip and search_sq.hip for the coded-index structs at its end.  It also holds the device
-// helpers that every search file spells the same way: ivr_key, ivr_wave_incl_scan, ivr_last_le and probe_valid.  Not part of the C ABI.
+// helpers that every search file spells the same way: ivr_key, ivr_wave_incl_scan, ivr_last_le, ivr_comp and probe_valid, and
+// ProbeTables, the probe tables of the inverted-list scans (search_lists.hip).  Not part of the C ABI.
 #pragma once
 #include "ivr_common.h"
 
@@ -131,6 +132,9 @@ __device__ __forceinline__ int ivr_last_le(const int64_t *off, int n, int64_t v)
     return lo;
 }
 
+// component c of a 16-byte word (the table-lookup scans walk a code four bytes at a time)
+__device__ __forceinline__ uint32_t ivr_comp(const uint4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
+
 // An inverted-file search names its lists in assign [nq][p], every row ascending (so a list named twice sits in adjacent entries and
 // counts once); entries outside [0, nlist) are skipped.  true: entry j of row a is the first mention of a valid list
 __device__ __forceinline__ bool probe_valid(const int64_t *__restrict__ a, int j, int p, int nlist) {
@@ -163,6 +167,40 @@ typedef std::initializer_list<std::pair<DevMem *, size_t>> DevSizes;
 int ivr_reserve(DevSizes bufs, bool zero = false);
 // every buffer of the group empty again (the sizes are not read); the first error, if any
 int ivr_release(DevSizes bufs);
+
+// ---- probe tables of a list-major inverted-list scan (defined in search_lists.hip) ---------------------------------------------
+// keys of the scratch a chunk of queries may fill: 2^25 slots of 8 bytes = 256 MiB, plus one query's stretch when a single query
+// probes more rows than that (its stretch is never split)
+constexpr int64_t kIvfChunkSlots = 1ll << 25;
+// pairs of a chunk: bounds the pair tables (20 bytes per pair) at 80 MiB
+constexpr int64_t kIvfChunkPairs = 1ll << 22;
+
+// The scratch, the chunk plan and the table build of a scan that groups the (query, list) pairs of a chunk of queries by list
+// (search_ivf.hip, search_ivfsq.hip).  Grow-only.
+struct ProbeTables {
+    int64_t chunk_slots = kIvfChunkSlots;    // key slots of a chunk of queries (one query's stretch at least)
+    DevBuf<uint64_t> keys;               // [chunk][qstride]: the key of every probed row, in its query's own stretch
+    DevBuf<int64_t> slot;                // [chunk][p]: first key slot of each probed list, -1 for a skipped entry
+    DevBuf<int64_t> qtotal;              // [chunk]: rows each query probes
+    DevBuf<int> count;                   // [nlist]: queries per list, then the fill cursors
+    DevBuf<int64_t> off;                 // [nlist + 1] pairs in front of each list, then [nlist + 1] 16-query pair tiles in front of it
+    DevBuf<int> pair_q;                  // [pairs of a chunk]: the (query, list) pairs grouped by list: the query of the chunk ...
+    DevBuf<int64_t> pair_slot;           // ... and its first key slot for that list
+    int64_t *pair_off() const { return off; }
+    int64_t *tile_off(int nlist) const { return (int64_t *)off + nlist + 1; }
+    // pair tiles of a chunk of npairs pairs at most: every probed list has one partly filled tile at most
+    static int64_t tiles(int nlist, int64_t npairs) { return std::min<int64_t>(nlist, npairs) + npairs / 16; }
+    // The plan of a search of nq queries that name p lists each and may probe qstride rows each: chunk = queries per chunk (the
+    // scratch holds chunk_slots keys, the pair tables kIvfChunkPairs pairs), nkeys = key slots of a chunk; reserves one chunk
+    int plan(int nq, int p, int64_t qstride, int nlist, int *chunk, int64_t *nkeys);
+    // The tables of the nqc queries whose ascending assign rows [nqc][p] start at `assign`, over the lists list_off [nlist + 1] of
+    // ntotal rows: a memset and four launches on stream s (probe_slots, probe_count, probe_offsets, probe_fill); the caller checks
+    // the launches
+    int build(const int64_t *assign, int p, int nqc, const int64_t *list_off, int nlist, int64_t ntotal, int64_t qstride, hipStream_t s);
+    // The best k keys of each of the nqc queries' stretches -> D, I [nqc][k]; the label of a key's low word r is ids[r], or r itself
+    // without ids (select_topk_kernel, one workgroup per query)
+    void select(int nqc, int k, int64_t qstride, float *D, int64_t *I, const int64_t *ids, hipStream_t s);
+};
 
 struct ivr_index {
     ivr_ctx *ctx = nullptr;
@@ -222,14 +260,7 @@ struct ivr_index {
     bool tab_ok = false;             // the table matches ids[0 .. ntotal): cleared by add_with_ids, remove_ids and reset
     // ivr_index_search_reconstruct (search_rows.hip): the row position behind every result slot of a search
     DevBuf<int64_t> rpos;            // DEV [nq][k], sized by ivr_index_reserve_search
-    // inverted-list search (ivr_index_search_lists, search_ivf.hip), one chunk of queries; grow-only
-    DevBuf<uint64_t> ivf_keys;       // DEV [queries of a chunk][rows one query may probe]: (ordered score, ~row) of every probed row
-    DevBuf<int64_t> ivf_slot;        // DEV [queries of a chunk][p]: first key slot of each probed list, -1 for a skipped entry
-    DevBuf<int64_t> ivf_qtotal;      // DEV [queries of a chunk]: rows each query probes
-    DevBuf<int> ivf_count;           // DEV [nlist]: queries per list, then the fill cursors
-    DevBuf<int64_t> ivf_off;         // DEV [nlist + 1] pairs in front of each list, then [nlist + 1] 16-query pair tiles in front of it
-    DevBuf<int> ivf_pair_q;          // DEV [pairs of a chunk]: the (query, list) pairs grouped by list: the query of the chunk ...
-    DevBuf<int64_t> ivf_pair_slot;   // ... and its first key slot for that list
+    ProbeTables ivf;                 // inverted-list search (ivr_index_search_lists, search_ivf.hip); chunk_slots: IVR_IVF_CHUNK_SLOTS (read at creation)
     // exact re-ranking of candidate lists (ivr_index_rescore, search_refine.hip); grow-only
     DevBuf<uint64_t> refine_keys;    // DEV [nq][kc]: (ordered score, ~row) of every candidate, 0 for an absent one
     // clip search (ivr_index_search_sequences, search_seq.hip), one chunk of target windows; grow-only
@@ -315,6 +346,9 @@ int ivr_reserve_queries(ivr_index *x, int qtiles);
 int ivr_reserve_gmax(ivr_index *x);
 void ivr_launch_scan_qt(ivr_index *x, const View &v, int qt, const float *qtile, hipStream_t s, const int *tile_flag = nullptr);
 void ivr_launch_fast_scan(ivr_index *x, const View &v, int qt, int64_t tile0, hipStream_t s);
+// search_sq.hip.  t int16 [nq][d] -> the int8 halves t = 128 h + l of the int8 MFMA scans, tiled per 16 queries: qh and ql
+// [qtiles][ksteps][64], zeros past d and past nq
+void ivr_launch_sq_stage(const int16_t *t, int nq, int d, int ksteps, int64_t qtiles, uint4 *qh, uint4 *ql, hipStream_t s);
 // search_scanq.hip
 int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s, const RowMask *mask = nullptr);
 

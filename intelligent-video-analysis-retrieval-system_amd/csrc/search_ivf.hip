@@ -17,11 +17,11 @@
 //   probe_fill    one thread per pair: the pairs grouped by list
 //   list_scan     one workgroup per (pair tile, row split): scores -> keys
 //   select_topk   one workgroup per query
-// The four probe kernels, list_run and SrcSlots are in search_lists.h: search_ivfsq.hip builds the same tables.
+// The probe tables and the selection over the key stretches are ProbeTables' (search_internal.h, search_lists.hip: the four probe
+// kernels, build, select); search_ivfsq.hip scans the same tables.  Only list_scan_kernel is emitted here.
 #include "ivr_common.h"
 #include "search_internal.h"
 #include "search_lists.h"
-#include "search_select.h"
 
 namespace {
 
@@ -156,14 +156,11 @@ int ivr_index_search_lists(ivr_index *x, const int64_t *list_off, int nlist, con
     std::lock_guard<std::mutex> lk(x->mu);
     IVR_HIP(hipSetDevice(x->ctx->device));
     const int64_t qstride = std::min(max_probe_rows, x->ntotal);
-    // queries per chunk: the scratch holds kIvfChunkSlots keys (one query's stretch at least), the pair tables kIvfChunkPairs pairs
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nq, kIvfChunkSlots / std::max<int64_t>(qstride, 1), kIvfChunkPairs / p}));
-    const int64_t nkeys = (int64_t)chunk * qstride, cpairs = (int64_t)chunk * p;
+    ProbeTables &pt = x->ivf;
+    int chunk;
+    int64_t nkeys;
     int rc = ivr_reserve_queries(x, (int)ivr_ceil_div(nq, 16));
-    if (rc == IVR_OK)
-        rc = ivr_reserve({{&x->ivf_keys, (size_t)std::max<int64_t>(nkeys, 1) * 8}, {&x->ivf_slot, (size_t)cpairs * 8}, {&x->ivf_qtotal, (size_t)chunk * 8},
-                          {&x->ivf_pair_q, (size_t)cpairs * 4}, {&x->ivf_pair_slot, (size_t)cpairs * 8}});
-    if (rc == IVR_OK) rc = ivr_reserve({{&x->ivf_count, (size_t)nlist * 4}, {&x->ivf_off, (size_t)(nlist + 1) * 16}}, true);
+    if (rc == IVR_OK) rc = pt.plan(nq, p, qstride, nlist, &chunk, &nkeys);
     if (rc != IVR_OK) return rc;
     rc = ivr_launch_tile_rows(x, x->qtiled, q, 0, nq, normalize_q, nullptr, s);
     if (rc != IVR_OK) return rc;
@@ -172,37 +169,25 @@ int ivr_index_search_lists(ivr_index *x, const int64_t *list_off, int nlist, con
     if (rc != IVR_OK) return rc;
     // row splits of a list: 256 rows each, for a list as long as everything one query may probe; at most 64, longer lists loop
     const unsigned ysplit = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ivr_ceil_div(qstride, 256)));
-    int64_t *pair_off = x->ivf_off, *tile_off = pair_off + nlist + 1;
     for (int q0 = 0; q0 < nq; q0 += chunk) {
         const int nqc = std::min(chunk, nq - q0);
         const int64_t npairs = (int64_t)nqc * p;
         const int64_t *a = assign + (int64_t)q0 * p;
         {
             IvrProf prof("ivf_probe_tables", s, (double)npairs * 48, true);
-            IVR_HIP(hipMemsetAsync((int *)x->ivf_count, 0, (size_t)nlist * 4, s));
-            hipLaunchKernelGGL(probe_slots_kernel, dim3((unsigned)ivr_ceil_div(nqc, 4)), dim3(256), 0, s, a, p, nqc, list_off, nlist, x->ntotal,
-                               qstride, (int64_t *)x->ivf_slot, (int64_t *)x->ivf_qtotal);
-            hipLaunchKernelGGL(probe_count_kernel, dim3((unsigned)ivr_ceil_div(npairs, 256)), dim3(256), 0, s, a, (const int64_t *)x->ivf_slot,
-                               npairs, (int *)x->ivf_count);
-            hipLaunchKernelGGL(probe_offsets_kernel, dim3(1), dim3(256), 0, s, (int *)x->ivf_count, nlist, pair_off, tile_off);
-            hipLaunchKernelGGL(probe_fill_kernel, dim3((unsigned)ivr_ceil_div(npairs, 256)), dim3(256), 0, s, a, (const int64_t *)x->ivf_slot, p,
-                               npairs, (int *)x->ivf_count, pair_off, (int *)x->ivf_pair_q, (int64_t *)x->ivf_pair_slot);
+            rc = pt.build(a, p, nqc, list_off, nlist, x->ntotal, qstride, s);
+            if (rc != IVR_OK) return rc;
             IVR_LAUNCH_CHECK();
         }
         if (x->ntotal > 0 && qstride > 0) {
-            // pair tiles of the chunk: every probed list has one partly filled tile at most
-            const int64_t tiles = std::min<int64_t>(nlist, npairs) + npairs / 16;
             ListScan ls{reinterpret_cast<const float4 *>(x->data), reinterpret_cast<const float4 *>((const float *)x->qtiled), x->dp4, nlist, q0, nqc,
-                        x->ntotal, list_off, pair_off, tile_off, x->ivf_pair_q, x->ivf_pair_slot, x->ivf_keys, nkeys};
+                        x->ntotal, list_off, pt.pair_off(), pt.tile_off(nlist), pt.pair_q, pt.pair_slot, pt.keys, nkeys};
             IvrProf prof("ivf_list_scan", s, 0.0);
-            hipLaunchKernelGGL(list_scan_kernel, dim3((unsigned)tiles, ysplit), dim3(256), lds, s, ls);
+            hipLaunchKernelGGL(list_scan_kernel, dim3((unsigned)ProbeTables::tiles(nlist, npairs), ysplit), dim3(256), lds, s, ls);
             IVR_LAUNCH_CHECK();
         }
         IvrProf prof("select_final", s, (double)nqc * qstride * 8, true);
-        const SrcSlots src{x->ivf_keys, x->ivf_qtotal, qstride, qstride};
-        const SelectOut o = SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, 0, x->has_ids ? x->ids : nullptr);
-        if (o.ids) launch_select<OUT_DI_IDS>(src, nqc, k, o, s);
-        else launch_select<OUT_DI>(src, nqc, k, o, s);
+        pt.select(nqc, k, qstride, D + (int64_t)q0 * k, I + (int64_t)q0 * k, x->has_ids ? x->ids : nullptr, s);
         IVR_LAUNCH_CHECK();
     }
     return IVR_OK;

@@ -2,8 +2,8 @@
 // _get_codes) and the probed table-lookup top-k (ivr_ivfpq_search).  DESIGN.md section 4, "inverted lists over PQ codes"; the
 // definitions are the numpy functions ivfpq_pack_ref, ivfpq_unpack_ref and ivfpq_scan_ref of ivr_amd/ivfpq.py.
 //
-// Storage.  A code is M bytes (search_pq.hip).  The codes are ordered by list and every list is padded to whole 64-row groups: list l
-// owns the groups [goff[l], goff[l + 1]), goff = the exclusive prefix of ceil(size / 64).  Inside a group the layout is that of
+// Storage.  A code is M bytes (search_pq.hip).  The store is a ListRows (search_lists.h): the codes ordered by list, every list padded
+// to whole 64-row groups, list l owning the groups [goff[l], goff[l + 1]), goff = the exclusive prefix of ceil(size / 64).  Inside a group the layout is that of
 // ivr_bin_index (search_binary.hip): W = 1, 2, 3, 4 or 8 words of 16 bytes per row, word w of the row in lane i at
 // data[g * W * 64 + w * 64 + i], pad bytes and pad rows zero, so bin_load_row loads one group of ONE list into a wave.  A row's
 // packed position is 64 g + i; ids[position] is its label, -1 on a pad row.  Positions stay below 2^32 (they are the low word of a key).
@@ -20,18 +20,14 @@
 // Equal scores rank the lower position first: the lower list, and inside a list the row added earlier.
 #include "ivr_common.h"
 #include "search_internal.h"
+#include "search_lists.h"
 #include "search_select.h"
-
-#include <cstdlib>
-#include <vector>
 
 namespace {
 
 constexpr int kIvfpqKsub = 256;              // centroids per slice (8-bit codes)
 constexpr int kIvfpqScanThreads = 512;       // the scan's workgroup: 8 waves share one LDS image of one query's table
 constexpr int kIvfpqProbeQueries = 4;        // queries (waves) per workgroup of the probe kernel
-// keys of the scratch a chunk of queries may fill: 2^25 slots of 8 bytes = 256 MiB (one query's stretch at least)
-constexpr int64_t kIvfpqChunkSlots = 1ll << 25;
 constexpr int kIvfpqMaxChunk = 16384;        // queries per chunk at most (the scan's grid is (shares, queries))
 // 64-row groups a scan workgroup takes per copy of a query's table.  Loading the table costs about as many LDS operations as scoring 4
 // groups; 8, 32, 128 and 512 were measured (tools/bench_ivfpq.py --ab; figures in DESIGN.md section 4, "inverted lists over PQ codes",
@@ -127,8 +123,6 @@ __global__ __launch_bounds__(64 * kIvfpqProbeQueries) void ivfpq_probe_kernel(co
     if (lane == 0) qgroups[q] = carry <= max_groups ? (int)carry : 0;
 }
 
-__device__ __forceinline__ uint32_t ivfpq_comp(const uint4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-
 // the score of the lane's row against one query's table t ([M][256], LDS): s0, then the entries in ascending m.  The 16 bytes of a
 // word, or the 4 of a component, are looked up together wherever M leaves them whole (the lookups do not depend on the additions,
 // and a whole word costs one wave-uniform branch)
@@ -140,7 +134,7 @@ __device__ __forceinline__ float ivfpq_score_row(const uint4 (&row)[W], const fl
         if (16 * w + 16 <= M) {
             float v[16];
 #pragma unroll
-            for (int b = 0; b < 16; ++b) v[b] = t[(16 * w + b) * kIvfpqKsub + ((ivfpq_comp(row[w], b >> 2) >> (8 * (b & 3))) & 255u)];
+            for (int b = 0; b < 16; ++b) v[b] = t[(16 * w + b) * kIvfpqKsub + ((ivr_comp(row[w], b >> 2) >> (8 * (b & 3))) & 255u)];
 #pragma unroll
             for (int b = 0; b < 16; ++b) s = s + v[b];
             continue;
@@ -148,7 +142,7 @@ __device__ __forceinline__ float ivfpq_score_row(const uint4 (&row)[W], const fl
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int m0 = 16 * w + 4 * c;
-            const uint32_t x = ivfpq_comp(row[w], c);
+            const uint32_t x = ivr_comp(row[w], c);
             if (m0 + 4 <= M) {
                 float v[4];
 #pragma unroll
@@ -237,33 +231,15 @@ struct SrcIvfpqSlots {     // the keys of query q: slots [q * qstride, q * qstri
     __device__ uint64_t key(int q, int64_t i) const { return i < (int64_t)qgroups[q] * 64 ? keys[(int64_t)q * qstride + i] : 0; }
 };
 
-long long ivfpq_env(const char *name, long long dflt) {
-    const char *e = std::getenv(name);
-    if (!e || !*e) return dflt;
-    char *end = nullptr;
-    const long long v = std::strtoll(e, &end, 10);
-    return end && *end == 0 && v > 0 ? v : dflt;
-}
-
 }  // namespace
 
-struct ivr_ivfpq {
-    ivr_ctx *ctx = nullptr;
-    int M = 0, w16 = 0, nlist = 0;
-    int64_t ntotal = 0, ngroups = 0;
-    std::mutex mu;
-    DevBuf<uint4> data;                  // [ngroups][w16][64]
-    DevBuf<int64_t> ids;                 // [ngroups * 64]: the label of every packed position, -1 on a pad row
-    DevBuf<int64_t> offs;                // [nlist + 1] list_off (rows in front of each list), then [nlist + 1] goff (groups in front of it)
-    std::vector<int64_t> by_size;        // HOST [nlist + 1]: groups of the p longest lists
-    int64_t chunk_slots = kIvfpqChunkSlots;      // IVR_IVFPQ_CHUNK_SLOTS: key slots of a chunk of queries (read at creation; tests)
+struct ivr_ivfpq : ListRows {          // data: [ngroups][w16][64]; by_size counts groups; chunk_slots: IVR_IVFPQ_CHUNK_SLOTS
+    int M = 0, w16 = 0;
     int64_t groups_per_wg = kIvfpqGroupsPerWg;   // IVR_IVFPQ_GROUPS_PER_WG: the scan's share size (A/B switch, read at creation)
     // search scratch of one chunk of queries (grow-only)
     DevBuf<uint64_t> keys;               // [chunk][qstride]
     DevBuf<int> gpre;                    // [chunk][p]
     DevBuf<int> qgroups;                 // [chunk]
-    const int64_t *list_off() const { return offs; }
-    const int64_t *goff() const { return (const int64_t *)offs + nlist + 1; }
 };
 
 extern "C" {
@@ -276,14 +252,10 @@ int ivr_ivfpq_create(ivr_ctx *ctx, int M, int nlist, ivr_ivfpq **out) {
     IVR_REQUIRE(nlist >= 1 && nlist < (1 << 30), "ivr_ivfpq_create: nlist=%d out of range", nlist);
     IVR_HIP(hipSetDevice(ctx->device));
     ivr_ivfpq *x = new ivr_ivfpq();
-    x->ctx = ctx;
     x->M = M;
     x->w16 = ivfpq_words(M);
-    x->nlist = nlist;
-    x->by_size.assign((size_t)nlist + 1, 0);
-    x->chunk_slots = ivfpq_env("IVR_IVFPQ_CHUNK_SLOTS", kIvfpqChunkSlots);
-    x->groups_per_wg = ivfpq_env("IVR_IVFPQ_GROUPS_PER_WG", kIvfpqGroupsPerWg);
-    const int rc = ivr_reserve({{&x->offs, (size_t)(nlist + 1) * 16}}, true);      // no rows: every offset 0
+    x->groups_per_wg = ivr_env_positive("IVR_IVFPQ_GROUPS_PER_WG", kIvfpqGroupsPerWg);
+    const int rc = x->init(ctx, nlist, "IVR_IVFPQ_CHUNK_SLOTS");
     if (rc != IVR_OK) {
         delete x;
         return rc;
@@ -300,70 +272,28 @@ int ivr_ivfpq_destroy(ivr_ivfpq *x) {
 int64_t ivr_ivfpq_ntotal(ivr_ivfpq *x) { return x ? x->ntotal : 0; }
 
 int ivr_ivfpq_set_lists(ivr_ivfpq *x, const uint8_t *codes, const int64_t *ids, const int64_t *list_off, int64_t n, ivr_stream stream) {
-    IVR_REQUIRE(x && list_off && ((codes && ids) || n == 0), "ivr_ivfpq_set_lists: NULL argument");
-    IVR_REQUIRE(n >= 0, "ivr_ivfpq_set_lists: n=%lld", (long long)n);
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int nlist = x->nlist;
-    std::vector<int64_t> host((size_t)(nlist + 1) * 2), sizes((size_t)nlist);
-    int64_t *goff = host.data() + nlist + 1;
-    IVR_REQUIRE(list_off[0] == 0 && list_off[nlist] == n, "ivr_ivfpq_set_lists: list_off must run from 0 to n=%lld", (long long)n);
-    goff[0] = 0;
-    for (int l = 0; l < nlist; ++l) {
-        IVR_REQUIRE(list_off[l + 1] >= list_off[l], "ivr_ivfpq_set_lists: list_off descends at list %d", l);
-        sizes[l] = ivr_ceil_div(list_off[l + 1] - list_off[l], 64);
-        goff[l + 1] = goff[l] + sizes[l];
-        host[l] = list_off[l];
-    }
-    host[nlist] = n;
-    const int64_t ngroups = goff[nlist];
-    IVR_REQUIRE(ngroups < (1ll << 26), "ivr_ivfpq_set_lists: %lld padded rows: packed positions must stay below 2^32",
-                (long long)(ngroups * 64));
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    IVR_HIP(hipDeviceSynchronize());             // a search in flight still reads the lists
-    // empty until the new content is in place, and empty for good when a step below fails: no rows, and no list long enough to probe
-    x->ntotal = x->ngroups = 0;
-    std::fill(x->by_size.begin(), x->by_size.end(), 0);
-    int rc = ivr_reserve({{&x->data, (size_t)ngroups * x->w16 * 64 * sizeof(uint4)}, {&x->ids, (size_t)ngroups * 64 * sizeof(int64_t)}});
-    hipError_t e = hipSuccess;
-    if (rc == IVR_OK) e = hipMemcpy((int64_t *)x->offs, host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (rc == IVR_OK && e == hipSuccess && ngroups > 0) {
+    IVR_REQUIRE(x, "ivr_ivfpq_set_lists: NULL argument");
+    return x->set_lists("ivr_ivfpq_set_lists", codes, ids, list_off, n, (int64_t)x->w16 * 64, false, [&](int64_t ngroups) {
         const int64_t threads = ngroups * x->w16 * 64;
         const int vec = x->M % 4 == 0 && ((uintptr_t)codes & 3) == 0;
         hipLaunchKernelGGL(ivfpq_pack_kernel, dim3((unsigned)ivr_ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream, codes, ids,
-                           x->list_off(), x->goff(), nlist, ngroups, x->M, x->w16, vec, (uint4 *)x->data, (int64_t *)x->ids);
-        e = hipGetLastError();
-    }
-    if (rc != IVR_OK || e != hipSuccess) {
-        (void)hipMemset((int64_t *)x->offs, 0, host.size() * sizeof(int64_t));       // every list empty again
-        if (rc != IVR_OK) return rc;
-        return ivr_fail(e == hipErrorOutOfMemory ? IVR_ERR_OOM : IVR_ERR_HIP, "ivr_ivfpq_set_lists: %s", hipGetErrorString(e));
-    }
-    std::sort(sizes.begin(), sizes.end(), [](int64_t a, int64_t b) { return a > b; });
-    for (int l = 0; l < nlist; ++l) x->by_size[l + 1] = x->by_size[l] + sizes[l];
-    x->ntotal = n;
-    x->ngroups = ngroups;
-    return IVR_OK;
+                           x->list_off(), x->goff(), x->nlist, ngroups, x->M, x->w16, vec, (uint4 *)x->data, (int64_t *)x->ids);
+    });
 }
 
 int ivr_ivfpq_reset(ivr_ivfpq *x) {
     IVR_REQUIRE(x, "ivr_ivfpq_reset: NULL index");
-    std::vector<int64_t> zero((size_t)x->nlist + 1, 0);
-    return ivr_ivfpq_set_lists(x, nullptr, nullptr, zero.data(), 0, nullptr);
+    return x->reset("ivr_ivfpq_set_lists");
 }
 
 int ivr_ivfpq_get_codes(ivr_ivfpq *x, int64_t start, int64_t n, uint8_t *codes, int64_t *ids, ivr_stream stream) {
-    IVR_REQUIRE(x && (codes || ids || n == 0), "ivr_ivfpq_get_codes: NULL argument");
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_REQUIRE(start >= 0 && n >= 0 && start + n <= x->ntotal, "ivr_ivfpq_get_codes: rows [%lld,%lld) outside [0,%lld)", (long long)start,
-                (long long)(start + n), (long long)x->ntotal);
-    if (n == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    const int64_t threads = n * ((x->M + 3) / 4);
-    hipLaunchKernelGGL(ivfpq_unpack_kernel, dim3((unsigned)ivr_ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const uint32_t *>((const uint4 *)x->data), (const int64_t *)x->ids, x->list_off(), x->goff(), x->nlist,
-                       start, n, x->M, x->w16, codes, ids);
-    IVR_LAUNCH_CHECK();
-    return IVR_OK;
+    IVR_REQUIRE(x, "ivr_ivfpq_get_codes: NULL argument");
+    return x->get_codes("ivr_ivfpq_get_codes", start, n, codes, ids, [&] {
+        const int64_t threads = n * ((x->M + 3) / 4);
+        hipLaunchKernelGGL(ivfpq_unpack_kernel, dim3((unsigned)ivr_ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const uint32_t *>((const uint4 *)x->data), (const int64_t *)x->ids, x->list_off(), x->goff(), x->nlist,
+                           start, n, x->M, x->w16, codes, ids);
+    });
 }
 
 int ivr_ivfpq_search(ivr_ivfpq *x, const float *T, const float *coarse, const int64_t *assign, int nq, int p, int k, float *D, int64_t *I,

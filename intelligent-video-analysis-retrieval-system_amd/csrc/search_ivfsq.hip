@@ -2,30 +2,26 @@
 // (ivr_ivfsq_set_lists / _get_codes) and the probed int8 MFMA top-k (ivr_ivfsq_search).  DESIGN.md section 4, "inverted lists over SQ
 // codes"; the definitions are the numpy functions ivfsq_pack_ref, ivfsq_unpack_ref and ivfsq_scan_ref of ivr_amd/ivfsq.py.
 //
-// Storage.  A code is d bytes (search_sq.hip).  The codes are ordered by list and every list is padded to whole 64-row groups, as in
-// search_ivfpq.hip: list l owns the groups [goff[l], goff[l + 1]), goff = the exclusive prefix of ceil(size / 64), and row i of the
-// list has the packed position 64 goff[l] + i.  Over the packed positions the layout is that of search_sq.hip: the stored byte is
+// Storage.  A code is d bytes (search_sq.hip).  The store is a ListRows (search_lists.h): the codes ordered by list, every list padded
+// to whole 64-row groups, list l owning the groups [goff[l], goff[l + 1]), goff = the exclusive prefix of ceil(size / 64), and row i
+// of the list at the packed position 64 goff[l] + i.  Over the packed positions the layout is that of search_sq.hip: the stored byte is
 // c' = code - 128, K is padded with zero bytes to ksteps = ceil(d / 64) steps, and position P sits in tile P / 16, whose piece s holds
 // bytes 64 s + 16 c .. + 15 of the row in lane (P & 15) + 16 c: one wave-wide 16-byte load is the A operand of one
 // v_mfma_i32_16x16x64_i8.  Pad rows and pad bytes are zero; ids[position] is the row's label, -1 on a pad row.  Positions stay below
 // 2^32 (they are the low word of a key).
 //
 // Search, per chunk of queries, all on the caller's stream and without a host round trip:
-//   sq_stage      once per call: t (int16) -> the two int8 halves, tiled per 16 queries (search_lists.h)
-//   probe tables  probe_slots / probe_count / probe_offsets / probe_fill of search_lists.h over the unpadded list sizes: the (query,
-//                 list) pairs grouped by list, the 16-query pair tiles, one key slot per probed row in the query's own stretch
+//   sq_stage      once per call: t (int16) -> the two int8 halves, tiled per 16 queries (ivr_launch_sq_stage, search_sq.hip)
+//   probe tables  ProbeTables::build (search_lists.hip) over the unpadded list sizes: the (query, list) pairs grouped by list, the
+//                 16-query pair tiles, one key slot per probed row in the query's own stretch
 //   ivfsq_scan    one workgroup per (pair tile, row split): both halves of its up to 16 queries gathered into LDS as B operands, its
 //                 waves walk the 16-row tiles of the list; acc = 128 acc_h + acc_l, D = ((float(acc) * scale) + bias) + coarse,
 //                 key (ordered D, ~position) into the row's slot
-//   select_topk   one workgroup per query over its stretch; labels through ids (OUT_DI_IDS)
+//   select_topk   ProbeTables::select: one workgroup per query over its stretch; labels through ids (OUT_DI_IDS)
 // Equal D rank the lower position first: the lower list, and inside a list the row added earlier.
 #include "ivr_common.h"
 #include "search_internal.h"
 #include "search_lists.h"
-#include "search_select.h"
-
-#include <cstdlib>
-#include <vector>
 
 namespace {
 
@@ -215,37 +211,13 @@ __global__ __launch_bounds__(kIvfsqThreads) void ivfsq_scan_kernel(IvfsqScan a) 
     }
 }
 
-long long ivfsq_env(const char *name, long long dflt) {
-    const char *e = std::getenv(name);
-    if (!e || !*e) return dflt;
-    char *end = nullptr;
-    const long long v = std::strtoll(e, &end, 10);
-    return end && *end == 0 && v > 0 ? v : dflt;
-}
-
 }  // namespace
 
-struct ivr_ivfsq {
-    ivr_ctx *ctx = nullptr;
-    int d = 0, ksteps = 0, nlist = 0;
-    int64_t ntotal = 0, ngroups = 0;
-    std::mutex mu;
-    DevBuf<uint4> data;                  // [ngroups * 4][ksteps][64]
-    DevBuf<int64_t> ids;                 // [ngroups * 64]: the label of every packed position, -1 on a pad row
-    DevBuf<int64_t> offs;                // [nlist + 1] list_off (rows in front of each list), then [nlist + 1] goff (groups in front of it)
-    std::vector<int64_t> by_size;        // HOST [nlist + 1]: rows of the p longest lists
-    int64_t chunk_slots = kIvfChunkSlots;        // IVR_IVFSQ_CHUNK_SLOTS: key slots of a chunk of queries (read at creation; tests)
+struct ivr_ivfsq : ListRows {          // data: [ngroups * 4][ksteps][64]; by_size counts rows; chunk_slots: IVR_IVFSQ_CHUNK_SLOTS
+    int d = 0, ksteps = 0;
     // search scratch (grow-only): the staged queries of a call, then the tables of one chunk of queries
     DevBuf<uint4> qh, ql;                // [query tiles][ksteps][64]
-    DevBuf<uint64_t> keys;               // [chunk][qstride]: (ordered D, ~position) of every probed row
-    DevBuf<int64_t> slot;                // [chunk][p]: first key slot of each probed list, -1 for a skipped entry
-    DevBuf<int64_t> qtotal;              // [chunk]: rows each query probes
-    DevBuf<int> count;                   // [nlist]: queries per list, then the fill cursors
-    DevBuf<int64_t> pt_off;              // [nlist + 1] pairs in front of each list, then [nlist + 1] 16-query pair tiles in front of it
-    DevBuf<int> pair_q;                  // [pairs of a chunk]: the (query, list) pairs grouped by list: the query of the chunk ...
-    DevBuf<int64_t> pair_slot;           // ... and its first key slot for that list
-    const int64_t *list_off() const { return offs; }
-    const int64_t *goff() const { return (const int64_t *)offs + nlist + 1; }
+    ProbeTables pt;                      // keys: (ordered D, ~position) of every probed row
     int64_t tile_words() const { return (int64_t)ksteps * 64; }
 };
 
@@ -257,17 +229,14 @@ int ivr_ivfsq_create(ivr_ctx *ctx, int d, int nlist, ivr_ivfsq **out) {
     IVR_REQUIRE(nlist >= 1 && nlist < (1 << 30), "ivr_ivfsq_create: nlist=%d out of range", nlist);
     IVR_HIP(hipSetDevice(ctx->device));
     ivr_ivfsq *x = new ivr_ivfsq();
-    x->ctx = ctx;
     x->d = d;
     x->ksteps = (d + 63) / 64;
-    x->nlist = nlist;
-    x->by_size.assign((size_t)nlist + 1, 0);
-    x->chunk_slots = ivfsq_env("IVR_IVFSQ_CHUNK_SLOTS", kIvfChunkSlots);
-    const int rc = ivr_reserve({{&x->offs, (size_t)(nlist + 1) * 16}}, true);      // no rows: every offset 0
+    const int rc = x->init(ctx, nlist, "IVR_IVFSQ_CHUNK_SLOTS");
     if (rc != IVR_OK) {
         delete x;
         return rc;
     }
+    x->pt.chunk_slots = x->chunk_slots;
     *out = x;
     return IVR_OK;
 }
@@ -280,70 +249,28 @@ int ivr_ivfsq_destroy(ivr_ivfsq *x) {
 int64_t ivr_ivfsq_ntotal(ivr_ivfsq *x) { return x ? x->ntotal : 0; }
 
 int ivr_ivfsq_set_lists(ivr_ivfsq *x, const uint8_t *codes, const int64_t *ids, const int64_t *list_off, int64_t n, ivr_stream stream) {
-    IVR_REQUIRE(x && list_off && ((codes && ids) || n == 0), "ivr_ivfsq_set_lists: NULL argument");
-    IVR_REQUIRE(n >= 0, "ivr_ivfsq_set_lists: n=%lld", (long long)n);
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int nlist = x->nlist;
-    std::vector<int64_t> host((size_t)(nlist + 1) * 2), sizes((size_t)nlist);
-    int64_t *goff = host.data() + nlist + 1;
-    IVR_REQUIRE(list_off[0] == 0 && list_off[nlist] == n, "ivr_ivfsq_set_lists: list_off must run from 0 to n=%lld", (long long)n);
-    goff[0] = 0;
-    for (int l = 0; l < nlist; ++l) {
-        IVR_REQUIRE(list_off[l + 1] >= list_off[l], "ivr_ivfsq_set_lists: list_off descends at list %d", l);
-        sizes[l] = list_off[l + 1] - list_off[l];
-        goff[l + 1] = goff[l] + ivr_ceil_div(sizes[l], 64);
-        host[l] = list_off[l];
-    }
-    host[nlist] = n;
-    const int64_t ngroups = goff[nlist];
-    IVR_REQUIRE(ngroups < (1ll << 26), "ivr_ivfsq_set_lists: %lld padded rows: packed positions must stay below 2^32",
-                (long long)(ngroups * 64));
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    IVR_HIP(hipDeviceSynchronize());             // a search in flight still reads the lists
-    // empty until the new content is in place, and empty for good when a step below fails: no rows, and no list long enough to probe
-    x->ntotal = x->ngroups = 0;
-    std::fill(x->by_size.begin(), x->by_size.end(), 0);
-    const int64_t nwords = ngroups * 4 * x->tile_words();
-    int rc = ivr_reserve({{&x->data, (size_t)nwords * sizeof(uint4)}, {&x->ids, (size_t)ngroups * 64 * sizeof(int64_t)}});
-    hipError_t e = hipSuccess;
-    if (rc == IVR_OK) e = hipMemcpy((int64_t *)x->offs, host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (rc == IVR_OK && e == hipSuccess && ngroups > 0) {
+    IVR_REQUIRE(x, "ivr_ivfsq_set_lists: NULL argument");
+    return x->set_lists("ivr_ivfsq_set_lists", codes, ids, list_off, n, 4 * x->tile_words(), true, [&](int64_t ngroups) {
+        const int64_t nwords = ngroups * 4 * x->tile_words();
         const int vec = x->d % 16 == 0 && ((uintptr_t)codes & 15) == 0;
         hipLaunchKernelGGL(ivfsq_pack_kernel, dim3((unsigned)ivr_ceil_div(nwords, 256)), dim3(256), 0, (hipStream_t)stream, codes, ids,
-                           x->list_off(), x->goff(), nlist, nwords, x->d, x->ksteps, vec, (uint4 *)x->data, (int64_t *)x->ids);
-        e = hipGetLastError();
-    }
-    if (rc != IVR_OK || e != hipSuccess) {
-        (void)hipMemset((int64_t *)x->offs, 0, host.size() * sizeof(int64_t));       // every list empty again
-        if (rc != IVR_OK) return rc;
-        return ivr_fail(e == hipErrorOutOfMemory ? IVR_ERR_OOM : IVR_ERR_HIP, "ivr_ivfsq_set_lists: %s", hipGetErrorString(e));
-    }
-    std::sort(sizes.begin(), sizes.end(), [](int64_t a, int64_t b) { return a > b; });
-    for (int l = 0; l < nlist; ++l) x->by_size[l + 1] = x->by_size[l] + sizes[l];
-    x->ntotal = n;
-    x->ngroups = ngroups;
-    return IVR_OK;
+                           x->list_off(), x->goff(), x->nlist, nwords, x->d, x->ksteps, vec, (uint4 *)x->data, (int64_t *)x->ids);
+    });
 }
 
 int ivr_ivfsq_reset(ivr_ivfsq *x) {
     IVR_REQUIRE(x, "ivr_ivfsq_reset: NULL index");
-    std::vector<int64_t> zero((size_t)x->nlist + 1, 0);
-    return ivr_ivfsq_set_lists(x, nullptr, nullptr, zero.data(), 0, nullptr);
+    return x->reset("ivr_ivfsq_set_lists");
 }
 
 int ivr_ivfsq_get_codes(ivr_ivfsq *x, int64_t start, int64_t n, uint8_t *codes, int64_t *ids, ivr_stream stream) {
-    IVR_REQUIRE(x && (codes || ids || n == 0), "ivr_ivfsq_get_codes: NULL argument");
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_REQUIRE(start >= 0 && n >= 0 && start + n <= x->ntotal, "ivr_ivfsq_get_codes: rows [%lld,%lld) outside [0,%lld)", (long long)start,
-                (long long)(start + n), (long long)x->ntotal);
-    if (n == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    const int64_t threads = n * ((x->d + 15) / 16);
-    hipLaunchKernelGGL(ivfsq_unpack_kernel, dim3((unsigned)ivr_ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)x->data, (const int64_t *)x->ids, x->list_off(), x->goff(), x->nlist, start, n, x->d, x->ksteps, codes,
-                       ids);
-    IVR_LAUNCH_CHECK();
-    return IVR_OK;
+    IVR_REQUIRE(x, "ivr_ivfsq_get_codes: NULL argument");
+    return x->get_codes("ivr_ivfsq_get_codes", start, n, codes, ids, [&] {
+        const int64_t threads = n * ((x->d + 15) / 16);
+        hipLaunchKernelGGL(ivfsq_unpack_kernel, dim3((unsigned)ivr_ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const uint4 *)x->data, (const int64_t *)x->ids, x->list_off(), x->goff(), x->nlist, start, n, x->d, x->ksteps, codes,
+                           ids);
+    });
 }
 
 int ivr_ivfsq_search(ivr_ivfsq *x, const int16_t *t, const float *scale, const float *bias, const float *coarse, const int64_t *assign, int nq,
@@ -357,58 +284,43 @@ int ivr_ivfsq_search(ivr_ivfsq *x, const int16_t *t, const float *scale, const f
     const int nlist = x->nlist;
     // what one query may probe: the rows of its p longest lists
     const int64_t qstride = x->by_size[(size_t)std::min<int64_t>(p, nlist)];
-    // queries per chunk: the scratch holds chunk_slots keys (one query's stretch at least), the pair tables kIvfChunkPairs pairs
-    const int chunk =
-        (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nq, x->chunk_slots / std::max<int64_t>(qstride, 1), kIvfChunkPairs / p}));
-    const int64_t nkeys = (int64_t)chunk * qstride, cpairs = (int64_t)chunk * p;
     const int64_t tw = x->tile_words(), qtiles = ivr_ceil_div(nq, 16);
+    ProbeTables &pt = x->pt;
+    int chunk;
+    int64_t nkeys;
     int rc = ivr_reserve({{&x->qh, (size_t)(qtiles * tw) * sizeof(uint4)}, {&x->ql, (size_t)(qtiles * tw) * sizeof(uint4)}});
-    if (rc == IVR_OK)
-        rc = ivr_reserve({{&x->keys, (size_t)std::max<int64_t>(nkeys, 1) * 8}, {&x->slot, (size_t)cpairs * 8}, {&x->qtotal, (size_t)chunk * 8},
-                          {&x->pair_q, (size_t)cpairs * 4}, {&x->pair_slot, (size_t)cpairs * 8}});
-    if (rc == IVR_OK) rc = ivr_reserve({{&x->count, (size_t)nlist * 4}, {&x->pt_off, (size_t)(nlist + 1) * 16}}, true);
+    if (rc == IVR_OK) rc = pt.plan(nq, p, qstride, nlist, &chunk, &nkeys);
     if (rc != IVR_OK) return rc;
     const size_t lds = (size_t)2 * tw * sizeof(uint4);               // 2 KiB per K step: 32 KiB at d = 1024
     rc = ivr_func_max_lds(reinterpret_cast<const void *>(ivfsq_scan_kernel), (int)lds);
     if (rc != IVR_OK) return rc;
     {
         IvrProf prof("ivfsq_stage", s, (double)nq * x->d * 2, true);
-        hipLaunchKernelGGL(sq_stage_kernel, dim3((unsigned)ivr_ceil_div(qtiles * tw, 256)), dim3(256), 0, s, t, nq, x->d, x->ksteps, qtiles * tw,
-                           (uint4 *)x->qh, (uint4 *)x->ql);
+        ivr_launch_sq_stage(t, nq, x->d, x->ksteps, qtiles, x->qh, x->ql, s);
         IVR_LAUNCH_CHECK();
     }
     // row splits of a list: 256 rows each, for a list as long as everything one query may probe; at most 64, longer lists loop
     const unsigned ysplit = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ivr_ceil_div(qstride, 16 * kIvfsqSplitTiles)));
-    int64_t *pair_off = x->pt_off, *tile_off = pair_off + nlist + 1;
     for (int q0 = 0; q0 < nq; q0 += chunk) {
         const int nqc = std::min(chunk, nq - q0);
         const int64_t npairs = (int64_t)nqc * p;
         const int64_t *a = assign + (int64_t)q0 * p;
         {
             IvrProf prof("ivfsq_probe_tables", s, (double)npairs * 48, true);
-            IVR_HIP(hipMemsetAsync((int *)x->count, 0, (size_t)nlist * 4, s));
-            hipLaunchKernelGGL(probe_slots_kernel, dim3((unsigned)ivr_ceil_div(nqc, 4)), dim3(256), 0, s, a, p, nqc, x->list_off(), nlist, x->ntotal,
-                               qstride, (int64_t *)x->slot, (int64_t *)x->qtotal);
-            hipLaunchKernelGGL(probe_count_kernel, dim3((unsigned)ivr_ceil_div(npairs, 256)), dim3(256), 0, s, a, (const int64_t *)x->slot, npairs,
-                               (int *)x->count);
-            hipLaunchKernelGGL(probe_offsets_kernel, dim3(1), dim3(256), 0, s, (int *)x->count, nlist, pair_off, tile_off);
-            hipLaunchKernelGGL(probe_fill_kernel, dim3((unsigned)ivr_ceil_div(npairs, 256)), dim3(256), 0, s, a, (const int64_t *)x->slot, p, npairs,
-                               (int *)x->count, pair_off, (int *)x->pair_q, (int64_t *)x->pair_slot);
+            rc = pt.build(a, p, nqc, x->list_off(), nlist, x->ntotal, qstride, s);
+            if (rc != IVR_OK) return rc;
             IVR_LAUNCH_CHECK();
         }
         if (x->ntotal > 0 && qstride > 0) {
-            // pair tiles of the chunk: every probed list has one partly filled tile at most
-            const int64_t tiles = std::min<int64_t>(nlist, npairs) + npairs / 16;
             const IvfsqScan sc{x->data, x->qh, x->ql, scale + q0, bias + q0, coarse ? coarse + (int64_t)q0 * p : nullptr, a, x->ksteps, nlist, p,
-                               q0, nqc, x->ntotal, x->ngroups, x->list_off(), x->goff(), pair_off, tile_off, x->pair_q, x->pair_slot, x->keys,
-                               nkeys};
+                               q0, nqc, x->ntotal, x->ngroups, x->list_off(), x->goff(), pt.pair_off(), pt.tile_off(nlist), pt.pair_q, pt.pair_slot,
+                               pt.keys, nkeys};
             IvrProf prof("ivfsq_list_scan", s, 0.0);
-            hipLaunchKernelGGL(ivfsq_scan_kernel, dim3((unsigned)tiles, ysplit), dim3(kIvfsqThreads), lds, s, sc);
+            hipLaunchKernelGGL(ivfsq_scan_kernel, dim3((unsigned)ProbeTables::tiles(nlist, npairs), ysplit), dim3(kIvfsqThreads), lds, s, sc);
             IVR_LAUNCH_CHECK();
         }
         IvrProf prof("ivfsq_select", s, (double)nqc * qstride * 8, true);
-        const SrcSlots src{x->keys, x->qtotal, qstride, qstride};
-        launch_select<OUT_DI_IDS>(src, nqc, k, SelectOut::to_rows(D + (int64_t)q0 * k, I + (int64_t)q0 * k, 0, x->ids), s);
+        pt.select(nqc, k, qstride, D + (int64_t)q0 * k, I + (int64_t)q0 * k, x->ids, s);
         IVR_LAUNCH_CHECK();
     }
     return IVR_OK;

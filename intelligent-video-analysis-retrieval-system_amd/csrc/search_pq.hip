@@ -54,7 +54,6 @@ struct SrcPqKeys {     // the re-scored rows of the selected groups
 };
 
 // component c of a code word (c is a constant wherever the loops around a call are unrolled)
-__device__ __forceinline__ uint32_t pq_comp(const uint4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 
 // s[r] = the score of row[r] against one query's table t ([M][256], LDS or global): additions in ascending m for every row, the R
 // rows side by side.  Four bytes of a code are looked up together wherever M leaves them whole
@@ -71,7 +70,7 @@ __device__ __forceinline__ void pq_score_rows(const uint4 (&row)[R][W], const fl
                 float v[R][4];
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    const uint32_t x = pq_comp(row[r][w], c);
+                    const uint32_t x = ivr_comp(row[r][w], c);
 #pragma unroll
                     for (int b = 0; b < 4; ++b) v[r][b] = t[(m0 + b) * kPqKsub + ((x >> (8 * b)) & 255u)];
                 }
@@ -86,7 +85,7 @@ __device__ __forceinline__ void pq_score_rows(const uint4 (&row)[R][W], const fl
                     if (m0 + b < M) {
 #pragma unroll
                         for (int r = 0; r < R; ++r) {
-                            const uint32_t x = pq_comp(row[r][w], c);
+                            const uint32_t x = ivr_comp(row[r][w], c);
                             const float v = t[(m0 + b) * kPqKsub + ((x >> (8 * b)) & 255u)];
                             s[r] = m0 + b == 0 ? v : s[r] + v;
                         }

@@ -74,7 +74,6 @@ struct SrcPqfsKeys {    // the re-scored rows of the selected groups
     __device__ uint64_t key(int q, int64_t i) const { return keys[(int64_t)q * n + i]; }
 };
 
-__device__ __forceinline__ uint32_t pqfs_comp(const uint4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 __device__ __forceinline__ uint32_t pqfs_pk_add(uint32_t a, uint32_t b) {
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(pqfs_u16x2, a) + __builtin_bit_cast(pqfs_u16x2, b));
 }
@@ -107,7 +106,7 @@ __device__ __forceinline__ uint32_t pqfs_wave_pk_max(uint32_t v) {
 __device__ __forceinline__ void pqfs_selectors(const uint4 &cw, uint32_t (&sel)[8], uint32_t (&hm)[8]) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        const uint32_t x = pqfs_comp(cw, c);
+        const uint32_t x = ivr_comp(cw, c);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const uint32_t n = (h ? x >> 4 : x) & 0x0f0f0f0fu;

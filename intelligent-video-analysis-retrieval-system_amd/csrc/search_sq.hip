@@ -21,8 +21,8 @@
 //               (ivr_ord2f, a bijection of 32-bit patterns)
 //   sq_finish   D = float(acc) * scale + bias from that word: one conversion, one multiplication, one addition
 // Scratch (grow-only, on the index object): both halves of the staged queries and, in its GroupTopK, 4 bytes per (query, group) and
-// 520 per (query, selected group) of a chunk.  sq_stage_kernel, sq_frag, sq_combine and SQ_NO_CONTRACT are in search_lists.h:
-// search_ivfsq.hip stages its queries and combines its halves the same way.
+// 520 per (query, selected group) of a chunk.  sq_frag, sq_combine and SQ_NO_CONTRACT are in search_lists.h and sq_stage_kernel is
+// behind ivr_launch_sq_stage: search_ivfsq.hip stages its queries and combines its halves the same way.
 #include "ivr_common.h"
 #include "search_internal.h"
 #include "search_lists.h"
@@ -46,6 +46,33 @@ constexpr int kSqMaxD = 1024;                // 16256 * 128 * d fits int32 up to
 constexpr float kSqTMax = 16256.f;           // 127 * 128: the largest |t|
 constexpr int kSqQT = 2;                     // 16-query tiles per index pass: 32 queries
 constexpr int kSqThreads = 256;              // the scan's workgroup: 4 waves share one LDS image of the queries
+
+// t int16 [nq][d] -> both halves, tiled: one thread per (query tile, K step, lane); zeros past d and past nq.  |t| is clamped to
+// 16256 so that h stays an int8 whatever the caller supplies
+__global__ __launch_bounds__(256) void sq_stage_kernel(const int16_t *__restrict__ t, int nq, int d, int ksteps, int64_t nwords,
+                                                       uint4 *__restrict__ qh, uint4 *__restrict__ ql) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= nwords) return;
+    const int lane = (int)(w & 63);
+    const int s = (int)((w >> 6) % ksteps);
+    const int64_t q = ((w >> 6) / ksteps) * 16 + (lane & 15);
+    const int k0 = 64 * s + 16 * (lane >> 4);
+    uint32_t h[4] = {0u, 0u, 0u, 0u}, l[4] = {0u, 0u, 0u, 0u};
+    if (q < nq) {
+        const int16_t *tp = t + q * d;
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+            if (k0 + b < d) {
+                const int v = min(max((int)tp[k0 + b], -16256), 16256);
+                const int lo = ((v + 64) & 127) - 64, hi = (v - lo) >> 7;
+                h[b >> 2] |= (uint32_t)(hi & 255) << (8 * (b & 3));
+                l[b >> 2] |= (uint32_t)(lo & 255) << (8 * (b & 3));
+            }
+        }
+    }
+    qh[w] = uint4{h[0], h[1], h[2], h[3]};
+    ql[w] = uint4{l[0], l[1], l[2], l[3]};
+}
 
 // the keys of the two selections: instantiations of select_topk_kernel of this file's own (search_select.h)
 struct SrcSqGroups {   // the group maxima of query q
@@ -278,6 +305,11 @@ __global__ __launch_bounds__(256) void sq_query_kernel(const float *__restrict__
 
 }  // namespace
 
+void ivr_launch_sq_stage(const int16_t *t, int nq, int d, int ksteps, int64_t qtiles, uint4 *qh, uint4 *ql, hipStream_t s) {
+    const int64_t nwords = qtiles * ksteps * 64;
+    hipLaunchKernelGGL(sq_stage_kernel, dim3((unsigned)ivr_ceil_div(nwords, 256)), dim3(256), 0, s, t, nq, d, ksteps, nwords, qh, ql);
+}
+
 extern "C" {
 
 int ivr_sq_encode(ivr_ctx *ctx, const float *x, int64_t n, int d, const float *vmin, const float *vdiff, uint8_t *codes, ivr_stream stream) {
@@ -401,8 +433,7 @@ int ivr_sq_index_search(ivr_sq_index *x, const int16_t *t, const float *scale, c
     if (rc != IVR_OK) return rc;
     {
         IvrProf prof("sq_stage", s, (double)nq * x->d * 2, true);
-        hipLaunchKernelGGL(sq_stage_kernel, dim3((unsigned)ivr_ceil_div(qtiles * tw, 256)), dim3(256), 0, s, t, nq, x->d, x->ksteps, qtiles * tw,
-                           (uint4 *)x->qh, (uint4 *)x->ql);
+        ivr_launch_sq_stage(t, nq, x->d, x->ksteps, qtiles, x->qh, x->ql, s);
     }
     // workgroups per CU that the LDS lets be resident, at most 4 (16 waves); each walks the groups with 4 waves
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / (int64_t)lds));

@@ -6,6 +6,7 @@ the offsets `_off_host` / `_off` (written by `_set_offsets` only), the checks of
 subclass supplies `ntotal`, `is_trained`, `train`, its row store (named in `_PARTS`) with `add_with_ids` (around `_new_ids`,
 `_assign_device` and `_regroup`), `_ids_device(start, n)`, its scan and `reset`.  `CodedInvertedFileIndex` below is that subclass for the two indexes that keep codes
 in a list store of the library: everything but the coder, the query form and the scan call.
+`_check_off` and `ivfpq_positions_ref` state the packed position of a row in that store (lists padded to whole 64-row groups).
 """
 import numpy as np
 import torch
@@ -27,6 +28,23 @@ def list_offsets(lists, nlist):
     off = np.zeros(nlist + 1, np.int64)
     np.cumsum(np.bincount(lists, minlength=nlist), out=off[1:])
     return off
+
+
+def _check_off(list_off, n):
+    off = np.asarray(list_off, np.int64).reshape(-1)
+    if len(off) < 2 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+        raise ValueError(f"list_off must ascend from 0 to n={n}")
+    return off
+
+
+def ivfpq_positions_ref(list_off):
+    """The packed position of every list-ordered row: list l starts at group goff[l] = sum over the lists below it of
+    ceil(size / 64), and its row i sits at 64 goff[l] + i.  -> (pos int64 [n], goff int64 [nlist + 1])."""
+    off = np.asarray(list_off, np.int64).reshape(-1)
+    sizes = np.diff(off)
+    goff = np.concatenate([[0], np.cumsum((sizes + 63) // 64)]).astype(np.int64)
+    pos = np.concatenate([64 * goff[l] + np.arange(sizes[l], dtype=np.int64) for l in range(len(sizes))] + [np.zeros(0, np.int64)])
+    return pos, goff
 
 
 def _nearest(index, t):

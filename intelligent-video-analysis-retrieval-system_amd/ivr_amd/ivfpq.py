@@ -20,7 +20,7 @@ import torch
 
 from . import _ffi, _staging
 from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
-from ._ivf import CodedInvertedFileIndex, check_quantizer
+from ._ivf import CodedInvertedFileIndex, _check_off, check_quantizer, ivfpq_positions_ref
 from ._staging import dev_f32 as _dev_f32
 from .index import FlatIPIndex
 from .pq import KSUB, PQIndex
@@ -31,23 +31,6 @@ def _words(M):
     """16-byte words per stored row: 1, 2, 3, 4 or 8 (the word counts of the binary store)."""
     w = (int(M) + 15) // 16
     return w if w <= 4 else 8
-
-
-def _check_off(list_off, n):
-    off = np.asarray(list_off, np.int64).reshape(-1)
-    if len(off) < 2 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
-        raise ValueError(f"list_off must ascend from 0 to n={n}")
-    return off
-
-
-def ivfpq_positions_ref(list_off):
-    """The packed position of every list-ordered row: list l starts at group goff[l] = sum over the lists below it of
-    ceil(size / 64), and its row i sits at 64 goff[l] + i.  -> (pos int64 [n], goff int64 [nlist + 1])."""
-    off = np.asarray(list_off, np.int64).reshape(-1)
-    sizes = np.diff(off)
-    goff = np.concatenate([[0], np.cumsum((sizes + 63) // 64)]).astype(np.int64)
-    pos = np.concatenate([64 * goff[l] + np.arange(sizes[l], dtype=np.int64) for l in range(len(sizes))] + [np.zeros(0, np.int64)])
-    return pos, goff
 
 
 def ivfpq_pack_ref(codes, list_off):

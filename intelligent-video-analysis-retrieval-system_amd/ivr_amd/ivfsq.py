@@ -23,10 +23,9 @@ import torch
 
 from . import _ffi, _staging
 from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
-from ._ivf import CodedInvertedFileIndex, check_quantizer
+from ._ivf import CodedInvertedFileIndex, _check_off, check_quantizer, ivfpq_positions_ref
 from ._staging import dev_f32 as _dev_f32
 from .index import FlatIPIndex
-from .ivfpq import _check_off, ivfpq_positions_ref
 from .sq import QT_8bit, T_MAX, SQIndex, _dev_i16, sq_score_bound
 
 _F = np.float32

@@ -153,6 +153,47 @@ def test_list_scan_matches_filtered_flat_search(d, nq, k):
     _check_scan(S, S.ivf, S.flat, S.lists, S.labels, nq, k)
 
 
+def test_several_chunks_give_the_bits_of_one(monkeypatch):
+    """A chunk of queries is bounded by its key slots (IVR_IVF_CHUNK_SLOTS, read when the storage of the index is made).  A query
+    that names three lists holds at most the rows of the three longest, so one slot more than three such stretches is chunks of 3
+    queries: 40 queries are 13 chunks and a ragged last one, every chunk but the first starting inside a 16-query tile of the staged
+    queries.  The chunked call equals the unchunked one, and both the filtered flat search."""
+    from ivr_amd.index import FlatIPIndex
+    from ivr_amd.ivf import IndexIVFFlat
+    d, nq, p = 24, 40, 3
+    sizes = [5, 64, 0, 130, 17, 300, 1, 33]
+    nlist, n = len(sizes), sum(sizes)
+    rng = np.random.default_rng(7024)
+    lists = np.repeat(np.arange(nlist), sizes)[rng.permutation(n)]
+    X = _unit64(np.eye(nlist, d)[lists] + 0.3 * rng.standard_normal((n, d)) / np.sqrt(d)).astype(np.float32)
+    assert np.array_equal(X[:, :nlist].argmax(1), lists)
+    labels = (BIG + rng.permutation(10 * n)[:n]).astype(np.int64)
+    Q = _unit64(rng.standard_normal((nq, d))).astype(np.float32)
+    i = np.arange(nq)
+    assign = np.stack([(5 * i) % nlist, (3 * i + 1) % nlist, np.where(i % 7 == 0, -1, 5)], 1).astype(np.int64)
+    flat = FlatIPIndex(d)
+    flat.add_with_ids(X, labels)
+
+    def scan():
+        ivf = IndexIVFFlat(_axis_quantizer(d, nlist), d, nlist)
+        ivf.train(X)
+        ivf.add_with_ids(X, labels)
+        assert ivf.list_sizes().tolist() == sizes
+        out = [ivf.search_preassigned(Q, k, assign) for k in (10, 500)]
+        ivf.close()
+        return out
+
+    whole = scan()
+    monkeypatch.setenv("IVR_IVF_CHUNK_SLOTS", str(3 * sum(sorted(sizes)[-p:]) + 1))
+    chunked = scan()
+    for k, (D, I), (Dw, Iw) in zip((10, 500), chunked, whole):
+        assert np.array_equal(_bits(D), _bits(Dw)) and np.array_equal(I, Iw), k
+        De, Ie = _expected(flat, lists, labels, Q, k, assign)
+        _assert_same(D, I, De, Ie, f"chunked k={k}")
+        _assert_same(Dw, Iw, De, Ie, f"whole k={k}")
+    flat.close()
+
+
 # -- 2. search = coarse search + list scan --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("d", [64, 768])
 def test_search_is_coarse_search_plus_list_scan(d):
