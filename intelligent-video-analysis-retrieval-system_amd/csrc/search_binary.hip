@@ -16,6 +16,7 @@
 //               slot is a function of the data alone (no cursor atomics), so the same rows are chosen on every run
 //   order       bitonic sort of the k (distance, row) keys of a query in one workgroup; D / I written
 // Scratch: nq W 16 bytes of staged queries, and per chunk (nbits + 1) 4 + (rows / 64) 8 + k 8 bytes per query.
+#include "search_coded.h"
 #include "search_internal.h"
 
 #include <climits>
@@ -25,7 +26,7 @@ namespace {
 constexpr uint64_t kBinEmpty = ~0ull;    // key of an unused result slot
 constexpr int64_t kSignEncodeSmall = 4096;   // ivr_sign_encode: up to this many rows take the latency-oriented instantiation
 
-// struct ivr_bin_index, bin_load_row and bin_with_words: search_internal.h (search_pq.hip scans the same storage)
+// struct ivr_bin_index: search_coded.h; bin_load_row and bin_with_words: search_internal.h (search_pq.hip scans the same storage)
 
 int bin_words(int code_size) {
     const int w = (code_size + 15) / 16;
@@ -392,37 +393,6 @@ void bin_launch_pack(const ivr_bin_index *x, const uint8_t *src, uint4 *dst, int
 
 }  // namespace
 
-// ---- what the coded indexes share (search_internal.h) -----------------------------------------------------------------------------
-int CodeRows::grow(int64_t rows) {
-    rows = ivr_round_up(std::max<int64_t>(rows, granule), granule);
-    uint4 *nd = nullptr;
-    IVR_HIP(hipMalloc(&nd, bytes(rows)));
-    IVR_HIP(hipMemset(nd, 0, bytes(rows)));
-    if (data) {
-        if (ntotal > 0) IVR_HIP(hipMemcpy(nd, data, bytes(ntotal), hipMemcpyDeviceToDevice));
-        IVR_HIP(hipFree(data));
-    }
-    data = nd;
-    cap = rows;
-    return IVR_OK;
-}
-
-int CodeRows::reserve_for_add(int64_t n, const char *what) {
-    if (ntotal + n <= cap) return IVR_OK;
-    IVR_REQUIRE(ntotal + n < (1ll << 31) - granule, "%s: index would exceed 2^31 rows", what);
-    IVR_HIP(hipDeviceSynchronize());
-    return grow(std::max<int64_t>(ntotal + n, cap + cap / 2));
-}
-
-int GroupTopK::plan(int nq, int k, int64_t ngroups, int pass, int64_t &mstride, int &ksel, int &qc) {
-    mstride = ivr_round_up(ngroups, 64);
-    ksel = (int)std::min<int64_t>(k, ngroups);
-    const int64_t fit = std::min<int64_t>({(int64_t)kMaxChunk, kChunkKeys / ((int64_t)ksel * 64), kChunkKeys / mstride});
-    qc = (int)std::min<int64_t>(nq, std::max<int64_t>(pass, fit / pass * pass));
-    return ivr_reserve({{&gmax, (size_t)qc * mstride * 4}, {&sel, (size_t)qc * ksel * sizeof(uint32_t)},
-                        {&keys, (size_t)qc * ksel * 64 * sizeof(uint64_t)}});
-}
-
 extern "C" {
 
 int ivr_bin_index_block_rows(void) { return kBinBlockRows; }
@@ -456,41 +426,23 @@ int ivr_bin_index_destroy(ivr_bin_index *x) {
 
 int ivr_bin_index_reset(ivr_bin_index *x) {
     IVR_REQUIRE(x, "ivr_bin_index_reset: NULL index");
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    IVR_HIP(hipDeviceSynchronize());             // a search in flight still reads the rows
-    IVR_HIP(hipMemset(x->data, 0, x->bytes(x->cap)));
-    x->ntotal = 0;
-    return IVR_OK;
+    return x->reset(true);                       // the distance loop reads the pad bits and the scans whole groups: all zero again
 }
 
 int64_t ivr_bin_index_ntotal(ivr_bin_index *x) { return x ? x->ntotal : 0; }
 
 int ivr_bin_index_add(ivr_bin_index *x, const uint8_t *codes, int64_t n, ivr_stream stream) {
-    IVR_REQUIRE(x && (codes || n == 0), "ivr_bin_index_add: NULL argument");
-    IVR_REQUIRE(n >= 0, "ivr_bin_index_add: n=%lld", (long long)n);
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (n == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    if (int rc = x->reserve_for_add(n, "ivr_bin_index_add")) return rc;
-    bin_launch_pack(x, codes, x->data, x->ntotal, n, 1, (hipStream_t)stream);
-    IVR_LAUNCH_CHECK();
-    x->ntotal += n;
-    return IVR_OK;
+    IVR_REQUIRE(x, "ivr_bin_index_add: NULL argument");
+    return x->add("ivr_bin_index_add", codes, n, [&] { bin_launch_pack(x, codes, x->data, x->ntotal, n, 1, (hipStream_t)stream); });
 }
 
 int ivr_bin_index_get_codes(ivr_bin_index *x, int64_t start, int64_t n, uint8_t *out, ivr_stream stream) {
-    IVR_REQUIRE(x && (out || n == 0), "ivr_bin_index_get_codes: NULL argument");
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_REQUIRE(start >= 0 && n >= 0 && start + n <= x->ntotal, "ivr_bin_index_get_codes: rows [%lld,%lld) outside [0,%lld)",
-                (long long)start, (long long)(start + n), (long long)x->ntotal);
-    if (n == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    const int64_t threads = n * ((x->code_size + 3) / 4);
-    hipLaunchKernelGGL(bin_unpack_kernel, dim3((unsigned)ivr_ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const uint32_t *>(x->data), start, n, x->code_size, x->w16, out);
-    IVR_LAUNCH_CHECK();
-    return IVR_OK;
+    IVR_REQUIRE(x, "ivr_bin_index_get_codes: NULL argument");
+    return x->get_codes("ivr_bin_index_get_codes", start, n, out, [&] {
+        const int64_t threads = n * ((x->code_size + 3) / 4);
+        hipLaunchKernelGGL(bin_unpack_kernel, dim3((unsigned)ivr_ceil_div(threads, 256)), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const uint32_t *>(x->data), start, n, x->code_size, x->w16, out);
+    });
 }
 
 int ivr_bin_index_search(ivr_bin_index *x, const uint8_t *qcodes, int nq, int k, int32_t *D, int64_t *I, ivr_stream stream) {

@@ -3,7 +3,8 @@
 // id table of an id-mapped index).  It holds what more
 // than one of them needs: the index object with the plan of a search, the view a search scans, the row mask of a filtered search, and
 // the launchers that are defined in one file and called from another.  search_rows.hip (gather / scatter of rows by position) uses it
-// too, and so do search_binary.hip, search_pq.hip and search_sq.hip for the coded-index structs at its end.  It also holds the device
+// too, and so do search_binary.hip, search_pq.hip and search_ivfpq.hip for the loaders of the binary-code layout at its end (the
+// coded-index structs themselves are in search_coded.h).  It also holds the device
 // helpers that every search file spells the same way: ivr_key, ivr_wave_incl_scan, ivr_last_le, ivr_comp and probe_valid, and
 // ProbeTables, the probe tables of the inverted-list scans (search_lists.hip).  Not part of the C ABI.
 #pragma once
@@ -352,56 +353,7 @@ void ivr_launch_sq_stage(const int16_t *t, int nq, int d, int ksteps, int64_t qt
 // search_scanq.hip
 int ivr_launch_scanq(ivr_ctx *ctx, const ScanQArgs &a, hipStream_t s, const RowMask *mask = nullptr);
 
-// ---- coded indexes: what ivr_bin_index (search_binary.hip, search_pq.hip) and ivr_sq_index (search_sq.hip) share ---------------
-// The growable row store of a coded index (defined in search_binary.hip): whatever the layout inside, 64 rows are group_words
-// 16-byte words.  Growing zero-fills the new block and copies the groups that hold rows.
-struct CodeRows {
-    ivr_ctx *ctx = nullptr;
-    int granule = 0;                     // rows the capacity is a multiple of (itself a multiple of 64)
-    int64_t group_words = 0;
-    int64_t cap = 0, ntotal = 0;
-    uint4 *data = nullptr;               // [cap / 64][group_words]
-    std::mutex mu;
-    ~CodeRows() { (void)hipFree(data); }
-    size_t bytes(int64_t rows) const { return (size_t)ivr_ceil_div(rows, 64) * group_words * sizeof(uint4); }
-    int grow(int64_t rows);              // a block of at least `rows` rows (one granule at least) that takes over the stored rows
-    // room for n more rows: when they do not fit, wait for the device (work in flight may still read the old block) and grow to
-    // max(ntotal + n, 1.5 cap).  what: the caller's name, for the message of an index that would exceed 2^31 rows
-    int reserve_for_add(int64_t n, const char *what);
-};
-
-// The workspace and the chunking of the two-level top-k of a coded scan (defined in search_binary.hip): per chunk of queries the
-// scan leaves the best score of every 64-row group in gmax, select_topk_kernel picks the best ksel groups into sel, their rows are
-// re-scored into keys and select_topk_kernel orders those.  Grow-only.
-struct GroupTopK {
-    static constexpr int kMaxChunk = 4096;               // queries per chunk at most
-    static constexpr int64_t kChunkKeys = 1ll << 25;     // keys and group maxima of a chunk (256 + 128 MiB), or one pass's if more
-    DevMem gmax;                         // [chunk][mstride] 4-byte entries (float or int32): best score of each 64-row group
-    DevBuf<uint32_t> sel;                // [chunk][ksel]: the selected groups, 0xFFFFFFFF = none
-    DevBuf<uint64_t> keys;               // [chunk][ksel * 64]: (ordered score, ~row) of the rows of the selected groups
-    // The plan of a search of nq queries for k rows over ngroups > 0 groups whose scan takes `pass` queries at a time: mstride =
-    // ngroups rounded up to 64, ksel = min(k, ngroups), qc = queries per chunk (whole passes, at least one); reserves one chunk
-    int plan(int nq, int k, int64_t ngroups, int pass, int64_t &mstride, int &ksel, int &qc);
-};
-
-// ---- binary codes (search_binary.hip) and the product-quantisation scan over the same storage (search_pq.hip) -----------------
-constexpr int kBinBlockRows = 256;       // rows per workgroup block: one row per lane, four 64-row groups (the store's granule)
-constexpr int kBinMaxChunk = 64;         // queries per chunk at most
-constexpr int kBinHistLds = 48 * 1024;   // LDS of the histogram pass: (nbits + 1) bins of 4 bytes per query of a chunk
-
-struct ivr_bin_index : CodeRows {        // data: [cap / 64][w16][64], group_words = 64 w16
-    int nbits = 0, code_size = 0, w16 = 0;
-    // search workspace (grow-only)
-    DevBuf<uint4> q;                     // [nq][w16] staged queries, row-major
-    DevBuf<uint32_t> hist;               // [chunk][nbits + 1]
-    DevBuf<uint32_t> thr;                // [chunk][4]: t, need, below
-    DevBuf<uint32_t> cnt;                // [2][chunk][groups]: rows below t / at t per 64-row group, then their exclusive prefix
-    DevBuf<uint64_t> cand;               // [chunk][k]: (distance << 32 | row) of the chosen rows, kBinEmpty elsewhere
-    GroupTopK pq;                        // product-quantisation scan (ivr_bin_index_search_pq, search_pq.hip): float maxima
-
-    int chunk() const { return std::max(1, std::min(kBinMaxChunk, kBinHistLds / (4 * (nbits + 1)))); }
-};
-
+// ---- the layout of binary codes (search_binary.hip), scanned by search_pq.hip and, per list, by search_ivfpq.hip too ---------------
 // The row of this lane: row 64 g + lane of the index layout
 template <int W>
 __device__ __forceinline__ void bin_load_row(const uint4 *__restrict__ data, int64_t g, uint4 (&row)[W]) {

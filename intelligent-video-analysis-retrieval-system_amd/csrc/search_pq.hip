@@ -22,8 +22,8 @@
 // as they come, which no layout of a table can change, and the scan is bound by them, not by the code stream.
 // Scratch (grow-only, the GroupTopK of the index object): 4 bytes per (query, group) and 520 per (query, selected group) of a chunk.
 #include "ivr_common.h"
+#include "search_coded.h"
 #include "search_internal.h"
-#include "search_select.h"
 
 #include <cfloat>
 
@@ -37,23 +37,6 @@ constexpr int kPqTableLds = 128 * 1024;      // LDS a workgroup spends on tables
 constexpr int kPqMaxGroupQ = 8;              // queries of a group at most (their scores are live at once)
 constexpr int kPqEncodeMaxReg = 64;          // widest slice the encoder keeps in registers and its codebook in LDS
 constexpr int kPqTabQ = 8;                   // queries per thread of the table builder
-
-// the keys of the two selections: instantiations of select_topk_kernel of this file's own (search_select.h)
-struct SrcPqGroups {   // the group maxima of query q
-    const float *gmax;
-    int64_t mstride;
-    int64_t n;
-    __device__ uint64_t key(int q, int64_t i) const {
-        return ivr_key(gmax[(int64_t)q * mstride + i], (uint32_t)i);
-    }
-};
-struct SrcPqKeys {     // the re-scored rows of the selected groups
-    const uint64_t *keys;
-    int64_t n;
-    __device__ uint64_t key(int q, int64_t i) const { return keys[(int64_t)q * n + i]; }
-};
-
-// component c of a code word (c is a constant wherever the loops around a call are unrolled)
 
 // s[r] = the score of row[r] against one query's table t ([M][256], LDS or global): additions in ascending m for every row, the R
 // rows side by side.  Four bytes of a code are looked up together wherever M leaves them whole
@@ -162,15 +145,6 @@ __global__ __launch_bounds__(256) void pq_keys_kernel(const uint4 *__restrict__ 
         if (r < ntotal) key = ivr_key(s[0], (uint32_t)r);
     }
     keys[p * 64 + lane] = key;
-}
-
-// every result slot unused: an empty index
-__global__ __launch_bounds__(256) void pq_absent_kernel(int64_t n, float *__restrict__ D, int64_t *__restrict__ I) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        D[i] = -FLT_MAX;
-        I[i] = -1;
-    }
 }
 
 // ---- encoder ----------------------------------------------------------------------------------------------------------------------
@@ -333,60 +307,42 @@ int ivr_bin_index_search_pq(ivr_bin_index *x, const float *T, int nq, int M, int
     IVR_HIP(hipSetDevice(x->ctx->device));
     hipStream_t s = (hipStream_t)stream;
     const int64_t ntotal = x->ntotal, ngroups = ivr_ceil_div(ntotal, 64);
-    if (ntotal == 0) {
-        const int64_t n = (int64_t)nq * k;
-        hipLaunchKernelGGL(pq_absent_kernel, dim3((unsigned)ivr_ceil_div(n, 256)), dim3(256), 0, s, n, D, I);
-        IVR_LAUNCH_CHECK();
-        return IVR_OK;
-    }
-    int64_t mstride;
-    int ksel, qc;
-    int rc = x->pq.plan(nq, k, ngroups, 1, mstride, ksel, qc);       // the scan takes any number of queries: a pass is one
+    if (ntotal == 0) return GroupTopK::absent(nq, k, D, I, s);
+    // never: M <= 128 is 8 words at most; the 16-word scan is not built
+    if (x->w16 > 8) return ivr_fail(IVR_ERR_INVALID, "ivr_bin_index_search_pq: %d words per row", x->w16);
+    GroupTopK &t = x->pq;
+    int rc = t.plan(nq, k, ngroups, 1);          // the scan takes any number of queries: a pass is one
     if (rc != IVR_OK) return rc;
-    float *gmax = static_cast<float *>(x->pq.gmax.ptr);
     const int tab = M * kPqKsub;
     const int qg_max = std::max(1, std::min(kPqMaxGroupQ, kPqTableLds / (tab * (int)sizeof(float))));
-    bin_with_words(x->w16, [&](auto w) {
-        constexpr int W = decltype(w)::value;
-        if (W > 8) {                         // never: M <= 128 is 8 words at most; the 16-word scan is not built
-            rc = ivr_fail(IVR_ERR_INVALID, "ivr_bin_index_search_pq: %d words per row", W);
-            return;
-        }
-        constexpr int WS = W > 8 ? 8 : W, R = pq_scan_rows(WS);
-        const int64_t nunits = ivr_ceil_div(ngroups, R);
-        for (int c0 = 0; c0 < nq && rc == IVR_OK; c0 += qc) {
-            const int nqc = std::min(qc, nq - c0);
-            const float *Tc = T + (int64_t)c0 * tab;
-            const int qg = std::min(qg_max, nqc);
-            const size_t lds = (size_t)qg * tab * sizeof(float);
-            rc = ivr_func_max_lds(reinterpret_cast<const void *>(pq_scan_kernel<WS, R>), (int)lds);
-            if (rc != IVR_OK) return;
-            // workgroups per CU that the LDS lets be resident, at most 2 (16 waves); each walks the rows with 8 waves
-            const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (160 * 1024) / (int64_t)lds));
-            const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ivr_ceil_div(nunits, kPqScanThreads / 64), per_cu * x->ctx->cu_count));
-            {
+    return t.run(
+        "ivr_bin_index_search_pq", "pq", nq, k, ngroups, D, I, nullptr, nullptr, s,
+        [&](int c0, int nqc) {
+            int rc = IVR_OK;
+            bin_with_words(x->w16, [&](auto w) {
+                constexpr int WS = decltype(w)::value > 8 ? 8 : decltype(w)::value, R = pq_scan_rows(WS);
+                const int qg = std::min(qg_max, nqc);
+                const size_t lds = (size_t)qg * tab * sizeof(float);
+                rc = ivr_func_max_lds(reinterpret_cast<const void *>(pq_scan_kernel<WS, R>), (int)lds);
+                if (rc != IVR_OK) return;
+                // workgroups per CU that the LDS lets be resident, at most 2 (16 waves); each walks the rows with 8 waves
+                const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (160 * 1024) / (int64_t)lds));
+                const unsigned gx = (unsigned)std::max<int64_t>(
+                    1, std::min<int64_t>(ivr_ceil_div(ivr_ceil_div(ngroups, R), kPqScanThreads / 64), per_cu * x->ctx->cu_count));
                 IvrProf prof("pq_scan", s, (double)nqc * ntotal * M);
-                hipLaunchKernelGGL((pq_scan_kernel<WS, R>), dim3(gx, (unsigned)ivr_ceil_div(nqc, qg)), dim3(kPqScanThreads), lds, s, x->data, ntotal, ngroups,
-                                   Tc, nqc, qg, M, gmax, mstride);
-            }
-            {
-                IvrProf prof("pq_select_groups", s, (double)nqc * ngroups * 4, true);
-                launch_select<OUT_GROUPS>(SrcPqGroups{gmax, mstride, ngroups}, nqc, ksel, SelectOut::to_groups(x->pq.sel), s);
-            }
-            {
-                const int64_t npairs = (int64_t)nqc * ksel;
+                hipLaunchKernelGGL((pq_scan_kernel<WS, R>), dim3(gx, (unsigned)ivr_ceil_div(nqc, qg)), dim3(kPqScanThreads), lds, s, x->data, ntotal,
+                                   ngroups, T + (int64_t)c0 * tab, nqc, qg, M, static_cast<float *>(t.gmax.ptr), t.mstride);
+            });
+            return rc;
+        },
+        [&](int c0, int, int64_t npairs) {
+            bin_with_words(x->w16, [&](auto w) {
+                constexpr int WS = decltype(w)::value > 8 ? 8 : decltype(w)::value;
                 IvrProf prof("pq_keys", s, (double)npairs * 64 * M, true);
-                hipLaunchKernelGGL(pq_keys_kernel<WS>, dim3((unsigned)ivr_ceil_div(npairs, 4)), dim3(256), 0, s, x->data, ntotal, ngroups, Tc, M,
-                                   (const uint32_t *)x->pq.sel, ksel, npairs, (uint64_t *)x->pq.keys);
-            }
-            {
-                IvrProf prof("pq_select_rows", s, (double)nqc * ksel * 64 * 8, true);
-                launch_select<OUT_DI>(SrcPqKeys{x->pq.keys, (int64_t)ksel * 64}, nqc, k, SelectOut::to_rows(D + (int64_t)c0 * k, I + (int64_t)c0 * k), s);
-            }
-            if (hipGetLastError() != hipSuccess) rc = ivr_fail(IVR_ERR_HIP, "ivr_bin_index_search_pq: launch failed");
-        }
-    });
-    return rc;
+                hipLaunchKernelGGL(pq_keys_kernel<WS>, dim3((unsigned)ivr_ceil_div(npairs, 4)), dim3(256), 0, s, x->data, ntotal, ngroups,
+                                   T + (int64_t)c0 * tab, M, (const uint32_t *)t.sel, t.ksel, npairs, (uint64_t *)t.keys);
+            });
+        });
 }
 
 }  // extern "C"

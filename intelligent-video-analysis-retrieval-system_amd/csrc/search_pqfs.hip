@@ -28,9 +28,9 @@
 // Scratch (grow-only, on the index object): 128 W bytes per staged query and, in its GroupTopK, 4 bytes per (query, group) and 520
 // per (query, selected group) of a chunk.
 #include "ivr_common.h"
+#include "search_coded.h"
 #include "search_internal.h"
 #include "search_lists.h"
-#include "search_select.h"
 
 #include <cfloat>
 
@@ -58,21 +58,6 @@ constexpr int kPqfsUnit = 4;
 constexpr int kPqfsThreads = 256;            // the scan's workgroup: 4 independent waves
 
 typedef unsigned short pqfs_u16x2 __attribute__((ext_vector_type(2)));
-
-// the keys of the two selections: instantiations of select_topk_kernel of this file's own (search_select.h)
-struct SrcPqfsGroups {  // the group maxima of query q
-    const int32_t *gmax;
-    int64_t mstride;
-    int64_t n;
-    __device__ uint64_t key(int q, int64_t i) const {
-        return ((uint64_t)((uint32_t)gmax[(int64_t)q * mstride + i] ^ 0x80000000u) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
-    }
-};
-struct SrcPqfsKeys {    // the re-scored rows of the selected groups
-    const uint64_t *keys;
-    int64_t n;
-    __device__ uint64_t key(int q, int64_t i) const { return keys[(int64_t)q * n + i]; }
-};
 
 __device__ __forceinline__ uint32_t pqfs_pk_add(uint32_t a, uint32_t b) {
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(pqfs_u16x2, a) + __builtin_bit_cast(pqfs_u16x2, b));
@@ -222,29 +207,6 @@ __global__ __launch_bounds__(256) void pqfs_keys_kernel(const uint4 *__restrict_
     keys[p * 64 + lane] = key;
 }
 
-// D[i] holds ivr_ord2f(key >> 32) of slot i as select_topk_kernel wrote it (I[i] >= 0) -> float(acc) * scale + bias of its query
-__global__ __launch_bounds__(256) void pqfs_finish_kernel(float *__restrict__ D, const int64_t *__restrict__ I,
-                                                          const float *__restrict__ scale, const float *__restrict__ bias, int64_t n, int k) {
-    SQ_NO_CONTRACT
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || I[i] < 0) return;
-    const uint32_t u = __float_as_uint(D[i]);
-    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);       // the inverse of ivr_ord2f
-    const int32_t acc = (int32_t)(o ^ 0x80000000u);
-    const int64_t q = i / k;
-    const float p = (float)acc * scale[q];
-    D[i] = p + bias[q];
-}
-
-// every result slot unused: an empty index
-__global__ __launch_bounds__(256) void pqfs_absent_kernel(int64_t n, float *__restrict__ D, int64_t *__restrict__ I) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        D[i] = -FLT_MAX;
-        I[i] = -1;
-    }
-}
-
 // U [nq][M][16] -> ut [nqp][8 W] tables of 16 bytes, zero for the sub-quantizers behind M and the queries behind nq
 __global__ __launch_bounds__(256) void pqfs_stage_kernel(const uint4 *__restrict__ U, int nq, int M, int W, int64_t total, uint4 *__restrict__ ut) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -386,25 +348,6 @@ __global__ __launch_bounds__(256) void pqfs_quantize_kernel(const float *__restr
 
 bool pqfs_valid_m(int M) { return M >= 2 && M <= IVR_PQFS_MAX_M && M % 2 == 0; }
 
-// room for n more rows.  CodeRows::reserve_for_add, but the block that takes over copies whole 256-row blocks: the rows of a block
-// are interleaved, so the groups in front of ntotal are not a prefix of its bytes
-int pqfs_reserve_for_add(ivr_pqfs_index *x, int64_t n, const char *what) {
-    if (x->ntotal + n <= x->cap) return IVR_OK;
-    IVR_REQUIRE(x->ntotal + n < (1ll << 31) - x->granule, "%s: index would exceed 2^31 rows", what);
-    IVR_HIP(hipDeviceSynchronize());
-    const int64_t rows = ivr_round_up(std::max<int64_t>(x->ntotal + n, x->cap + x->cap / 2), x->granule);
-    uint4 *nd = nullptr;
-    IVR_HIP(hipMalloc(&nd, x->bytes(rows)));
-    IVR_HIP(hipMemset(nd, 0, x->bytes(rows)));
-    if (x->data) {
-        if (x->ntotal > 0) IVR_HIP(hipMemcpy(nd, x->data, x->bytes(ivr_round_up(x->ntotal, x->granule)), hipMemcpyDeviceToDevice));
-        IVR_HIP(hipFree(x->data));
-    }
-    x->data = nd;
-    x->cap = rows;
-    return IVR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -473,12 +416,7 @@ int ivr_pqfs_index_destroy(ivr_pqfs_index *x) {
 
 int ivr_pqfs_index_reset(ivr_pqfs_index *x) {
     IVR_REQUIRE(x, "ivr_pqfs_index_reset: NULL index");
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->ntotal == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    IVR_HIP(hipDeviceSynchronize());         // a search in flight still reads the rows
-    x->ntotal = 0;                           // the bytes stay: every kernel masks the rows at or beyond ntotal by number
-    return IVR_OK;
+    return x->reset(false);
 }
 
 int64_t ivr_pqfs_index_ntotal(ivr_pqfs_index *x) {
@@ -487,32 +425,21 @@ int64_t ivr_pqfs_index_ntotal(ivr_pqfs_index *x) {
 }
 
 int ivr_pqfs_index_add(ivr_pqfs_index *x, const uint8_t *codes, int64_t n, ivr_stream stream) {
-    IVR_REQUIRE(x && (codes || n == 0), "ivr_pqfs_index_add: NULL argument");
-    IVR_REQUIRE(n >= 0, "ivr_pqfs_index_add: n=%lld", (long long)n);
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (n == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    if (int rc = pqfs_reserve_for_add(x, n, "ivr_pqfs_index_add")) return rc;
-    const int64_t total = n * 4 * x->W;
-    hipLaunchKernelGGL(pqfs_pack_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, codes,
-                       reinterpret_cast<uint8_t *>(x->data), x->ntotal, n, x->M / 2, x->W);
-    IVR_LAUNCH_CHECK();
-    x->ntotal += n;
-    return IVR_OK;
+    IVR_REQUIRE(x, "ivr_pqfs_index_add: NULL argument");
+    return x->add("ivr_pqfs_index_add", codes, n, [&] {
+        const int64_t total = n * 4 * x->W;
+        hipLaunchKernelGGL(pqfs_pack_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, codes,
+                           reinterpret_cast<uint8_t *>(x->data), x->ntotal, n, x->M / 2, x->W);
+    });
 }
 
 int ivr_pqfs_index_get_codes(ivr_pqfs_index *x, int64_t start, int64_t n, uint8_t *out, ivr_stream stream) {
-    IVR_REQUIRE(x && (out || n == 0), "ivr_pqfs_index_get_codes: NULL argument");
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_REQUIRE(start >= 0 && n >= 0 && start + n <= x->ntotal, "ivr_pqfs_index_get_codes: rows [%lld,%lld) outside [0,%lld)", (long long)start,
-                (long long)(start + n), (long long)x->ntotal);
-    if (n == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    const int64_t total = n * (x->M / 2);
-    hipLaunchKernelGGL(pqfs_unpack_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const uint8_t *>(x->data), start, n, x->M / 2, x->W, out);
-    IVR_LAUNCH_CHECK();
-    return IVR_OK;
+    IVR_REQUIRE(x, "ivr_pqfs_index_get_codes: NULL argument");
+    return x->get_codes("ivr_pqfs_index_get_codes", start, n, out, [&] {
+        const int64_t total = n * (x->M / 2);
+        hipLaunchKernelGGL(pqfs_unpack_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const uint8_t *>(x->data), start, n, x->M / 2, x->W, out);
+    });
 }
 
 int ivr_pqfs_index_search(ivr_pqfs_index *x, const uint8_t *U, const float *scale, const float *bias, int nq, int k, float *D, int64_t *I,
@@ -525,17 +452,10 @@ int ivr_pqfs_index_search(ivr_pqfs_index *x, const uint8_t *U, const float *scal
     IVR_HIP(hipSetDevice(x->ctx->device));
     hipStream_t s = (hipStream_t)stream;
     const int64_t ntotal = x->ntotal, ngroups = ivr_ceil_div(ntotal, 64), nblocks = ivr_ceil_div(ntotal, kPqfsBlockRows);
-    if (ntotal == 0) {
-        const int64_t n = (int64_t)nq * k;
-        hipLaunchKernelGGL(pqfs_absent_kernel, dim3((unsigned)ivr_ceil_div(n, 256)), dim3(256), 0, s, n, D, I);
-        IVR_LAUNCH_CHECK();
-        return IVR_OK;
-    }
-    int64_t mstride;
-    int ksel, qc;
-    int rc = x->topk.plan(nq, k, ngroups, kPqfsPassQ, mstride, ksel, qc);
+    if (ntotal == 0) return GroupTopK::absent(nq, k, D, I, s);
+    GroupTopK &g = x->topk;
+    int rc = g.plan(nq, k, ngroups, kPqfsPassQ);
     if (rc != IVR_OK) return rc;
-    int32_t *gmax = static_cast<int32_t *>(x->topk.gmax.ptr);
     const int W = x->W;
     const int64_t nqp = ivr_round_up(nq, kPqfsPassQ), tw = 8 * W;        // 16-byte tables per query
     rc = ivr_reserve({{&x->ut, (size_t)(nqp * tw) * sizeof(uint4)}});
@@ -545,43 +465,26 @@ int ivr_pqfs_index_search(ivr_pqfs_index *x, const uint8_t *U, const float *scal
         hipLaunchKernelGGL(pqfs_stage_kernel, dim3((unsigned)ivr_ceil_div(nqp * tw, 256)), dim3(256), 0, s, reinterpret_cast<const uint4 *>(U), nq,
                            x->M, W, nqp * tw, (uint4 *)x->ut);
     }
-    for (int c0 = 0; c0 < nq && rc == IVR_OK; c0 += qc) {                // c0 is a multiple of kPqfsPassQ
-        const int nqc = std::min(qc, nq - c0);
-        const uint4 *ut = x->ut + (int64_t)c0 * tw;
-        pqfs_with_pass(nqc, [&](auto qv, auto rv) {
-            constexpr int Q = decltype(qv)::value, R = decltype(rv)::value;
-            const unsigned passes = (unsigned)ivr_ceil_div(nqc, Q);
-            // 8 workgroups (32 waves) per CU over all passes; each walks the units of R blocks with 4 waves
-            const unsigned gx = (unsigned)std::max<int64_t>(
-                1, std::min<int64_t>(ivr_ceil_div(ivr_ceil_div(nblocks, R), kPqfsThreads / 64), ivr_ceil_div(8ll * x->ctx->cu_count, passes)));
-            IvrProf prof("pqfs_scan", s, (double)passes * nblocks * x->block_words() * 16);
-            hipLaunchKernelGGL((pqfs_scan_kernel<Q, R>), dim3(gx, passes), dim3(kPqfsThreads), 0, s, x->data, ntotal, nblocks, W, ut, nqc, gmax,
-                               mstride);
-        });
-        {
-            IvrProf prof("pqfs_select_groups", s, (double)nqc * ngroups * 4, true);
-            launch_select<OUT_GROUPS>(SrcPqfsGroups{gmax, mstride, ngroups}, nqc, ksel, SelectOut::to_groups(x->topk.sel), s);
-        }
-        const int64_t npairs = (int64_t)nqc * ksel;
-        {
+    return g.run(
+        "ivr_pqfs_index_search", "pqfs", nq, k, ngroups, D, I, scale, bias, s,
+        [&](int c0, int nqc) {
+            pqfs_with_pass(nqc, [&](auto qv, auto rv) {
+                constexpr int Q = decltype(qv)::value, R = decltype(rv)::value;
+                const unsigned passes = (unsigned)ivr_ceil_div(nqc, Q);
+                // 8 workgroups (32 waves) per CU over all passes; each walks the units of R blocks with 4 waves
+                const unsigned gx = (unsigned)std::max<int64_t>(
+                    1, std::min<int64_t>(ivr_ceil_div(ivr_ceil_div(nblocks, R), kPqfsThreads / 64), ivr_ceil_div(8ll * x->ctx->cu_count, passes)));
+                IvrProf prof("pqfs_scan", s, (double)passes * nblocks * x->block_words() * 16);
+                hipLaunchKernelGGL((pqfs_scan_kernel<Q, R>), dim3(gx, passes), dim3(kPqfsThreads), 0, s, x->data, ntotal, nblocks, W,
+                                   x->ut + (int64_t)c0 * tw, nqc, static_cast<int32_t *>(g.gmax.ptr), g.mstride);
+            });
+            return IVR_OK;
+        },
+        [&](int c0, int, int64_t npairs) {
             IvrProf prof("pqfs_keys", s, (double)npairs * x->block_words() * 16, true);
-            hipLaunchKernelGGL(pqfs_keys_kernel, dim3((unsigned)ivr_ceil_div(npairs, 4)), dim3(256), 0, s, x->data, ntotal, ngroups, W, ut,
-                               (const uint32_t *)x->topk.sel, ksel, npairs, (uint64_t *)x->topk.keys);
-        }
-        float *Dc = D + (int64_t)c0 * k;
-        int64_t *Ic = I + (int64_t)c0 * k;
-        {
-            IvrProf prof("pqfs_select_rows", s, (double)nqc * ksel * 64 * 8, true);
-            launch_select<OUT_DI>(SrcPqfsKeys{x->topk.keys, (int64_t)ksel * 64}, nqc, k, SelectOut::to_rows(Dc, Ic), s);
-        }
-        {
-            const int64_t n = (int64_t)nqc * k;
-            IvrProf prof("pqfs_finish", s, (double)n * 16, true);
-            hipLaunchKernelGGL(pqfs_finish_kernel, dim3((unsigned)ivr_ceil_div(n, 256)), dim3(256), 0, s, Dc, Ic, scale + c0, bias + c0, n, k);
-        }
-        if (hipGetLastError() != hipSuccess) rc = ivr_fail(IVR_ERR_HIP, "ivr_pqfs_index_search: launch failed");
-    }
-    return rc;
+            hipLaunchKernelGGL(pqfs_keys_kernel, dim3((unsigned)ivr_ceil_div(npairs, 4)), dim3(256), 0, s, x->data, ntotal, ngroups, W,
+                               x->ut + (int64_t)c0 * tw, (const uint32_t *)g.sel, g.ksel, npairs, (uint64_t *)g.keys);
+        });
 }
 
 }  // extern "C"

@@ -24,9 +24,9 @@
 // 520 per (query, selected group) of a chunk.  sq_frag, sq_combine and SQ_NO_CONTRACT are in search_lists.h and sq_stage_kernel is
 // behind ivr_launch_sq_stage: search_ivfsq.hip stages its queries and combines its halves the same way.
 #include "ivr_common.h"
+#include "search_coded.h"
 #include "search_internal.h"
 #include "search_lists.h"
-#include "search_select.h"
 
 #include <cfloat>
 #include <climits>
@@ -73,21 +73,6 @@ __global__ __launch_bounds__(256) void sq_stage_kernel(const int16_t *__restrict
     qh[w] = uint4{h[0], h[1], h[2], h[3]};
     ql[w] = uint4{l[0], l[1], l[2], l[3]};
 }
-
-// the keys of the two selections: instantiations of select_topk_kernel of this file's own (search_select.h)
-struct SrcSqGroups {   // the group maxima of query q
-    const int32_t *gmax;
-    int64_t mstride;
-    int64_t n;
-    __device__ uint64_t key(int q, int64_t i) const {
-        return ((uint64_t)((uint32_t)gmax[(int64_t)q * mstride + i] ^ 0x80000000u) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
-    }
-};
-struct SrcSqKeys {     // the re-scored rows of the selected groups
-    const uint64_t *keys;
-    int64_t n;
-    __device__ uint64_t key(int q, int64_t i) const { return keys[(int64_t)q * n + i]; }
-};
 
 // gmax[q][g] = the best acc of the stored rows of group g for the 32 queries of pass blockIdx.y.  Wave w of workgroup b takes the
 // groups b * 4 + w, + gridDim.x * 4, ...  In an accumulator tile lane l holds query l & 15 and rows 4 (l >> 4) + reg.
@@ -187,29 +172,6 @@ __global__ __launch_bounds__(256) void sq_keys_kernel(const uint4 *__restrict__ 
                 keys[p * 64 + in] = row < ntotal ? ((uint64_t)(acc ^ 0x80000000u) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)row) : 0;
             }
         }
-    }
-}
-
-// D[i] holds ivr_ord2f(key >> 32) of slot i as select_topk_kernel wrote it (I[i] >= 0) -> float(acc) * scale + bias of its query
-__global__ __launch_bounds__(256) void sq_finish_kernel(float *__restrict__ D, const int64_t *__restrict__ I, const float *__restrict__ scale,
-                                                        const float *__restrict__ bias, int64_t n, int k) {
-    SQ_NO_CONTRACT
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || I[i] < 0) return;
-    const uint32_t u = __float_as_uint(D[i]);
-    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);       // the inverse of ivr_ord2f
-    const int32_t acc = (int32_t)(o ^ 0x80000000u);
-    const int64_t q = i / k;
-    const float p = (float)acc * scale[q];
-    D[i] = p + bias[q];
-}
-
-// every result slot unused: an empty index
-__global__ __launch_bounds__(256) void sq_absent_kernel(int64_t n, float *__restrict__ D, int64_t *__restrict__ I) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        D[i] = -FLT_MAX;
-        I[i] = -1;
     }
 }
 
@@ -361,12 +323,7 @@ int ivr_sq_index_destroy(ivr_sq_index *x) {
 
 int ivr_sq_index_reset(ivr_sq_index *x) {
     IVR_REQUIRE(x, "ivr_sq_index_reset: NULL index");
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->ntotal == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    IVR_HIP(hipDeviceSynchronize());         // a search in flight still reads the rows
-    x->ntotal = 0;                           // the bytes stay: every kernel masks the rows at or beyond ntotal by number
-    return IVR_OK;
+    return x->reset(false);
 }
 
 int64_t ivr_sq_index_ntotal(ivr_sq_index *x) {
@@ -375,33 +332,22 @@ int64_t ivr_sq_index_ntotal(ivr_sq_index *x) {
 }
 
 int ivr_sq_index_add(ivr_sq_index *x, const uint8_t *codes, int64_t n, ivr_stream stream) {
-    IVR_REQUIRE(x && (codes || n == 0), "ivr_sq_index_add: NULL argument");
-    IVR_REQUIRE(n >= 0, "ivr_sq_index_add: n=%lld", (long long)n);
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (n == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    if (int rc = x->reserve_for_add(n, "ivr_sq_index_add")) return rc;
-    const int64_t words = n * x->ksteps * 4;
-    const int vec = x->d % 16 == 0 && ((uintptr_t)codes & 15) == 0;
-    hipLaunchKernelGGL(sq_pack_kernel, dim3((unsigned)ivr_ceil_div(words, 256)), dim3(256), 0, (hipStream_t)stream, codes, x->data, x->ntotal, n,
-                       x->d, x->ksteps, vec);
-    IVR_LAUNCH_CHECK();
-    x->ntotal += n;
-    return IVR_OK;
+    IVR_REQUIRE(x, "ivr_sq_index_add: NULL argument");
+    return x->add("ivr_sq_index_add", codes, n, [&] {
+        const int64_t words = n * x->ksteps * 4;
+        const int vec = x->d % 16 == 0 && ((uintptr_t)codes & 15) == 0;
+        hipLaunchKernelGGL(sq_pack_kernel, dim3((unsigned)ivr_ceil_div(words, 256)), dim3(256), 0, (hipStream_t)stream, codes, x->data, x->ntotal,
+                           n, x->d, x->ksteps, vec);
+    });
 }
 
 int ivr_sq_index_get_codes(ivr_sq_index *x, int64_t start, int64_t n, uint8_t *out, ivr_stream stream) {
-    IVR_REQUIRE(x && (out || n == 0), "ivr_sq_index_get_codes: NULL argument");
-    std::lock_guard<std::mutex> lk(x->mu);
-    IVR_REQUIRE(start >= 0 && n >= 0 && start + n <= x->ntotal, "ivr_sq_index_get_codes: rows [%lld,%lld) outside [0,%lld)", (long long)start,
-                (long long)(start + n), (long long)x->ntotal);
-    if (n == 0) return IVR_OK;
-    IVR_HIP(hipSetDevice(x->ctx->device));
-    const int64_t words = n * ((x->d + 15) / 16);
-    hipLaunchKernelGGL(sq_unpack_kernel, dim3((unsigned)ivr_ceil_div(words, 256)), dim3(256), 0, (hipStream_t)stream, x->data, start, n, x->d,
-                       x->ksteps, out);
-    IVR_LAUNCH_CHECK();
-    return IVR_OK;
+    IVR_REQUIRE(x, "ivr_sq_index_get_codes: NULL argument");
+    return x->get_codes("ivr_sq_index_get_codes", start, n, out, [&] {
+        const int64_t words = n * ((x->d + 15) / 16);
+        hipLaunchKernelGGL(sq_unpack_kernel, dim3((unsigned)ivr_ceil_div(words, 256)), dim3(256), 0, (hipStream_t)stream, x->data, start, n, x->d,
+                           x->ksteps, out);
+    });
 }
 
 int ivr_sq_index_search(ivr_sq_index *x, const int16_t *t, const float *scale, const float *bias, int nq, int k, float *D, int64_t *I,
@@ -413,18 +359,11 @@ int ivr_sq_index_search(ivr_sq_index *x, const int16_t *t, const float *scale, c
     IVR_HIP(hipSetDevice(x->ctx->device));
     hipStream_t s = (hipStream_t)stream;
     const int64_t ntotal = x->ntotal, ngroups = ivr_ceil_div(ntotal, 64);
-    if (ntotal == 0) {
-        const int64_t n = (int64_t)nq * k;
-        hipLaunchKernelGGL(sq_absent_kernel, dim3((unsigned)ivr_ceil_div(n, 256)), dim3(256), 0, s, n, D, I);
-        IVR_LAUNCH_CHECK();
-        return IVR_OK;
-    }
+    if (ntotal == 0) return GroupTopK::absent(nq, k, D, I, s);
     constexpr int kPass = 16 * kSqQT;        // queries of one index pass
-    int64_t mstride;
-    int ksel, qc;
-    int rc = x->topk.plan(nq, k, ngroups, kPass, mstride, ksel, qc);
+    GroupTopK &g = x->topk;
+    int rc = g.plan(nq, k, ngroups, kPass);
     if (rc != IVR_OK) return rc;
-    int32_t *gmax = static_cast<int32_t *>(x->topk.gmax.ptr);
     const int64_t tw = x->tile_words(), qtiles = ivr_round_up(ivr_ceil_div(nq, 16), kSqQT);
     rc = ivr_reserve({{&x->qh, (size_t)(qtiles * tw) * sizeof(uint4)}, {&x->ql, (size_t)(qtiles * tw) * sizeof(uint4)}});
     if (rc != IVR_OK) return rc;
@@ -437,41 +376,23 @@ int ivr_sq_index_search(ivr_sq_index *x, const int16_t *t, const float *scale, c
     }
     // workgroups per CU that the LDS lets be resident, at most 4 (16 waves); each walks the groups with 4 waves
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / (int64_t)lds));
-    for (int c0 = 0; c0 < nq && rc == IVR_OK; c0 += qc) {                // c0 is a multiple of kPass
-        const int nqc = std::min(qc, nq - c0);
-        const uint4 *qh = x->qh + (int64_t)(c0 / 16) * tw, *ql = x->ql + (int64_t)(c0 / 16) * tw;
-        const unsigned passes = (unsigned)ivr_ceil_div(nqc, kPass);
-        const unsigned gx = (unsigned)std::max<int64_t>(
-            1, std::min<int64_t>(ivr_ceil_div(ngroups, kSqThreads / 64), ivr_ceil_div(per_cu * x->ctx->cu_count, passes)));
-        {
+    return g.run(
+        "ivr_sq_index_search", "sq", nq, k, ngroups, D, I, scale, bias, s,
+        [&](int c0, int nqc) {
+            const unsigned passes = (unsigned)ivr_ceil_div(nqc, kPass);
+            const unsigned gx = (unsigned)std::max<int64_t>(
+                1, std::min<int64_t>(ivr_ceil_div(ngroups, kSqThreads / 64), ivr_ceil_div(per_cu * x->ctx->cu_count, passes)));
             IvrProf prof("sq_scan", s, (double)passes * ngroups * 4 * tw * 16);
-            hipLaunchKernelGGL(sq_scan_kernel, dim3(gx, passes), dim3(kSqThreads), lds, s, x->data, ntotal, ngroups, x->ksteps, qh, ql, nqc, gmax,
-                               mstride);
-        }
-        {
-            IvrProf prof("sq_select_groups", s, (double)nqc * ngroups * 4, true);
-            launch_select<OUT_GROUPS>(SrcSqGroups{gmax, mstride, ngroups}, nqc, ksel, SelectOut::to_groups(x->topk.sel), s);
-        }
-        const int64_t npairs = (int64_t)nqc * ksel;
-        {
+            hipLaunchKernelGGL(sq_scan_kernel, dim3(gx, passes), dim3(kSqThreads), lds, s, x->data, ntotal, ngroups, x->ksteps,
+                               x->qh + (int64_t)(c0 / 16) * tw, x->ql + (int64_t)(c0 / 16) * tw, nqc, static_cast<int32_t *>(g.gmax.ptr), g.mstride);
+            return IVR_OK;
+        },
+        [&](int c0, int, int64_t npairs) {
             IvrProf prof("sq_keys", s, (double)npairs * 4 * tw * 16, true);
-            hipLaunchKernelGGL(sq_keys_kernel, dim3((unsigned)ivr_ceil_div(npairs, 4)), dim3(256), 0, s, x->data, ntotal, ngroups, x->ksteps, qh, ql,
-                               (const uint32_t *)x->topk.sel, ksel, npairs, (uint64_t *)x->topk.keys);
-        }
-        float *Dc = D + (int64_t)c0 * k;
-        int64_t *Ic = I + (int64_t)c0 * k;
-        {
-            IvrProf prof("sq_select_rows", s, (double)nqc * ksel * 64 * 8, true);
-            launch_select<OUT_DI>(SrcSqKeys{x->topk.keys, (int64_t)ksel * 64}, nqc, k, SelectOut::to_rows(Dc, Ic), s);
-        }
-        {
-            const int64_t n = (int64_t)nqc * k;
-            IvrProf prof("sq_finish", s, (double)n * 16, true);
-            hipLaunchKernelGGL(sq_finish_kernel, dim3((unsigned)ivr_ceil_div(n, 256)), dim3(256), 0, s, Dc, Ic, scale + c0, bias + c0, n, k);
-        }
-        if (hipGetLastError() != hipSuccess) rc = ivr_fail(IVR_ERR_HIP, "ivr_sq_index_search: launch failed");
-    }
-    return rc;
+            hipLaunchKernelGGL(sq_keys_kernel, dim3((unsigned)ivr_ceil_div(npairs, 4)), dim3(256), 0, s, x->data, ntotal, ngroups, x->ksteps,
+                               x->qh + (int64_t)(c0 / 16) * tw, x->ql + (int64_t)(c0 / 16) * tw, (const uint32_t *)g.sel, g.ksel, npairs,
+                               (uint64_t *)g.keys);
+        });
 }
 
 }  // extern "C"

@@ -1,18 +1,66 @@
-"""What the code-based indexes (IndexLSH, PQIndex, SQIndex) share: rows are encoded on the device, only their codes are stored, and a
-search scans the codes.
+"""What the code-based indexes (IndexLSH, PQIndex, SQIndex, PQFastScanIndex) share: rows are encoded on the device, only their codes
+are stored, and a search scans the codes.
 
 A subclass supplies `_encode_device(t, ...)` (contiguous float32 CUDA rows -> uint8 CUDA codes), its trained state (`is_trained` and
 the tables behind it, refused while rows are stored: `_require_empty`), `search_device`, and in `_index` a store of code rows with
-`ntotal`, `_add_device(codes)`, `_codes_device(start, n)`, `reset()` and `close()` (a `BinaryFlatIndex`, or the store of sq.py).
+`ntotal`, `_add_device(codes)`, `_codes_device(start, n)`, `reset()` and `close()`: a `_CodeStore` below (the handle of one of the
+library's row stores, csrc/search_coded.h), or a `BinaryFlatIndex`, which takes its adding and reading from it.
 `DecodableIndex` adds the decode half for the codes that stand for a row (`sa_decode_device` is the subclass's).
 """
 import numpy as np
 import torch
 
-from . import _staging
+from . import _ffi, _staging
 from ._faiss import search_numpy
 
 ENCODE_CHUNK = 1 << 18        # rows of a host array staged per encoder launch
+
+
+class _CodeStore(_ffi.Handle):
+    """The code rows of a coded index behind one family of the ABI (`abi`_create, _add, _get_codes, _reset, _ntotal, _destroy):
+    uint8 [n, code_size] in, the same bytes out.  The library handle is made by the first call that needs it, `abi`_create(ctx,
+    *create_args, &handle), so that an index can be made and refuse untrained use where there is no GPU.  owner: the index class, for
+    the message of a closed index."""
+
+    def __init__(self, abi, create_args, code_size, owner, device):
+        self._abi, self._create_args, self.code_size, self._owner = abi, create_args, code_size, owner
+        self._DESTROY = abi + "_destroy"
+        self.device = torch.device("cuda", int(device) if device is not None else
+                                   torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self._closed = False
+
+    def _call(self, name, *args):
+        if self._h is None:
+            if self._closed:
+                raise RuntimeError(f"{self._owner}: the index is closed")
+            self._open(self._abi + "_create", self.device.index, *self._create_args)
+        return super()._call(name, *args)
+
+    def close(self):
+        self._closed = True
+        super().close()
+
+    @property
+    def ntotal(self):
+        return 0 if self._h is None else int(_ffi.call(self._abi + "_ntotal", self._h))
+
+    def _add_device(self, codes):
+        self._call(self._abi + "_add", codes, codes.shape[0])
+        torch.cuda.current_stream(self.device).synchronize()  # `codes` may be a temporary staging copy
+
+    def _codes_device(self, start=0, n=None):
+        start = int(start)
+        n = self.ntotal - start if n is None else int(n)
+        if start < 0 or n < 0 or start + n > self.ntotal:
+            raise ValueError(f"reconstruct_n: rows [{start},{start + n}) outside [0,{self.ntotal})")
+        out = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device)
+        if n:
+            self._call(self._abi + "_get_codes", start, n, out)
+        return out
+
+    def reset(self):
+        if self._h is not None:
+            self._call(self._abi + "_reset")
 
 
 class CodedIndex:

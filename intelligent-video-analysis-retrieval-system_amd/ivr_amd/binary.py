@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _ffi, _staging
-from ._coded import CodedIndex, cat_chunks
+from ._coded import CodedIndex, _CodeStore, cat_chunks
 from ._faiss import METRIC_L2, search_numpy
 from ._staging import dev_u8 as _dev_u8
 
@@ -39,7 +39,8 @@ def lsh_rotation(d, nbits, seed=5):
 class BinaryFlatIndex(_ffi.Handle):
     """Exact Hamming-distance index over binary codes (FAISS IndexBinaryFlat contract) on one GPU.  d_bits is the code length in
     bits and must be a multiple of 8, as in faiss; a code is d_bits / 8 bytes."""
-    _DESTROY = "ivr_bin_index_destroy"
+    _DESTROY, _abi = "ivr_bin_index_destroy", "ivr_bin_index"
+    _add_device, _codes_device = _CodeStore._add_device, _CodeStore._codes_device     # the handle itself is opened at once, below
 
     def __init__(self, d_bits, device=None):
         d_bits = int(d_bits)
@@ -61,10 +62,6 @@ class BinaryFlatIndex(_ffi.Handle):
         """Append codes: uint8 [n, d/8], a numpy array or a torch tensor."""
         self._add_device(_dev_u8(codes, self.code_size, self.device, "add"))
 
-    def _add_device(self, t):
-        self._call("ivr_bin_index_add", t, t.shape[0])
-        torch.cuda.current_stream(self.device).synchronize()  # `t` may be a temporary staging copy
-
     def search(self, codes, k):
         """(D, I) numpy arrays: D int32 [nq,k] Hamming distances ascending, I int64 row numbers; equal distances rank the lower row
         first; unused slots (2147483647, -1)."""
@@ -84,16 +81,6 @@ class BinaryFlatIndex(_ffi.Handle):
     def reconstruct_n(self, start=0, n=None):
         """The stored codes of rows [start, start + n) as numpy uint8 [n, d/8]."""
         return self._codes_device(start, n).cpu().numpy()
-
-    def _codes_device(self, start=0, n=None):
-        start = int(start)
-        n = self.ntotal - start if n is None else int(n)
-        if start < 0 or n < 0 or start + n > self.ntotal:
-            raise ValueError(f"reconstruct_n: rows [{start},{start + n}) outside [0,{self.ntotal})")
-        out = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device)
-        if n:
-            self._call("ivr_bin_index_get_codes", start, n, out)
-        return out
 
     def reset(self):
         self._call("ivr_bin_index_reset")

@@ -11,17 +11,16 @@ segment means, repair of empty clusters) is `_kmeans.py`'s, shared with the coar
 What the kernels are pinned to is stated by the numpy functions below: `pq_encode_ref`, `pq_tables_ref` (float64 references with the
 tolerances in their docstrings) and `pq_scan_ref` (the float32 additions of the scan, which numpy reproduces to the bit).
 
-faiss's own k-means draws from a random stream that cannot be reproduced here, so training is defined by `train` below; a codebook
+faiss's own k-means draws from a random stream that cannot be reproduced here, so training is defined by `train` (_pqbase.py); a codebook
 exported from a real faiss index can be assigned to `centroids` while the index is empty and then reproduces that index's codes up
 to the rounding stated in `pq_encode_ref`.
 """
 import numpy as np
 import torch
 
-from . import _ffi, _kmeans, _staging
-from ._coded import DecodableIndex
+from . import _ffi, _pqbase, _staging
 from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
-from ._staging import dev_f32 as _dev_f32, dev_u8 as _dev_u8
+from ._staging import dev_f32 as _dev_f32
 from .binary import BinaryFlatIndex
 
 KSUB = 256                    # centroids per slice: nbits = 8
@@ -44,25 +43,13 @@ def pq_encode_ref(x, centroids):
         dist[i,m,j] <= min_j' dist[i,m,j'] + 2 * (dsub + 3) * 2^-23 * (|x_m|^2 + max_j |centroids[m,j]|^2):
     the first-order float32 rounding bound of sum (x - c)^2 and of |c|^2 - 2 <x, c> alike, doubled because two distances are
     compared.  Two centroids with identical bits always resolve to the lower j."""
-    c = _codebooks(centroids).astype(np.float64)
-    M, _, dsub = c.shape
-    x = np.asarray(x, np.float64)
-    if x.ndim != 2 or x.shape[1] != M * dsub:
-        raise ValueError(f"pq_encode_ref: x must be [n,{M * dsub}], got {x.shape}")
-    xs = x.reshape(len(x), M, 1, dsub)
-    dist = ((xs - c[None]) ** 2).sum(-1)
-    return dist.argmin(-1).astype(np.uint8), dist
+    return _pqbase.encode_ref("pq_encode_ref", x, _codebooks(centroids))
 
 
 def pq_tables_ref(q, centroids):
     """The lookup tables in float64: T[i,m,j] = <slice m of q[i], centroids[m,j]>, [nq,M,256].  The kernel's float32 entry lies
     within (dsub + 2) * 2^-24 * sum_t |q_t * c_t| of it."""
-    c = _codebooks(centroids).astype(np.float64)
-    M, _, dsub = c.shape
-    q = np.asarray(q, np.float64)
-    if q.ndim != 2 or q.shape[1] != M * dsub:
-        raise ValueError(f"pq_tables_ref: q must be [nq,{M * dsub}], got {q.shape}")
-    return np.einsum("imt,mjt->imj", q.reshape(len(q), M, dsub), c)
+    return _pqbase.tables_ref("pq_tables_ref", q, _codebooks(centroids))
 
 
 def pq_scan_ref(T, codes, k):
@@ -91,12 +78,14 @@ def pq_scan_ref(T, codes, k):
     return D, I
 
 
-class PQIndex(DecodableIndex):
+class PQIndex(_pqbase.ProductQuantizerIndex):
     """Product-quantisation index (FAISS IndexPQ contract, METRIC_INNER_PRODUCT, nbits = 8) on one GPU.
 
     search(x, k) returns (D float32, I int64): the asymmetric score pq_scan_ref defines, descending, equal scores the lower row
     first (quantised scores tie in bulk: rows with the same code always do), unused slots (-FLT_MAX, -1).  add() and search() raise
-    RuntimeError until train() has run or `centroids` has been assigned."""
+    RuntimeError until train() has run or `centroids` (numpy float32 [M,256,dsub]) has been assigned.  train(x) needs n >= 256 rows; the
+    codebook state, train, sa_decode_device, search_tables and search_device are ProductQuantizerIndex's (_pqbase.py)."""
+    _KSUB, _ENCODE = KSUB, "ivr_pq_encode"
 
     def __init__(self, d, M, nbits=8, metric=METRIC_INNER_PRODUCT, device=None):
         self.d, self.M = int(d), int(M)
@@ -105,84 +94,12 @@ class PQIndex(DecodableIndex):
         require_inner_product(metric, "PQIndex")
         if self.M < 1 or self.M > _ffi.IVR_PQ_MAX_M:
             raise ValueError(f"PQIndex: M={M} outside [1,{_ffi.IVR_PQ_MAX_M}]")
-        if self.d < 1 or self.d > 65536 or self.d % self.M != 0:
-            raise ValueError(f"PQIndex: d={d} outside [1,65536] or not a multiple of M={self.M}")
-        self.dsub = self.d // self.M
-        self.code_size = self.M
-        self.nbits = 8
-        self.metric_type = METRIC_INNER_PRODUCT
-        self.is_trained = False
-        self._index = BinaryFlatIndex(8 * self.M, device=device)
-        self.device = self._index.device
-        self._centroids = np.zeros((self.M, KSUB, self.dsub), np.float32)
-        self._cb_dev = None
+        self._setup("PQIndex", d, 8, self.M, lambda: BinaryFlatIndex(8 * self.M, device=device))
 
-    # -- attributes ------------------------------------------------------------------------------
-    @property
-    def centroids(self):
-        """numpy float32 [M,256,dsub]: the codebooks.  Assignable while the index is empty, which makes it trained."""
-        return self._centroids
-
-    @centroids.setter
-    def centroids(self, c):
-        self._require_empty("centroids", "codebooks")
-        c = np.asarray(c)
-        if c.shape != self._centroids.shape:
-            raise ValueError(f"centroids expects [{self.M},{KSUB},{self.dsub}], got {c.shape}")
-        self._set_centroids(np.ascontiguousarray(c, dtype=np.float32))
-
-    def _set_centroids(self, c, dev=None):
-        self._centroids, self._cb_dev = c, dev
-        self.is_trained = True
-
-    def _codebooks_device(self):
-        if self._cb_dev is None:
-            self._cb_dev = torch.from_numpy(self._centroids).to(self.device)
-        return self._cb_dev
-
-    # -- encoding --------------------------------------------------------------------------------
-    def _encode_device(self, t, cb=None):
-        """t: contiguous float32 CUDA tensor [n,d] -> codes uint8 CUDA [n,M] under the codebooks cb (default: the index's)."""
-        codes = torch.empty((t.shape[0], self.M), dtype=torch.uint8, device=self.device)
-        _ffi.call("ivr_pq_encode", _ffi.CTX, t, t.shape[0], self.d, self._codebooks_device() if cb is None else cb, self.M, codes,
-                  device=self.device)
-        return codes
-
-    def sa_decode_device(self, codes):
-        """float32 CUDA [n,d]: row i is the concatenation of centroids[m, codes[i,m]] over m (a gather, no arithmetic)."""
-        self._require_trained("sa_decode")
-        c = _dev_u8(codes, self.M, self.device, "sa_decode").to(torch.int64)
-        m = torch.arange(self.M, device=self.device).expand(c.shape[0], -1)
-        return self._codebooks_device()[m, c].reshape(c.shape[0], self.d)
-
-    # -- training --------------------------------------------------------------------------------
-    def train(self, x, niter=25, seed=1234, max_points_per_centroid=256):
-        """Make the M codebooks by k-means on x [n,d], n >= 256 (ValueError otherwise):
-          sample   _kmeans.kmeans_sample(n, 256, max_points_per_centroid, seed): one sample serves all slices, and the initial codebook of
-                   slice m is slice m of its first 256 rows
-          iterate  niter times: assign every sampled row's slices with the encoder (ivr_pq_encode: equal distances pick the lower
-                   centroid), order the rows of each slice by code (stable), take the mean of every run (ivr_segment_mean with
-                   spherical=False: fixed summation order, so a seed gives the same bits every time), repair empty clusters
-                   (split_empty_clusters, per slice).  The loop's shared halves are those of _kmeans.py."""
-        self._require_empty("train", "codebooks")
-        _staging.check_rows(x, self.d, "train")
-        n = len(x)
-        if n < KSUB:
-            raise ValueError(f"train: {n} training rows for {KSUB} centroids per slice")
-        niter = _kmeans.check_niter(niter)
-        with torch.cuda.device(self.device):
-            xs = _kmeans.sample_rows(x, KSUB, max_points_per_centroid, seed, self.device)
-            cent = xs[:KSUB].reshape(KSUB, self.M, self.dsub).permute(1, 0, 2).contiguous()
-            for _ in range(niter):
-                cent = self._kmeans_step(xs, cent)
-            self._set_centroids(cent.cpu().numpy(), cent)
-
-    def _kmeans_step(self, xs, cent):
-        a = self._encode_device(xs, cent).t().contiguous().to(torch.int64)        # [M, ns]
-        order = torch.argsort(a, dim=1, stable=True)        # one batched sort for all slices
-        out = torch.empty_like(cent)
-        counts = [_kmeans.segment_means(xs[:, m * self.dsub:(m + 1) * self.dsub], a[m], KSUB, out[m], order=order[m]) for m in range(self.M)]
-        return _kmeans.repair_empty_clusters(out, torch.stack(counts).cpu().numpy())
+    @staticmethod
+    def _slice_codes(codes):
+        """codes uint8 CUDA [n,M] -> int64 CUDA [n,M]: a byte is the centroid of its slice."""
+        return codes.to(torch.int64)
 
     # -- FAISS surface ---------------------------------------------------------------------------
     def compute_tables_device(self, x):
@@ -215,17 +132,6 @@ class PQIndex(DecodableIndex):
         self._index._call("ivr_bin_index_search_pq", t, nq, self.M, k, D, I)
         _staging.sync_if_staged(_staging.is_staged(t, T), self.device)
         return D, I
-
-    def search_tables(self, T, k):
-        """search_tables_device as numpy arrays."""
-        D, I = self.search_tables_device(T, k)
-        return D.cpu().numpy(), I.cpu().numpy()
-
-    def search_device(self, x, k):
-        """search returning CUDA tensors: search_tables_device(compute_tables_device(x), k), bit for bit."""
-        self._require_trained("search")
-        k = _staging.check_k(k, _ffi.IVR_MAX_K)
-        return self.search_tables_device(self.compute_tables_device(x), k)
 
 
 def IndexPQ(d, M, nbits=8, metric=METRIC_INNER_PRODUCT):

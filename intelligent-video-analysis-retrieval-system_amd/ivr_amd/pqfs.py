@@ -13,14 +13,14 @@ What the kernels are pinned to is stated by the numpy functions below: `pqfs_enc
 with the tolerances in their docstrings), `pqfs_quantize_ref` and `pqfs_scan_ref` (to the bit), `pqfs_pack_ref` / `pqfs_unpack_ref`
 (the byte form of a code).
 
-faiss's own k-means draws from a random stream that cannot be reproduced here, so training is defined by `train` below; a codebook
+faiss's own k-means draws from a random stream that cannot be reproduced here, so training is defined by `train` (_pqbase.py); a codebook
 exported from a real faiss index can be assigned to `centroids` while the index is empty.
 """
 import numpy as np
 import torch
 
-from . import _ffi, _kmeans, _staging
-from ._coded import DecodableIndex
+from . import _ffi, _pqbase, _staging
+from ._coded import _CodeStore
 from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
 from ._staging import dev_f32 as _dev_f32, dev_u8 as _dev_u8
 
@@ -66,25 +66,13 @@ def pqfs_encode_ref(x, centroids):
         dist[i,m,j] <= min_j' dist[i,m,j'] + 2 * (dsub + 3) * 2^-23 * (|x_m|^2 + max_j |centroids[m,j]|^2):
     the first-order float32 rounding bound of sum (x - c)^2, doubled because two distances are compared.  Two centroids with
     identical bits always resolve to the lower j."""
-    c = _codebooks(centroids).astype(np.float64)
-    M, _, dsub = c.shape
-    x = np.asarray(x, np.float64)
-    if x.ndim != 2 or x.shape[1] != M * dsub:
-        raise ValueError(f"pqfs_encode_ref: x must be [n,{M * dsub}], got {x.shape}")
-    xs = x.reshape(len(x), M, 1, dsub)
-    dist = ((xs - c[None]) ** 2).sum(-1)
-    return dist.argmin(-1).astype(np.uint8), dist
+    return _pqbase.encode_ref("pqfs_encode_ref", x, _codebooks(centroids))
 
 
 def pqfs_tables_ref(q, centroids):
     """The float tables in float64: T[i,m,j] = <slice m of q[i], centroids[m,j]>, [nq,M,16].  The kernel's float32 entry
     (accumulated from zero in ascending coordinate order) lies within (dsub + 2) * 2^-24 * sum_t |q_t * c_t| of it."""
-    c = _codebooks(centroids).astype(np.float64)
-    M, _, dsub = c.shape
-    q = np.asarray(q, np.float64)
-    if q.ndim != 2 or q.shape[1] != M * dsub:
-        raise ValueError(f"pqfs_tables_ref: q must be [nq,{M * dsub}], got {q.shape}")
-    return np.einsum("imt,mjt->imj", q.reshape(len(q), M, dsub), c)
+    return _pqbase.tables_ref("pqfs_tables_ref", q, _codebooks(centroids))
 
 
 def _tables(T):
@@ -174,152 +162,32 @@ def pqfs_score_bound(T):
     return step + 2.0 ** -24 * (7.0 * M * span + (M + 1) * np.abs(lo).sum(axis=1))
 
 
-def _check_shape(d, M, who):
-    if M < 2 or M > _ffi.IVR_PQFS_MAX_M or M % 2:
-        raise ValueError(f"{who}: M={M} odd or outside [2,{_ffi.IVR_PQFS_MAX_M}] (255 * M must fit the 16-bit accumulator)")
-    if d < 1 or d > 65536 or d % M != 0:
-        raise ValueError(f"{who}: d={d} outside [1,65536] or not a multiple of M={M}")
-
-
-class _PQFSStore(_ffi.Handle):
-    """The code rows of a PQFastScanIndex (ivr_pqfs_index_*): uint8 [n,M/2] in, the same bytes out.  The library handle is made by
-    the first call that needs it, so that an index can be made and refuse untrained use where there is no GPU."""
-    _DESTROY = "ivr_pqfs_index_destroy"
-
-    def __init__(self, M, device):
-        self.M, self.code_size = M, M // 2
-        self.device = torch.device("cuda", int(device) if device is not None else
-                                   torch.cuda.current_device() if torch.cuda.is_available() else 0)
-        self._closed = False
-
-    def _call(self, name, *args):
-        if self._h is None:
-            if self._closed:
-                raise RuntimeError("PQFastScanIndex: the index is closed")
-            self._open("ivr_pqfs_index_create", self.device.index, self.M)
-        return super()._call(name, *args)
-
-    def close(self):
-        self._closed = True
-        super().close()
-
-    @property
-    def ntotal(self):
-        return 0 if self._h is None else int(_ffi.call("ivr_pqfs_index_ntotal", self._h))
-
-    def _add_device(self, codes):
-        self._call("ivr_pqfs_index_add", codes, codes.shape[0])
-        torch.cuda.current_stream(self.device).synchronize()  # `codes` may be a temporary
-
-    def _codes_device(self, start=0, n=None):
-        start = int(start)
-        n = self.ntotal - start if n is None else int(n)
-        if start < 0 or n < 0 or start + n > self.ntotal:
-            raise ValueError(f"reconstruct_n: rows [{start},{start + n}) outside [0,{self.ntotal})")
-        out = torch.empty((n, self.code_size), dtype=torch.uint8, device=self.device)
-        if n:
-            self._call("ivr_pqfs_index_get_codes", start, n, out)
-        return out
-
-    def reset(self):
-        if self._h is not None:
-            self._call("ivr_pqfs_index_reset")
-
-
-class PQFastScanIndex(DecodableIndex):
+class PQFastScanIndex(_pqbase.ProductQuantizerIndex):
     """4-bit product-quantisation index (FAISS IndexPQFastScan contract, METRIC_INNER_PRODUCT, nbits = 4) on one GPU.
 
     search(x, k) returns (D float32, I int64): the score pqfs_scan_ref defines under the query's 8-bit tables, descending by its
     integer part, equal integers the lower row first (rows with the same code always tie), unused slots (-FLT_MAX, -1).  add() and
-    search() raise RuntimeError until train() has run or `centroids` has been assigned."""
+    search() raise RuntimeError until train() has run or `centroids` (numpy float32 [M,16,dsub]) has been assigned.  train(x) needs
+    n >= 16 rows; the codebook state, train, sa_decode_device, search_tables and search_device are ProductQuantizerIndex's
+    (_pqbase.py)."""
+    _KSUB, _ENCODE = KSUB, "ivr_pqfs_encode"
 
     def __init__(self, d, M, nbits=4, metric=METRIC_INNER_PRODUCT, device=None):
         self.d, self.M = int(d), int(M)
         if int(nbits) != 4:
             raise ValueError(f"PQFastScanIndex: only nbits=4 is supported, got {nbits}")
         require_inner_product(metric, "PQFastScanIndex")
-        _check_shape(self.d, self.M, "PQFastScanIndex")
-        self.dsub = self.d // self.M
-        self.code_size = self.M // 2
-        self.nbits, self.ksub = 4, KSUB
-        self.metric_type = METRIC_INNER_PRODUCT
-        self.is_trained = False
-        self._index = _PQFSStore(self.M, device)
-        self.device = self._index.device
-        self._centroids = np.zeros((self.M, KSUB, self.dsub), _F)
-        self._cb_dev = None
-
-    # -- attributes ------------------------------------------------------------------------------
-    @property
-    def centroids(self):
-        """numpy float32 [M,16,dsub]: the codebooks.  Assignable while the index is empty, which makes it trained."""
-        return self._centroids
-
-    @centroids.setter
-    def centroids(self, c):
-        self._require_empty("centroids", "codebooks")
-        c = np.asarray(c)
-        if c.shape != self._centroids.shape:
-            raise ValueError(f"centroids expects [{self.M},{KSUB},{self.dsub}], got {c.shape}")
-        self._set_centroids(np.ascontiguousarray(c, dtype=_F))
-
-    def _set_centroids(self, c, dev=None):
-        self._centroids, self._cb_dev = c, dev
-        self.is_trained = True
-
-    def _codebooks_device(self):
-        if self._cb_dev is None:
-            self._cb_dev = torch.from_numpy(self._centroids).to(self.device)
-        return self._cb_dev
-
-    # -- encoding --------------------------------------------------------------------------------
-    def _encode_device(self, t, cb=None):
-        """t: contiguous float32 CUDA tensor [n,d] -> packed codes uint8 CUDA [n,M/2] under the codebooks cb (default: the index's)."""
-        codes = torch.empty((t.shape[0], self.code_size), dtype=torch.uint8, device=self.device)
-        _ffi.call("ivr_pqfs_encode", _ffi.CTX, t, t.shape[0], self.d, self._codebooks_device() if cb is None else cb, self.M, codes,
-                  device=self.device)
-        return codes
+        if self.M < 2 or self.M > _ffi.IVR_PQFS_MAX_M or self.M % 2:
+            raise ValueError(f"PQFastScanIndex: M={self.M} odd or outside [2,{_ffi.IVR_PQFS_MAX_M}] "
+                             "(255 * M must fit the 16-bit accumulator)")
+        self.ksub = KSUB
+        self._setup("PQFastScanIndex", self.d, 4, self.M // 2,
+                    lambda: _CodeStore("ivr_pqfs_index", (self.M,), self.M // 2, "PQFastScanIndex", device))
 
     @staticmethod
-    def _nibbles(packed):
+    def _slice_codes(packed):
         """packed uint8 CUDA [n,M/2] -> int64 CUDA [n,M]: pqfs_unpack_ref."""
         return torch.stack((packed & 15, packed >> 4), dim=2).reshape(packed.shape[0], -1).to(torch.int64)
-
-    def sa_decode_device(self, codes):
-        """float32 CUDA [n,d]: row i is the concatenation of centroids[m, code[i,m]] over m (a gather, no arithmetic)."""
-        self._require_trained("sa_decode")
-        c = self._nibbles(_dev_u8(codes, self.code_size, self.device, "sa_decode"))
-        m = torch.arange(self.M, device=self.device).expand(c.shape[0], -1)
-        return self._codebooks_device()[m, c].reshape(c.shape[0], self.d)
-
-    # -- training --------------------------------------------------------------------------------
-    def train(self, x, niter=25, seed=1234, max_points_per_centroid=256):
-        """Make the M codebooks by k-means on x [n,d], n >= 16 (ValueError otherwise): PQIndex.train with 16 centroids per slice.
-          sample   _kmeans.kmeans_sample(n, 16, max_points_per_centroid, seed): one sample serves all slices, and the initial codebook
-                   of slice m is slice m of its first 16 rows
-          iterate  niter times: assign every sampled row's slices with the encoder (ivr_pqfs_encode: equal distances pick the lower
-                   centroid), order the rows of each slice by code (stable), take the mean of every run (ivr_segment_mean with
-                   spherical=False: fixed summation order, so a seed gives the same bits every time), repair empty clusters
-                   (split_empty_clusters, per slice)."""
-        self._require_empty("train", "codebooks")
-        _staging.check_rows(x, self.d, "train")
-        n = len(x)
-        if n < KSUB:
-            raise ValueError(f"train: {n} training rows for {KSUB} centroids per slice")
-        niter = _kmeans.check_niter(niter)
-        with torch.cuda.device(self.device):
-            xs = _kmeans.sample_rows(x, KSUB, max_points_per_centroid, seed, self.device)
-            cent = xs[:KSUB].reshape(KSUB, self.M, self.dsub).permute(1, 0, 2).contiguous()
-            for _ in range(niter):
-                cent = self._kmeans_step(xs, cent)
-            self._set_centroids(cent.cpu().numpy(), cent)
-
-    def _kmeans_step(self, xs, cent):
-        a = self._nibbles(self._encode_device(xs, cent)).t().contiguous()         # [M, ns]
-        order = torch.argsort(a, dim=1, stable=True)        # one batched sort for all slices
-        out = torch.empty_like(cent)
-        counts = [_kmeans.segment_means(xs[:, m * self.dsub:(m + 1) * self.dsub], a[m], KSUB, out[m], order=order[m]) for m in range(self.M)]
-        return _kmeans.repair_empty_clusters(out, torch.stack(counts).cpu().numpy())
 
     # -- FAISS surface ---------------------------------------------------------------------------
     def add_codes(self, codes):
@@ -383,17 +251,6 @@ class PQFastScanIndex(DecodableIndex):
         staged = _staging.is_staged(ud, U) or _staging.is_staged(sd, scale) or _staging.is_staged(bd, bias)
         _staging.sync_if_staged(staged, self.device)
         return D, I
-
-    def search_tables(self, U, scale, bias, k):
-        """search_tables_device as numpy arrays."""
-        D, I = self.search_tables_device(U, scale, bias, k)
-        return D.cpu().numpy(), I.cpu().numpy()
-
-    def search_device(self, x, k):
-        """search returning CUDA tensors: search_tables_device(*compute_tables_device(x), k), bit for bit."""
-        self._require_trained("search")
-        k = _staging.check_k(k, _ffi.IVR_MAX_K)
-        return self.search_tables_device(*self.compute_tables_device(x), k)
 
 
 def IndexPQFastScan(d, M, nbits=4, metric=METRIC_INNER_PRODUCT):

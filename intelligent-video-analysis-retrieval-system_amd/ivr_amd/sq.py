@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _ffi, _staging
-from ._coded import DecodableIndex
+from ._coded import DecodableIndex, _CodeStore
 from ._faiss import FLT_MAX, METRIC_INNER_PRODUCT, require_inner_product
 from ._staging import dev_f32 as _dev_f32, dev_u8 as _dev_u8
 
@@ -169,51 +169,6 @@ def _dev_i16(t, d, device):
     return t.to(device=device).contiguous()
 
 
-class _SQStore(_ffi.Handle):
-    """The code rows of an SQIndex (ivr_sq_index_*): uint8 [n,d] in, the same bytes out.  The library handle is made by the first
-    call that needs it, so that an index can be made and refuse untrained use where there is no GPU."""
-    _DESTROY = "ivr_sq_index_destroy"
-
-    def __init__(self, d, device):
-        self.d = d
-        self.device = torch.device("cuda", int(device) if device is not None else
-                                   torch.cuda.current_device() if torch.cuda.is_available() else 0)
-        self._closed = False
-
-    def _call(self, name, *args):
-        if self._h is None:
-            if self._closed:
-                raise RuntimeError("SQIndex: the index is closed")
-            self._open("ivr_sq_index_create", self.device.index, self.d)
-        return super()._call(name, *args)
-
-    def close(self):
-        self._closed = True
-        super().close()
-
-    @property
-    def ntotal(self):
-        return 0 if self._h is None else int(_ffi.call("ivr_sq_index_ntotal", self._h))
-
-    def _add_device(self, codes):
-        self._call("ivr_sq_index_add", codes, codes.shape[0])
-        torch.cuda.current_stream(self.device).synchronize()  # `codes` may be a temporary
-
-    def _codes_device(self, start=0, n=None):
-        start = int(start)
-        n = self.ntotal - start if n is None else int(n)
-        if start < 0 or n < 0 or start + n > self.ntotal:
-            raise ValueError(f"reconstruct_n: rows [{start},{start + n}) outside [0,{self.ntotal})")
-        out = torch.empty((n, self.d), dtype=torch.uint8, device=self.device)
-        if n:
-            self._call("ivr_sq_index_get_codes", start, n, out)
-        return out
-
-    def reset(self):
-        if self._h is not None:
-            self._call("ivr_sq_index_reset")
-
-
 class SQIndex(DecodableIndex):
     """Scalar-quantiser index (FAISS IndexScalarQuantizer contract, QT_8bit, METRIC_INNER_PRODUCT) on one GPU.
 
@@ -233,7 +188,7 @@ class SQIndex(DecodableIndex):
         self.is_trained = False
         self._trained = np.zeros(2 * self.d, _F)
         self._dev = None                     # (vmin, vdiff, gain, offset, decode table) on the device, made on first use
-        self._index = _SQStore(self.d, device)
+        self._index = _CodeStore("ivr_sq_index", (self.d,), self.d, "SQIndex", device)
         self.device = self._index.device
 
     # -- attributes ------------------------------------------------------------------------------

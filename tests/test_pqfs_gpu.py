@@ -108,6 +108,18 @@ def test_scan_over_a_store_grown_by_ragged_adds(M):
     idx.close()
 
 
+def test_scan_query_cap_second_chunk_of_one_query():
+    """A chunk holds 4096 queries at most: query 4096 of 4097 is a chunk of its own (c0 = 4096).  100 rows of one-byte codes, tables
+    supplied through search_tables."""
+    rng = np.random.default_rng(21)
+    U, scale, bias = _tables(rng, 4097, 2)
+    codes = _codes(rng, 100, 2)
+    idx = _index(2)
+    idx.add_codes(codes)
+    _same(idx.search_tables(U, scale, bias, 3), pqfs_scan_ref(U, scale, bias, codes, 3))
+    idx.close()
+
+
 def test_nibble_order_is_faiss():
     M = 6
     idx = _index(M)

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Device-code comparison of two source trees:  isa_compare.py PARENT_CSRC THIS_CSRC  (needs hipcc, no GPU).
+"""Device-code comparison of two source trees:  isa_compare.py PARENT_CSRC THIS_CSRC [--merged OLD=NEW ...]  (needs hipcc, no GPU).
 
 Every *.hip of both csrc directories is compiled with its Makefile's flags for the device only and disassembled; addresses are
 stripped, branch targets replaced by a placeholder, and the text is split per kernel symbol.  Kernels are paired by mangled name
 across ALL objects of a tree (a kernel may move between files) and reported as identical / differing / added / lost / emitted by
 more than one object.  Each file of THIS_CSRC is also compiled in full to check that every device kernel has its host-side stub
 (hipcc can drop the host instantiation of a kernel template silently; the kernel is then undefined at load time).
-Exit status 0: every kernel of the parent is present once and identical, none is added, no stub is missing."""
+--merged OLD=NEW (repeatable) declares that this tree folds duplicates: the identifier OLD in a kernel's name (a kernel, or a
+type one is instantiated over) is now NEW.  A lost kernel whose renamed name is a kernel of this tree with the same normalised
+disassembly is MERGED into it, many old names to one new one; a lost kernel without such a partner stays LOST, and an added kernel
+that no lost one merges into stays ADDED.
+Exit status 0: every kernel of the parent is present once and identical or merged, none is added, no stub is missing."""
 import os
 import re
 import subprocess
@@ -79,8 +83,24 @@ def tree(csrc, tmp, full):
     return code, where, [(src, k) for src, _, miss in res for k in miss]
 
 
+def merged_into(lost, added, pc, tc, renames):
+    """{lost kernel: the added kernel it is merged into} under the identifier renames [(old, new)]; an identifier is mangled as its
+    length and its text, wherever it stands in a name (behind another digit only where that ends the unnamed namespace's own name)"""
+    out = {}
+    for k in lost:
+        t = k
+        for old, new in renames:
+            t = re.sub(rf"(?:(?<!\d)|(?<=_GLOBAL__N_1)){len(old)}{re.escape(old)}", f"{len(new)}{new}", t)
+        if t != k and t in added and pc[k] == tc[t]:
+            out[k] = t
+    return out
+
+
 def main():
     parent, this = sys.argv[1], sys.argv[2]
+    renames = [tuple(a.split("=", 1)) for f, a in zip(sys.argv[3::2], sys.argv[4::2]) if f == "--merged"]
+    if len(sys.argv) % 2 == 0 or 2 * len(renames) != len(sys.argv) - 3:
+        sys.exit(__doc__)
     with tempfile.TemporaryDirectory() as tmp:
         pc, pw, _ = tree(parent, os.path.join(tmp, "parent"), False)
         tc, tw, nostub = tree(this, os.path.join(tmp, "this"), True)
@@ -88,6 +108,8 @@ def main():
     diff = sorted(k for k in pc if k in tc and pc[k] != tc[k])
     lost, added = sorted(set(pc) - set(tc)), sorted(set(tc) - set(pc))
     twice = sorted(k for k, w in tw.items() if len(w) > 1)
+    merged = merged_into(lost, added, pc, tc, renames) if renames else {}
+    lost, added = [k for k in lost if k not in merged], [k for k in added if k not in merged.values()]
     for src in sorted({s for w in tw.values() for s in w} | {s for w in pw.values() for s in w}):
         mine = [k for k in tc if src in tw[k]]
         moved = sorted({pw[k][0] for k in mine if k in pw and src not in pw[k]})
@@ -96,11 +118,14 @@ def main():
     for title, ks in (("DIFFERENT", diff), ("LOST", lost), ("ADDED", added), ("EMITTED TWICE", twice)):
         for k in ks:
             print(f"{title}: {k}  [{' '.join(pw.get(k, []))} -> {' '.join(tw.get(k, []))}]")
+    for k, t in sorted(merged.items()):
+        print(f"MERGED: {k}  [{' '.join(pw[k])}]\n     -> {t}  [{' '.join(tw[t])}]  same disassembly")
     for src, k in nostub:
         print(f"NO HOST STUB: {k}  [{src}]")
-    print(f"total: parent {len(pc)} kernels; {len(same)} identical, {len(diff)} different, {len(lost)} lost, {len(added)} added, "
+    print(f"total: parent {len(pc)} kernels; {len(same)} identical, {len(diff)} different, {len(merged)} merged into "
+          f"{len(set(merged.values()))}, {len(lost)} lost, {len(added)} added, "
           f"{len(twice)} emitted twice, {len(nostub)} without host stub")
-    return 0 if not (diff or lost or added or twice or nostub) and len(same) == len(pc) else 1
+    return 0 if not (diff or lost or added or twice or nostub) and len(same) + len(merged) == len(pc) else 1
 
 
 if __name__ == "__main__":
