@@ -458,6 +458,38 @@ int ivr_index_range_search_sequences(ivr_index *idx, const float *q /*DEV [T,d]*
                                      int64_t *lims /*DEV [T-L+2]*/, float *D /*DEV [cap]*/, int64_t *I /*DEV [cap]*/, int64_t cap,
                                      ivr_stream stream);
 
+/* ---- frame clustering: DBSCAN over the stored rows of the flat index ----------------------------------
+ * Which stored frames are the same shot?  The reference's AdvancedKeyframeExtractor.cluster_similar_frames
+ * (filter_research_update.py:113-134: sklearn DBSCAN on the precomputed 1 - cosine matrix) without the N x N matrix: a tiled self-join
+ * of the storage, three passes, nothing stored per pair.
+ *   score     S[q, r] = the float32 inner product ivr_index_search reports for (query = stored row q, stored row r), to the bit
+ *   edge      rows i < j are neighbours iff both lie in one segment and (float)1 - S[j, i] <= eps: one rounded float32 subtraction, <=
+ *             as sklearn's test.  Only S[j, i] with the HIGHER row as the query is read, so adjacency is symmetric by construction;
+ *             S[i, i] is never read
+ *   segments  seg_off: DEV int64 [nseg + 1], ascending, or NULL (then nseg is not read and the whole index is one segment), as for
+ *             clip search: empty runs are allowed, rows outside [seg_off[0], seg_off[nseg]) belong to nothing (not core, label -1)
+ *   core      row i is core iff 1 + (its neighbours) >= min_samples: a row always counts itself (sklearn reads the diagonal distance
+ *             instead, which differs for a zero row or an eps below about 1e-6)
+ *   cluster   a connected component of the core rows under edges; its root is its lowest row.  A non-core row with a core neighbour
+ *             takes the cluster with the lowest root among its core neighbours (sklearn's result: it grows cluster 0 completely
+ *             before it starts cluster 1); every other non-core row is noise
+ *   labels    DEV int32 [ntotal]: the rank of the cluster's root among the roots of the row's own segment, ascending from 0 (numbering
+ *             restarts in every segment), -1 for noise.  core: DEV uint8 [ntotal], 1 for a core row.  nclusters: DEV int32
+ *             [max(nseg, 1)], the clusters of each segment (offsets clipped to [0, ntotal])
+ * Positional like ivr_index_rescore, on plain and id-mapped indexes alike: labels are indexed by row.  eps negative or NaN,
+ * min_samples < 1, ntotal >= 2^31 and NULL handles or outputs are IVR_ERR_INVALID; an empty index succeeds and writes nothing.
+ * Every result is an integer built from integer atomic adds and minima: the same bits on every run.  Cost: three float32 self-join
+ * passes over the pairs i < j of each segment.  Scratch on the index, grow-only: six 4-byte words per row.  Eight launches on the
+ * caller's stream, no host synchronisation once the scratch has grown (a call that grows it allocates); not graph-capturable then. */
+int ivr_index_dbscan(ivr_index *idx, float eps, int min_samples, const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg,
+                     int32_t *labels /*DEV [ntotal]*/, uint8_t *core /*DEV [ntotal]*/, int32_t *nclusters /*DEV [max(nseg,1)]*/, ivr_stream stream);
+/* The representative of each run of rows (filter_research_update.py:136-155): best[s] = the row of rows[seg_off[s] .. seg_off[s + 1])
+ * (row-major float32 [n,d]; seg_off ascending, clipped to [0, n]) with the largest cosine to centers[s], as its position in `rows`, and
+ * score[s] = that cosine, computed with the arithmetic of ivr_rowwise_cosine, to the bit (a zero norm counts as 1).  Equal cosines go to
+ * the lower row, a NaN cosine is never the best, an empty run gives -1 / -FLT_MAX.  One workgroup per run. */
+int ivr_segment_best_cosine(ivr_ctx *ctx, const float *rows /*DEV [n,d]*/, int64_t n, const int64_t *seg_off /*DEV [nseg+1]*/, int nseg, int d,
+                            const float *centers /*DEV [nseg,d]*/, int64_t *best /*DEV [nseg]*/, float *score /*DEV [nseg]*/, ivr_stream stream);
+
 /* ---- binary codes (faiss IndexBinaryFlat, and the sign-bit encoder of IndexLSH) --------------------------
  * Stands in for faiss.IndexLSH(dimension, 256), one of the index types of _create_index (core.py:1198-1230): a row is stored as
  * nbits sign bits (32 bytes at 256 bits, where the flat index stores 2-4.6 KB) and ranked by Hamming distance.

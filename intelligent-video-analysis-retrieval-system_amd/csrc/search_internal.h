@@ -270,6 +270,8 @@ struct ivr_index {
     DevBuf<uint64_t> seq_keys;       // DEV [windows of a chunk][N - L + 1]: (ordered window score, ~start row), 0 for a start that is no candidate
     DevBuf<int64_t> seq_off;         // DEV [windows of a chunk][4096-key blocks of a stretch]: hits of each block, then their output positions
     DevBuf<int64_t> seq_total;       // DEV [1]: the running total of the range call, carried from chunk to chunk
+    // frame clustering (ivr_index_dbscan, cluster.hip); grow-only
+    DevBuf<int32_t> cl_words;        // DEV [6][ntotal + 1 rounded up to 64]: segment start, degree, parent, root, border root, root prefix of each row
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

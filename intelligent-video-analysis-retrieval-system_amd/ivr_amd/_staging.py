@@ -93,6 +93,20 @@ def check_window(L, T, lmax, what):
     return L
 
 
+def check_dbscan(eps, min_samples, what):
+    """The parameters of a DBSCAN call: eps a number >= 0 (not NaN), min_samples an integer >= 1 -> (float eps, int min_samples)."""
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{what}: eps must be a number, got {type(eps).__name__}")
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError(f"{what}: eps={eps} is negative or NaN")
+    if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)):
+        raise ValueError(f"{what}: min_samples must be an integer, got {type(min_samples).__name__}")
+    if min_samples < 1 or min_samples >= 2**31:
+        raise ValueError(f"{what}: min_samples={min_samples} outside [1,2^31)")
+    return eps, int(min_samples)
+
+
 def alloc_DI(nq, k, device, dtype=torch.float32):
     """The (D, I) pair of a search: D `dtype` [nq,k], I int64 [nq,k]."""
     return torch.empty((nq, k), dtype=dtype, device=device), torch.empty((nq, k), dtype=torch.int64, device=device)
