@@ -490,6 +490,32 @@ int ivr_index_dbscan(ivr_index *idx, float eps, int min_samples, const int64_t *
 int ivr_segment_best_cosine(ivr_ctx *ctx, const float *rows /*DEV [n,d]*/, int64_t n, const int64_t *seg_off /*DEV [nseg+1]*/, int nseg, int d,
                             const float *centers /*DEV [nseg,d]*/, int64_t *best /*DEV [nseg]*/, float *score /*DEV [nseg]*/, ivr_stream stream);
 
+/* ---- neighbour graph: segmented exact kNN self-join of the stored rows of the flat index --------------
+ * For every stored row its k best OTHER rows of the same segment, optionally above a score: the reference's
+ * MetadataManager._build_similarity_relationships (core.py:3493-3531: per folder the full cosine matrix, every row sorted, the top 10
+ * others with cosine > 0.7) for all folders in one call, without a matrix and without copying a row into a query buffer.
+ *   score       S[j, i] = the float32 inner product ivr_index_search / ivr_index_rescore report for (query = stored row j, stored row
+ *               i), to the bit; every ordered pair is scored with its own j as the query
+ *   segments    seg_off: DEV int64 [nseg + 1], ascending, or NULL (then nseg is not read and the whole index is one segment), as for
+ *               ivr_index_dbscan: empty runs are allowed, rows outside [seg_off[0], seg_off[nseg]) have no neighbours and are nobody's
+ *   candidates  of row j: the rows i != j of j's segment with i < ntotal whose S[j, i] is not NaN and, when threshold is not -inf,
+ *               S[j, i] > threshold (strict, as the reference's > 0.7).  The row itself is left out by its number, not by its place in
+ *               the order (the reference drops the first entry of its sort, which among duplicate frames may be another row)
+ *   order       score descending, equal scores the lower row
+ *   D           DEV float32 [ntotal][k], unused slots -FLT_MAX (a score of -0.0 is reported as +0.0, as by every top-k here)
+ *   I           DEV int64 [ntotal][k]: ROW numbers, on plain and id-mapped indexes alike (as the labels of ivr_index_dbscan), unused -1
+ *   count       DEV int32 [ntotal]: the used slots of each row
+ * 1 <= k <= IVR_KNN_MAX_K; a NaN threshold, ntotal >= 2^31 and NULL handles or outputs are IVR_ERR_INVALID; an empty index succeeds
+ * and writes nothing.  The candidates of a row are totally ordered by unique keys: the same bits on every run and stream.  Cost: one
+ * float32 self-join pass over the ordered pairs of each segment.  Scratch on the index, grow-only: two words per row and at most 2^25
+ * keys (256 MiB) of partial lists, an index too large for that is walked in chunks of rows.  One launch, then two per chunk, on the
+ * caller's stream; no host synchronisation once the scratch has grown (a call that grows it allocates); not graph-capturable then. */
+#define IVR_KNN_MAX_K 64
+int ivr_knn_max_k(void);
+int ivr_knn_piece_rows(void);   /* stored rows one workgroup's piece of a walk covers at least: tests size their cases from it */
+int ivr_index_knn_graph(ivr_index *idx, int k, const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, float threshold,
+                        float *D /*DEV [ntotal][k]*/, int64_t *I /*DEV [ntotal][k]*/, int32_t *count /*DEV [ntotal]*/, ivr_stream stream);
+
 /* ---- binary codes (faiss IndexBinaryFlat, and the sign-bit encoder of IndexLSH) --------------------------
  * Stands in for faiss.IndexLSH(dimension, 256), one of the index types of _create_index (core.py:1198-1230): a row is stored as
  * nbits sign bits (32 bytes at 256 bits, where the flat index stores 2-4.6 KB) and ranked by Hamming distance.

@@ -272,6 +272,9 @@ struct ivr_index {
     DevBuf<int64_t> seq_total;       // DEV [1]: the running total of the range call, carried from chunk to chunk
     // frame clustering (ivr_index_dbscan, cluster.hip); grow-only
     DevBuf<int32_t> cl_words;        // DEV [6][ntotal + 1 rounded up to 64]: segment start, degree, parent, root, border root, root prefix of each row
+    // neighbour graph (ivr_index_knn_graph, knn.hip); grow-only
+    DevBuf<int32_t> kn_seg;          // DEV [2][ntotal rounded up to 64]: start and end of each row's segment
+    DevBuf<uint64_t> kn_keys;        // DEV [query blocks of a chunk][parts of a walk][64][k]: the partial lists, at most 2^25 keys
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

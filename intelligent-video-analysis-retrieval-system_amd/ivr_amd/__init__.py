@@ -1,6 +1,6 @@
 """ivr_amd: the HIP-backed pieces of the retrieval system.  The submodules are imported by name (ivr_amd.index, ivr_amd.tower, ...);
 the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index, the product-quantisation (8- and 4-bit codes) and scalar-quantisation indexes
-and the clip search and the frame clustering are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
+and the clip search, the frame clustering and the neighbour graph are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
 _IVF = ("IVFFlatIndex", "IndexIVFFlat", "SearchParametersIVF", "METRIC_INNER_PRODUCT", "METRIC_L2")
 _BINARY = ("BinaryFlatIndex", "IndexBinaryFlat", "IndexLSH", "lsh_rotation")
 _GRAPH = ("GraphFlatIndex", "IndexHNSWFlat", "SearchParametersHNSW", "graph_prune_ref", "graph_link_ref", "graph_build_ref",
@@ -16,7 +16,8 @@ _TEMPORAL = ("TemporalAnalyzer", "sequence_search", "sequence_search_device", "s
              "sequence_scores_ref", "sequence_search_ref", "sequence_range_ref")
 _CLUSTER = ("dbscan", "dbscan_device", "dbscan_ref", "cluster_members", "select_representatives", "representatives_ref",
             "cluster_similar_frames", "select_representative_frame")
-__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _PQFS + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL + _CLUSTER)
+_NEIGHBORS = ("knn_graph", "knn_graph_device", "knn_graph_ref", "similarity_graphs", "build_similarity_relationships")
+__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _PQFS + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL + _CLUSTER + _NEIGHBORS)
 
 
 def __getattr__(name):
@@ -53,4 +54,7 @@ def __getattr__(name):
     if name in _CLUSTER:
         from . import cluster
         return getattr(cluster, name)
+    if name in _NEIGHBORS:
+        from . import neighbors
+        return getattr(neighbors, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -20,6 +20,7 @@ IVR_PQ_MAX_M = 128
 IVR_PQFS_MAX_M = 256
 IVR_SQ_MAX_D = 1024
 IVR_SEQ_MAX_LEN = 64
+IVR_KNN_MAX_K = 64
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -111,6 +112,9 @@ _SIGS = {
     "ivr_index_range_search_sequences": (_i, [_p, _p, _i, _i, _p, _i, _f, _i, _p, _p, _p, _i64, _p]),
     "ivr_index_dbscan": (_i, [_p, _f, _i, _p, _i, _p, _p, _p, _p]),
     "ivr_segment_best_cosine": (_i, [_p, _p, _i64, _p, _i, _i, _p, _p, _p, _p]),
+    "ivr_knn_max_k": (_i, []),
+    "ivr_knn_piece_rows": (_i, []),
+    "ivr_index_knn_graph": (_i, [_p, _i, _p, _i, _f, _p, _p, _p, _p]),
     "ivr_bin_index_create": (_i, [_p, _i, _i64, C.POINTER(_p)]),
     "ivr_bin_index_destroy": (_i, [_p]),
     "ivr_bin_index_reset": (_i, [_p]),
@@ -184,7 +188,7 @@ _VALUE = frozenset(("ivr_api_version", "ivr_last_error", "ivr_preprocess_scratch
                     "ivr_index_dim", "ivr_index_capacity", "ivr_index_has_ids", "ivr_bin_index_ntotal", "ivr_bin_index_block_rows",
                     "ivr_graph_max_ef", "ivr_graph_max_cand", "ivr_graph_ntotal", "ivr_frame_quality_scratch_bytes",
                     "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries", "ivr_ivfsq_ntotal",
-                    "ivr_pqfs_pass_queries", "ivr_pqfs_index_ntotal"))
+                    "ivr_pqfs_pass_queries", "ivr_pqfs_index_ntotal", "ivr_knn_max_k", "ivr_knn_piece_rows"))
 # the slot of the ivr_stream argument (the last one wherever there is one): call() fills it when the caller leaves it out
 _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_release_stream_scratch", "ivr_preprocess", "ivr_tower_encode_image", "ivr_tower_encode_text", "ivr_tower_debug_hidden",
@@ -193,7 +197,7 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_index_search_filtered", "ivr_index_range_search_filtered", "ivr_index_remove_ids", "ivr_index_add_with_ids",
     "ivr_index_get_ids", "ivr_index_find_ids", "ivr_index_gather", "ivr_index_scatter", "ivr_index_search_reconstruct",
     "ivr_index_search_lists", "ivr_segment_mean", "ivr_index_rescore", "ivr_index_search_sequences",
-    "ivr_index_range_search_sequences", "ivr_index_dbscan", "ivr_segment_best_cosine", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
+    "ivr_index_range_search_sequences", "ivr_index_dbscan", "ivr_segment_best_cosine", "ivr_index_knn_graph", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
     "ivr_sign_encode", "ivr_pq_encode", "ivr_pq_tables", "ivr_bin_index_search_pq", "ivr_ivfpq_set_lists", "ivr_ivfpq_get_codes",
     "ivr_ivfpq_search", "ivr_ivfsq_set_lists", "ivr_ivfsq_get_codes", "ivr_ivfsq_search", "ivr_sq_encode", "ivr_sq_query", "ivr_sq_index_add",
     "ivr_sq_index_get_codes", "ivr_sq_index_search", "ivr_pqfs_encode", "ivr_pqfs_tables", "ivr_pqfs_quantize", "ivr_pqfs_index_add",

@@ -107,6 +107,23 @@ def check_dbscan(eps, min_samples, what):
     return eps, int(min_samples)
 
 
+def check_knn(k, threshold, kmax, what):
+    """The parameters of a neighbour-graph call: k an integer in [1, kmax], threshold a number that is not NaN, or None -> (int k,
+    float threshold, -inf for None)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"{what}: k must be an integer, got {type(k).__name__}")
+    if k < 1 or k > kmax:
+        raise ValueError(f"{what}: k={k} outside [1,{kmax}]")
+    if threshold is None:
+        return int(k), float("-inf")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{what}: threshold must be a number, got {type(threshold).__name__}")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError(f"{what}: threshold={threshold} is NaN")
+    return int(k), threshold
+
+
 def alloc_DI(nq, k, device, dtype=torch.float32):
     """The (D, I) pair of a search: D `dtype` [nq,k], I int64 [nq,k]."""
     return torch.empty((nq, k), dtype=dtype, device=device), torch.empty((nq, k), dtype=torch.int64, device=device)
