@@ -2,9 +2,9 @@
 // reference's AdvancedKeyframeExtractor.cluster_similar_frames / select_representative_frame (filter_research_update.py:113-155)
 // without the N x N distance matrix and without sklearn.  DESIGN.md section 4, "frame clustering".
 //
-// Score S[j, i] = <stored row j as the query, stored row i>, accumulated by mfma_chunk4 in ascending chunk order from a zero
-// accumulator (search_internal.h), so it has the bits ivr_index_search and ivr_index_rescore report for that pair.  The float32
-// storage tiles have the layout of the tiled query buffer, so a stored 16-row tile is the query operand as it lies.
+// Score S[j, i] = <stored row j as the query, stored row i> with the bits ivr_index_search and ivr_index_rescore report for that
+// pair.  The segment bounds, the query block in LDS and the scoring of a stored tile are the self-join frame's (self_join.h); here are
+// the walk of the triangle, the three integer epilogues and the union-find.
 //   edge     rows i < j of one segment with 1.0f - S[j, i] <= eps (one rounded subtraction; only the higher row is ever the query)
 //   core     1 + edges at the row >= min_samples, and the row lies in a segment
 //   cluster  a connected component of the core rows; its root is its lowest row
@@ -12,9 +12,9 @@
 //   label    the rank of the cluster's root among the roots of its own segment, -1 for noise
 //
 // Launches, all on the caller's stream and without a host round trip:
-//   cl_init      per row: seg_lo (the start of its segment, row + 1 outside every segment), deg = 0, parent = row, broot = none
+//   sj_bounds    per row: seg_lo (the start of its segment, row + 1 outside every segment); deg is cleared by a memset beside it
 //   cl_score<COUNT>   the tiled self-join, every accepted pair adds 1 to deg of both rows
-//   cl_core      per row: the core byte
+//   cl_core      per row: the core byte, and parent = row, broot = none for the two passes behind it
 //   cl_score<UNITE>   accepted pairs of two core rows: union-find over parent, written only through atomicMin
 //   cl_flatten   root[i] = find(i), into its own array
 //   cl_score<BORDER>  accepted pairs of one core and one non-core row: broot[non-core] = min(broot, root[core])
@@ -24,44 +24,25 @@
 #include <climits>
 
 #include "ivr_common.h"
-#include "search_internal.h"
+#include "self_join.h"
 
 namespace {
 
 enum { CL_COUNT = 0, CL_UNITE = 1, CL_BORDER = 2 };
 constexpr int kNoRoot = INT_MAX;
-// Measured on 20,000 / 100,000 x 512 rows as one segment (whole call): 4 waves and unsplit walks 18.0 / 277 ms, 4 waves and pieces of
-// 128 tiles 12.6 / 281 ms, 8 waves and pieces of 64 / 128 / 256 tiles 9.5 / 9.7 / 10.8 ms and 219 / 217 / 216 ms
-constexpr int kClWaves = 8;                 // waves of a score workgroup: two per SIMD, so that one's tile loads overlap the other's MFMAs
-constexpr int kClSplit = 128;               // stored 16-row tiles a score workgroup streams: the walk of one query block is cut into equal pieces
-constexpr int kClMaxPieces = 65535;         // grid.y; an index of more than 65535 kClSplit tiles gets longer pieces
+constexpr int kClMaxPieces = 65535;         // grid.y; an index of more than 65535 kSjSplit tiles gets longer pieces
 
-// The per-row words of a call: one block of x->cl_words, each array rounded up to a multiple of 64 words
+// The per-row words of a call: the segment starts of the self-join frame, and one block of x->cl_words, each array rounded up to a
+// multiple of 64 words
 struct ClWords {
-    int *seg_lo, *deg, *parent, *root, *broot, *prefix;     // prefix is [n + 1]
+    const int *seg_lo;
+    int *deg, *parent, *root, *broot, *prefix;      // prefix is [n + 1]
     static int64_t stride(int64_t n) { return ivr_round_up(n + 1, 64); }
-    ClWords(int *p, int64_t n) {
+    ClWords(const int *seg, int *p, int64_t n) {
         const int64_t s = stride(n);
-        seg_lo = p, deg = p + s, parent = p + 2 * s, root = p + 3 * s, broot = p + 4 * s, prefix = p + 5 * s;
+        seg_lo = seg, deg = p, parent = p + s, root = p + 2 * s, broot = p + 3 * s, prefix = p + 4 * s;
     }
 };
-
-__global__ __launch_bounds__(256) void cl_init_kernel(int n, const int64_t *__restrict__ seg_off, int nseg, ClWords w) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    int lo = 0;
-    if (seg_off) {
-        lo = j + 1;                                  // outside every segment: no i < j passes i >= seg_lo[j]
-        if (seg_off[0] <= j) {
-            const int s = ivr_last_le(seg_off, nseg + 1, j);
-            if (s < nseg) lo = (int)max(seg_off[s], (int64_t)0);       // seg_off[s] <= j < seg_off[s + 1]
-        }
-    }
-    w.seg_lo[j] = lo;
-    w.deg[j] = 0;
-    w.parent[j] = j;
-    w.broot[j] = kNoRoot;
-}
 
 __device__ __forceinline__ int cl_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -91,12 +72,9 @@ __device__ __forceinline__ void cl_unite(int *parent, int a, int b) {
 }
 
 struct ClScore {
-    const float4 *data;          // the float32 tiles of the storage
-    int dp4;
-    int qt;                      // 16-row tiles a workgroup holds as the query operand: ivr_index::qt_max()
+    SjArgs j;                    // query blocks of ivr_index::qt_max() tiles
     int ntiles;                  // 16-row tiles that hold stored rows
-    int split;                   // stored tiles per piece of a walk: kClSplit, more when that would be more than kClMaxPieces pieces
-    int n;                       // stored rows
+    int split;                   // stored tiles per piece of a walk: kSjSplit, more when that would be more than kClMaxPieces pieces
     float eps;
     ClWords w;
     const uint8_t *core;         // UNITE, BORDER
@@ -112,58 +90,33 @@ struct ClScore {
 // Every tile read lies inside the storage's allocation, whose capacity is a multiple of 64 rows >= ntotal; every word written belongs
 // to a row < n, because an accepted entry has i < j < n.
 template <int EPI>
-__global__ __launch_bounds__(64 * kClWaves) void cl_score_kernel(ClScore a) {
+__global__ __launch_bounds__(64 * kSjWaves) void cl_score_kernel(ClScore a) {
     extern __shared__ __attribute__((aligned(16))) float4 qs[];
-    const int per_tile = a.dp4 * 16, kchunks = a.dp4 >> 2;
-    const int tb0 = (int)blockIdx.x * a.qt, nq = min(a.qt, a.ntiles - tb0);
-    const int ta0 = max(min(a.w.seg_lo[tb0 * 16], tb0 * 16) >> 4, (int)blockIdx.y * a.split);
+    const int tb0 = (int)blockIdx.x * a.j.qt, nq = min(a.j.qt, a.ntiles - tb0);
+    const int ta0 = max(min(a.j.seg_lo[tb0 * 16], tb0 * 16) >> 4, (int)blockIdx.y * a.split);
     const int ta1 = min(tb0 + nq, (int)std::min<int64_t>(((int64_t)blockIdx.y + 1) * a.split, INT_MAX));
     if (ta0 >= ta1) return;          // the whole workgroup: nothing staged, no barrier reached
-    const float4 *qt = a.data + (int64_t)tb0 * per_tile;
-    for (int i = threadIdx.x; i < nq * per_tile; i += blockDim.x) qs[i] = qt[i];
+    sj_stage(a.j, tb0, nq, qs);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // this lane's column of each query tile: row j, accepted rows i in [ilo, j); an empty range for a column that is no stored row
-    int jq[4], ilo[4], cj[4];
+    // this lane's column of each query tile: row col.jq, accepted rows i in [col.lo, col.jq); col.lo is INT_MAX for a column that is no stored row
+    const SjCols col = sj_columns(a.j, tb0, nq);
+    int cj[4];
     bool corej[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        jq[q] = (tb0 + q) * 16 + (lane & 15);
-        const bool valid = q < nq && jq[q] < a.n;
-        ilo[q] = valid ? a.w.seg_lo[jq[q]] : INT_MAX;
-        corej[q] = EPI != CL_COUNT && valid && a.core[jq[q]];
+        corej[q] = EPI != CL_COUNT && col.lo[q] != INT_MAX && a.core[col.jq[q]];
         cj[q] = 0;
     }
-    for (int ta = ta0 + wave; ta < ta1; ta += kClWaves) {
-        const float4 *at = a.data + (int64_t)ta * per_tile + lane;
+    for (int ta = ta0 + wave; ta < ta1; ta += kSjWaves) {
         f32x4 acc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        int kc = 0;
-        for (; kc + 8 <= kchunks; kc += 8) {
-            float4 av[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) av[u] = at[(kc + u) * 64];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (q < nq) mfma_chunk4(acc[q], av[u], qs[q * per_tile + (kc + u) * 64 + lane]);
-            }
-        }
-        for (; kc < kchunks; ++kc) {
-            const float4 av = at[kc * 64];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (q < nq) mfma_chunk4(acc[q], av, qs[q * per_tile + kc * 64 + lane]);
-        }
-        // acc[q][r] = S[j, i] for j = jq[q], i = i0 + r
+        sj_score_tile(a.j, qs, nq, ta, acc);
         const int i0 = ta * 16 + (lane >> 4) * 4;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             bool ok[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ok[r] = i0 + r >= ilo[q] && i0 + r < jq[q] && 1.0f - acc[q][r] <= a.eps;
+            for (int r = 0; r < 4; ++r) ok[r] = i0 + r >= col.lo[q] && i0 + r < col.jq[q] && 1.0f - acc[q][r] <= a.eps;
             if (!__any(ok[0] || ok[1] || ok[2] || ok[3])) continue;
             if (EPI == CL_COUNT) {
                 // deg[j]: summed in the lane over the whole walk, reduced once at the end.  deg[i]: the 16 lanes of a quad row hold
@@ -182,10 +135,10 @@ __global__ __launch_bounds__(64 * kClWaves) void cl_score_kernel(ClScore a) {
                     const int i = i0 + r;
                     const bool corei = a.core[i];
                     if (EPI == CL_UNITE) {
-                        if (corei && corej[q]) cl_unite(a.w.parent, i, jq[q]);
+                        if (corei && corej[q]) cl_unite(a.w.parent, i, col.jq[q]);
                     } else if (corei != corej[q]) {
-                        if (corei) atomicMin(a.w.broot + jq[q], a.w.root[i]);
-                        else atomicMin(a.w.broot + i, a.w.root[jq[q]]);
+                        if (corei) atomicMin(a.w.broot + col.jq[q], a.w.root[i]);
+                        else atomicMin(a.w.broot + i, a.w.root[col.jq[q]]);
                     }
                 }
             }
@@ -197,14 +150,18 @@ __global__ __launch_bounds__(64 * kClWaves) void cl_score_kernel(ClScore a) {
             int c = cj[q];
             c += __shfl_xor(c, 16, 64);
             c += __shfl_xor(c, 32, 64);
-            if (lane < 16 && c) atomicAdd(a.w.deg + jq[q], c);      // c > 0: column jq[q] accepted something, so it is a stored row
+            if (lane < 16 && c) atomicAdd(a.w.deg + col.jq[q], c);      // c > 0: column col.jq[q] accepted something, so it is a stored row
         }
     }
 }
 
+// the core byte of every row, and the start of the two passes behind it: every row its own root, no border root
 __global__ __launch_bounds__(256) void cl_core_kernel(int n, int min_samples, ClWords w, uint8_t *__restrict__ core) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) core[i] = w.seg_lo[i] <= i && (int64_t)w.deg[i] + 1 >= min_samples;
+    if (i >= n) return;
+    core[i] = w.seg_lo[i] <= i && (int64_t)w.deg[i] + 1 >= min_samples;
+    w.parent[i] = i;
+    w.broot[i] = kNoRoot;
 }
 
 __global__ __launch_bounds__(256) void cl_flatten_kernel(int n, ClWords w) {
@@ -297,12 +254,12 @@ __global__ __launch_bounds__(256) void segment_best_cosine_kernel(const float *_
 
 template <int EPI>
 int cl_launch_score(const char *name, ivr_index *x, const ClScore &a, hipStream_t s) {
-    const size_t lds = (size_t)a.qt * 16 * x->dp * 4;
+    const size_t lds = (size_t)a.j.qt * 16 * x->dp * 4;
     const int rc = ivr_func_max_lds(reinterpret_cast<const void *>(cl_score_kernel<EPI>), (int)lds);
     if (rc != IVR_OK) return rc;
     IvrProf prof(name, s, (double)x->ntotal * x->ntotal * x->dp);
-    hipLaunchKernelGGL(cl_score_kernel<EPI>, dim3((unsigned)ivr_ceil_div(a.ntiles, a.qt), (unsigned)ivr_ceil_div(a.ntiles, a.split)),
-                       dim3(64 * kClWaves), lds, s, a);
+    hipLaunchKernelGGL(cl_score_kernel<EPI>, dim3((unsigned)ivr_ceil_div(a.ntiles, a.j.qt), (unsigned)ivr_ceil_div(a.ntiles, a.split)),
+                       dim3(64 * kSjWaves), lds, s, a);
     IVR_LAUNCH_CHECK();
     return IVR_OK;
 }
@@ -323,15 +280,16 @@ int ivr_index_dbscan(ivr_index *x, float eps, int min_samples, const int64_t *se
     if (x->ntotal == 0) return IVR_OK;
     IVR_HIP(hipSetDevice(x->ctx->device));
     const int n = (int)x->ntotal;
-    int rc = ivr_reserve({{&x->cl_words, (size_t)6 * ClWords::stride(n) * 4}});
+    int rc = ivr_reserve({{&x->cl_words, (size_t)5 * ClWords::stride(n) * 4}});
     if (rc != IVR_OK) return rc;
-    const ClWords w(x->cl_words, n);
+    SjArgs j;
+    rc = sj_prepare(x, x->qt_max(), seg_off, nseg, s, j);
+    if (rc != IVR_OK) return rc;
+    const ClWords w(j.seg_lo, x->cl_words, n);
     const unsigned nblk = (unsigned)ivr_ceil_div(n, 256);
-    hipLaunchKernelGGL(cl_init_kernel, dim3(nblk), dim3(256), 0, s, n, seg_off, nseg, w);
-    IVR_LAUNCH_CHECK();
+    IVR_HIP(hipMemsetAsync(w.deg, 0, (size_t)n * 4, s));
     const int ntiles = (int)ivr_ceil_div(n, 16);
-    const ClScore sc{reinterpret_cast<const float4 *>(x->data), x->dp4, x->qt_max(), ntiles, std::max(kClSplit, (int)ivr_ceil_div(ntiles, kClMaxPieces)),
-                     n, eps, w, core};
+    const ClScore sc{j, ntiles, std::max(kSjSplit, (int)ivr_ceil_div(ntiles, kClMaxPieces)), eps, w, core};
     rc = cl_launch_score<CL_COUNT>("cluster_count", x, sc, s);
     if (rc != IVR_OK) return rc;
     hipLaunchKernelGGL(cl_core_kernel, dim3(nblk), dim3(256), 0, s, n, min_samples, w, core);

@@ -3,68 +3,40 @@
 // cosine matrix, a sort of every row, the top 10 others with cosine > 0.7) for all folders in one call and without a matrix.  DESIGN.md
 // section 4, "neighbour graph".
 //
-// Score S[j, i] = <stored row j as the query, stored row i>, accumulated by mfma_chunk4 in ascending chunk order from a zero
-// accumulator (search_internal.h), so it has the bits ivr_index_search and ivr_index_rescore report for that pair.  As in cluster.hip a
-// stored 16-row tile is the query operand as it lies; unlike there every ORDERED pair is scored with its own j as the query (the full
-// square of a segment, not the triangle), so nothing rests on S[j, i] and S[i, j] having the same bits.
+// Score S[j, i] = <stored row j as the query, stored row i> with the bits ivr_index_search and ivr_index_rescore report for that
+// pair.  The segment bounds, the query block in LDS and the scoring of a stored tile are the self-join frame's (self_join.h), shared
+// with cluster.hip; here are the walk of the full square in parts, the lists in LDS and the merge.  Unlike cluster.hip's triangle every
+// ORDERED pair is scored with its own j as the query, so nothing rests on S[j, i] and S[i, j] having the same bits.
 //   candidates of j   the rows i != j with seg_lo[j] <= i < seg_hi[j] (so i < ntotal), S[j, i] not NaN, and S[j, i] > threshold when
 //                     one is given (-inf: none)
 //   order             ivr_key(S[j, i], i): score descending, equal scores the lower row.  The keys of one row are unique
 //
 // Launches, all on the caller's stream and without a host round trip:
-//   kn_init     per row: seg_lo, seg_hi (the run of seg_off that holds it, clipped to [0, n); empty for a row outside every segment)
+//   sj_bounds   per row: seg_lo, seg_hi (the run of seg_off that holds it, clipped to [0, n); empty for a row outside every segment)
 //   kn_score    per chunk of query blocks: the tiled self-join; workgroup (b, y) keeps the best k keys of part y of block b's walk per
 //               query column in LDS and writes them to the scratch
 //   kn_merge    per chunk: the best k of a row's parts -> D, I, count
 // A query block is 16 qt rows (qt tiles, as many as the LDS holds beside the lists); its walk runs from the tile of the lowest segment
-// start among its rows to the tile of the highest segment end, and is cut into at most kKnMaxParts equal parts of at least kKnSplit
+// start among its rows to the tile of the highest segment end, and is cut into at most kKnMaxParts equal parts of at least kSjSplit
 // tiles.  Scratch: query blocks of a chunk x kKnMaxParts x 64 x k keys, at most kKnScratchKeys; a larger index takes several chunks.
 #include <climits>
 
 #include "ivr_common.h"
-#include "search_internal.h"
+#include "self_join.h"
 
 namespace {
 
-// Measured on 20,000 / 100,000 x 512 rows as one segment and 1M rows in 2,000 folders (whole call, k = 10, threshold 0.7 / none):
-// as below 6.56 / 12.6, 151 / 216 and 15.8 / 26.2 ms; 4 waves 8.59 / 14.5, 199 / 263 and 19.3 / 29.5 ms; parts of >= 512 tiles
-// 6.92 / 9.53, 150 / 204 and 15.9 / 26.4 ms; <= 32 parts 6.58 / 12.7, 152 / 261 and 17.0 / 27.8 ms
-constexpr int kKnWaves = 8;                     // waves of a score workgroup, as cluster.hip's kClWaves
-constexpr int kKnSplit = 128;                   // least stored 16-row tiles of one part of a walk (cluster.hip's kClSplit)
 constexpr int kKnMaxParts = 16;                 // grid.y: parts of one query block's walk, each with its own partial lists
 constexpr int64_t kKnScratchKeys = 1ll << 25;   // keys of the partial lists of one chunk of query blocks: 256 MiB
 
 struct KnArgs {
-    const float4 *data;          // the float32 tiles of the storage
-    int dp4;
-    int qt;                      // 16-row tiles of a query block
-    int n;                       // stored rows
+    SjArgs j;                    // query blocks of kn_qt() tiles
     int k;
     int parts;                   // grid.y of the score launch
     float thr;
     int has_thr;
-    const int *seg_lo, *seg_hi;  // [n]
     uint64_t *keys;              // [query blocks of a chunk][parts][64][k]
 };
-
-__global__ __launch_bounds__(256) void kn_init_kernel(int n, const int64_t *__restrict__ seg_off, int nseg, int *__restrict__ seg_lo,
-                                                      int *__restrict__ seg_hi) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    int lo = 0, hi = n;
-    if (seg_off) {
-        lo = hi = 0;                                 // outside every segment: no candidates, and nobody's candidate
-        if (seg_off[0] <= j) {
-            const int s = ivr_last_le(seg_off, nseg + 1, j);
-            if (s < nseg) {                          // seg_off[s] <= j < seg_off[s + 1]
-                lo = (int)max(seg_off[s], (int64_t)0);
-                hi = (int)min(seg_off[s + 1], (int64_t)n);
-            }
-        }
-    }
-    seg_lo[j] = lo;
-    seg_hi[j] = hi;
-}
 
 // The walk of the query block of `nrows` <= 64 rows from row0 on: tiles [t0, t0 + tiles) hold every candidate of its rows; it is cut
 // into nparts <= parts pieces of len tiles (nparts = 0: no row of the block lies in a segment).  Called by whole waves; every wave of
@@ -75,8 +47,8 @@ struct KnWalk {
 __device__ __forceinline__ KnWalk kn_walk(const KnArgs &a, int row0, int nrows) {
     const int lane = threadIdx.x & 63, j = row0 + lane;
     int lo = INT_MAX, hi = 0;
-    if (lane < nrows && j < a.n) {
-        const int l = a.seg_lo[j], h = a.seg_hi[j];
+    if (lane < nrows && j < a.j.n) {
+        const int l = a.j.seg_lo[j], h = a.j.seg_hi[j];
         if (l < h) lo = l, hi = h;
     }
 #pragma unroll
@@ -89,7 +61,7 @@ __device__ __forceinline__ KnWalk kn_walk(const KnArgs &a, int row0, int nrows) 
         w.t0 = lo >> 4;
         w.t1 = (hi + 15) >> 4;                       // hi <= n: inside the tiles that hold stored rows
         const int tiles = w.t1 - w.t0;
-        w.len = max(kKnSplit, (tiles + a.parts - 1) / a.parts);
+        w.len = max(kSjSplit, (tiles + a.parts - 1) / a.parts);
         w.nparts = (tiles + w.len - 1) / w.len;
     }
     return w;
@@ -103,60 +75,31 @@ __device__ __forceinline__ KnWalk kn_walk(const KnArgs &a, int row0, int nrows) 
 // the lane (q, c) owns column 16 q + c, collects the survivors of that column from the four quad rows of its wave by shuffles and
 // inserts them.  So a list is written by one lane at a time, a stale threshold is only ever too low, and since the candidates of a
 // column have unique keys its final list is the best k of the part whatever the order of the insertions.
-__global__ __launch_bounds__(64 * kKnWaves) void kn_score_kernel(KnArgs a, int blk0) {
+__global__ __launch_bounds__(64 * kSjWaves) void kn_score_kernel(KnArgs a, int blk0) {
     extern __shared__ __attribute__((aligned(16))) float4 qs[];
-    const int per_tile = a.dp4 * 16, kchunks = a.dp4 >> 2, k = a.k, ncol = a.qt * 16;
-    const int ntiles = (a.n + 15) >> 4;
-    const int tb0 = (blk0 + (int)blockIdx.x) * a.qt, nq = min(a.qt, ntiles - tb0);
+    const int k = a.k, ncol = a.j.qt * 16;
+    const int ntiles = (a.j.n + 15) >> 4;
+    const int tb0 = (blk0 + (int)blockIdx.x) * a.j.qt, nq = min(a.j.qt, ntiles - tb0);
     const KnWalk w = kn_walk(a, tb0 * 16, nq * 16);
     if ((int)blockIdx.y >= w.nparts) return;         // the whole workgroup: nothing staged, no barrier reached, nothing written
     const int pa0 = w.t0 + (int)blockIdx.y * w.len, pa1 = min(w.t1, pa0 + w.len);
-    uint64_t *list = reinterpret_cast<uint64_t *>(qs + a.qt * per_tile);          // [k][ncol]
+    uint64_t *list = reinterpret_cast<uint64_t *>(qs + a.j.qt * a.j.dp4 * 16);    // [k][ncol]
     unsigned *flag = reinterpret_cast<unsigned *>(list + k * ncol);               // [3]: the waves with survivors in round r, at r % 3
-    const float4 *qtile = a.data + (int64_t)tb0 * per_tile;
-    for (int i = threadIdx.x; i < nq * per_tile; i += blockDim.x) qs[i] = qtile[i];
+    sj_stage(a.j, tb0, nq, qs);
     for (int i = threadIdx.x; i < k * ncol; i += blockDim.x) list[i] = 0;
     if (threadIdx.x < 3) flag[threadIdx.x] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 4, c = lane & 15;
-    // this lane's column of each query tile: row j, candidate rows [ilo, ihi) except j; an empty range for a column that is no stored row
-    int jq[4], ilo[4], ihi[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        jq[q] = (tb0 + q) * 16 + c;
-        const bool valid = q < nq && jq[q] < a.n;
-        ilo[q] = valid ? a.seg_lo[jq[q]] : 0;
-        ihi[q] = valid ? a.seg_hi[jq[q]] : 0;
-    }
+    // this lane's column of each query tile: row col.jq, candidate rows [col.lo, col.hi) except col.jq
+    const SjCols col = sj_columns(a.j, tb0, nq);
     int round = 0;
-    for (int t0 = pa0; t0 < pa1; t0 += kKnWaves, ++round) {
+    for (int t0 = pa0; t0 < pa1; t0 += kSjWaves, ++round) {
         const int ta = t0 + wave;
         uint64_t key[4][4];
         bool mine = false;
         if (ta < pa1) {                              // wave-uniform
-            const float4 *at = a.data + (int64_t)ta * per_tile + lane;
             f32x4 acc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-            int kc = 0;
-            for (; kc + 8 <= kchunks; kc += 8) {
-                float4 av[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) av[u] = at[(kc + u) * 64];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (q < nq) mfma_chunk4(acc[q], av[u], qs[q * per_tile + (kc + u) * 64 + lane]);
-                }
-            }
-            for (; kc < kchunks; ++kc) {
-                const float4 av = at[kc * 64];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (q < nq) mfma_chunk4(acc[q], av, qs[q * per_tile + kc * 64 + lane]);
-            }
-            // acc[q][r] = S[j, i] for j = jq[q], i = i0 + r
+            sj_score_tile(a.j, qs, nq, ta, acc);
             const int i0 = ta * 16 + h * 4;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -165,7 +108,7 @@ __global__ __launch_bounds__(64 * kKnWaves) void kn_score_kernel(KnArgs a, int b
                 for (int r = 0; r < 4; ++r) {
                     const int i = i0 + r;
                     const float s = acc[q][r];
-                    const bool ok = i >= ilo[q] && i < ihi[q] && i != jq[q] && s == s && (!a.has_thr || s > a.thr);
+                    const bool ok = i >= col.lo[q] && i < col.hi[q] && i != col.jq[q] && s == s && (!a.has_thr || s > a.thr);
                     const uint64_t x = ivr_key(s, (uint32_t)i);
                     key[q][r] = ok && x > low ? x : 0;
                     mine = mine || key[q][r] != 0;
@@ -182,7 +125,7 @@ __global__ __launch_bounds__(64 * kKnWaves) void kn_score_kernel(KnArgs a, int b
         __syncthreads();
         const unsigned turns = flag[round % 3];
         if (threadIdx.x == 0) flag[(round + 2) % 3] = 0;         // read last in the round before, set next in the round after the next
-        for (int v = 0; v < kKnWaves; ++v) {
+        for (int v = 0; v < kSjWaves; ++v) {
             if (!((turns >> v) & 1u)) continue;                  // the same word in every thread: the barrier below is uniform
             if (v == wave) {
 #pragma unroll
@@ -245,7 +188,7 @@ __device__ __forceinline__ int kn_above(const uint64_t *l, int k, uint64_t x) {
 __global__ __launch_bounds__(256) void kn_merge_kernel(KnArgs a, int blk0, float *__restrict__ D, int64_t *__restrict__ I,
                                                        int32_t *__restrict__ count) {
     extern __shared__ __attribute__((aligned(16))) uint64_t ml[];                 // [4 waves][parts][k]
-    const int k = a.k, row0 = (blk0 + (int)blockIdx.x) * a.qt * 16, nrows = min(a.qt * 16, a.n - row0);
+    const int k = a.k, row0 = (blk0 + (int)blockIdx.x) * a.j.qt * 16, nrows = min(a.j.qt * 16, a.j.n - row0);
     const KnWalk w = kn_walk(a, row0, nrows);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint64_t *l = ml + wave * a.parts * k;
@@ -296,7 +239,7 @@ extern "C" {
 
 int ivr_knn_max_k(void) { return IVR_KNN_MAX_K; }
 
-int ivr_knn_piece_rows(void) { return kKnSplit * 16; }
+int ivr_knn_piece_rows(void) { return kSjSplit * 16; }
 
 int ivr_index_knn_graph(ivr_index *x, int k, const int64_t *seg_off, int nseg, float threshold, float *D, int64_t *I, int32_t *count,
                         ivr_stream stream) {
@@ -312,24 +255,22 @@ int ivr_index_knn_graph(ivr_index *x, int k, const int64_t *seg_off, int nseg, f
     const int n = (int)x->ntotal, ntiles = (int)ivr_ceil_div(n, 16);
     const int qt = kn_qt(x->dp, k);
     const int nblocks = (int)ivr_ceil_div(ntiles, qt);
-    const int parts = (int)std::min<int64_t>(kKnMaxParts, ivr_ceil_div(ntiles, kKnSplit));
+    const int parts = (int)std::min<int64_t>(kKnMaxParts, ivr_ceil_div(ntiles, kSjSplit));
     const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(nblocks, kKnScratchKeys / ((int64_t)parts * 64 * k)));
-    const int64_t stride = ivr_round_up(n, 64);
-    int rc = ivr_reserve({{&x->kn_seg, (size_t)2 * stride * 4}, {&x->kn_keys, (size_t)chunk * parts * 64 * k * 8}});
+    int rc = ivr_reserve({{&x->kn_keys, (size_t)chunk * parts * 64 * k * 8}});
     if (rc != IVR_OK) return rc;
     const size_t lds = kn_lds(qt, x->dp, k), mlds = (size_t)4 * parts * k * 8;
     rc = ivr_func_max_lds(reinterpret_cast<const void *>(kn_score_kernel), (int)lds);
     if (rc != IVR_OK) return rc;
-    int *seg_lo = x->kn_seg, *seg_hi = seg_lo + stride;
-    hipLaunchKernelGGL(kn_init_kernel, dim3((unsigned)ivr_ceil_div(n, 256)), dim3(256), 0, s, n, seg_off, nseg, seg_lo, seg_hi);
-    IVR_LAUNCH_CHECK();
-    const KnArgs a{reinterpret_cast<const float4 *>(x->data), x->dp4, qt, n, k, parts, threshold, threshold != -INFINITY, seg_lo, seg_hi,
-                   x->kn_keys};
+    SjArgs j;
+    rc = sj_prepare(x, qt, seg_off, nseg, s, j);
+    if (rc != IVR_OK) return rc;
+    const KnArgs a{j, k, parts, threshold, threshold != -INFINITY, x->kn_keys};
     for (int b0 = 0; b0 < nblocks; b0 += chunk) {
         const unsigned nb = (unsigned)std::min(chunk, nblocks - b0);
         {
             IvrProf prof("knn_score", s, (double)nb * qt * 16 * n * x->dp);
-            hipLaunchKernelGGL(kn_score_kernel, dim3(nb, (unsigned)parts), dim3(64 * kKnWaves), lds, s, a, b0);
+            hipLaunchKernelGGL(kn_score_kernel, dim3(nb, (unsigned)parts), dim3(64 * kSjWaves), lds, s, a, b0);
             IVR_LAUNCH_CHECK();
         }
         hipLaunchKernelGGL(kn_merge_kernel, dim3(nb), dim3(256), mlds, s, a, b0, D, I, count);

@@ -39,28 +39,11 @@ __device__ __forceinline__ void score_group(const float4 *__restrict__ a, int64_
     for (int q = 0; q < QT; ++q)
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[q][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // one row tile at a time, eight 16-float chunks per trip: 8 independent 1 KiB loads = 8 KiB CONTIGUOUS in flight per wave
-    // before the MFMAs (a tile is [d/4][16 rows][4 floats], so consecutive chunks of one tile are adjacent in memory).
-    // Per accumulator the K order is ascending whatever the trip shape, so scan and re-score stay bit-identical.
+    // one row tile at a time (stream_tile, search_internal.h): per accumulator the K order is ascending, so scan and re-score stay
+    // bit-identical
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const float4 *at = a + t * tile_stride;
-        int kc = 0;
-        for (; kc + 8 <= kchunks; kc += 8) {
-            float4 av[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) av[u] = at[(kc + u) * 64];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int q = 0; q < QT; ++q) mfma_chunk4(acc[q][t], av[u], bload(q, kc + u));
-        }
-        for (; kc < kchunks; ++kc) {
-            const float4 av = at[kc * 64];
-#pragma unroll
-            for (int q = 0; q < QT; ++q) mfma_chunk4(acc[q][t], av, bload(q, kc));
-        }
-    }
+    for (int t = 0; t < 4; ++t)
+        stream_tile<QT>(a + t * tile_stride, kchunks, [&](int q, int kc, const float4 &av) { mfma_chunk4(acc[q][t], av, bload(q, kc)); });
 }
 
 // pass 1.  gmax layout: [16*QT queries][mstride groups]
@@ -406,18 +389,7 @@ __global__ __launch_bounds__(256) void rescore_groups_kernel(const float *__rest
     const float4 *a = reinterpret_cast<const float4 *>(data) + ((int64_t)g * kSplit + t) * per_tile + lane;
     uint32_t mbyte = 0;
     if constexpr (MASK) mbyte = row_mask_fetch(rm..., (int64_t)g * kRows + t * 16);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int kc = 0;
-    for (; kc + 16 <= kchunks; kc += 16) {
-        float4 av[16], bv[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) av[u] = a[(kc + u) * 64];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) bv[u] = b[(kc + u) * 64];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) mfma_chunk4(acc, av[u], bv[u]);
-    }
-    for (; kc < kchunks; ++kc) mfma_chunk4(acc, a[kc * 64], b[kc * 64]);
+    const f32x4 acc = pair_score(a, b, kchunks);
     uint64_t mw = 0;
     if constexpr (MASK) mw = row_mask_word(rm..., (int64_t)g * kRows + t * 16, mbyte);
     if ((lane & 15) == (qs & 15)) {

@@ -1,12 +1,22 @@
-// The one internal header of the flat index: search_index.hip (the index object and its storage), search.hip (group-maximum scans and
-// the top-k driver), search_range.hip (range search), search_scanq.hip (the large-query-batch candidate scan) and search_ids.hip (the
-// id table of an id-mapped index).  It holds what more
-// than one of them needs: the index object with the plan of a search, the view a search scans, the row mask of a filtered search, and
-// the launchers that are defined in one file and called from another.  search_rows.hip (gather / scatter of rows by position) uses it
-// too, and so do search_binary.hip, search_pq.hip and search_ivfpq.hip for the loaders of the binary-code layout at its end (the
-// coded-index structs themselves are in search_coded.h).  It also holds the device
-// helpers that every search file spells the same way: ivr_key, ivr_wave_incl_scan, ivr_last_le, ivr_comp and probe_valid, and
-// ProbeTables, the probe tables of the inverted-list scans (search_lists.hip).  Not part of the C ABI.
+// The one internal header of the flat index.  Not part of the C ABI.  What it holds, in order:
+//   plan constants, ScanQArgs     the sizes the flat search files agree on; one launch of the large-batch candidate scan
+//   RowMask, with_mask            the allowed rows of a filtered search, and the plain-or-masked choice of a kernel instantiation
+//   the float32 score             mfma_chunk4 (one 16-float chunk), stream_tile (one stored 16-row tile against query tiles staged
+//                                 in LDS) and pair_score (one tile against one query column in global memory).  Together they are
+//                                 THE accumulation order of every float32 score: ascending chunks, x y z w inside a chunk, zero
+//                                 accumulator.  Every exact kernel goes through them, which is why a (query, row) pair has the same
+//                                 bits wherever it is scored ("one accumulation order")
+//   small device helpers          ivr_load_quad, ivr_key, ivr_wave_incl_scan, ivr_last_le, ivr_comp, probe_valid
+//   DevMem, DevBuf, ivr_reserve   grow-only device buffers
+//   ProbeTables                   the probe tables of the inverted-list scans (defined in search_lists.hip)
+//   ivr_index                     the index object: storage, every workspace, and the plan of a search
+//   View, with_view               the rows one search scans
+//   launchers                     defined in one file and called from another
+//   bin_load_row, bin_with_words  the loaders of the binary-code layout (search_binary.hip, search_pq.hip, search_ivfpq.hip; the
+//                                 coded-index structs themselves are in search_coded.h)
+// Users: search_index.hip (the index object and its storage), search.hip (group-maximum scans and the top-k driver), search_range.hip,
+// search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_ivf.hip and the other list scans, and
+// through self_join.h cluster.hip and knn.hip.
 #pragma once
 #include "ivr_common.h"
 
@@ -83,13 +93,61 @@ void with_mask(const M *mask, F &&f) {
 }
 
 // One 16-float chunk of a float32 score: lane l holds floats 4 (l >> 4) .. + 3 of the chunk for row / query (l & 15) in a and b.
-// Every float32 score of the index (scan, re-score, range search) is accumulated by this sequence in ascending chunk order, which
-// is what makes them bit-identical to each other.
+// Every float32 score of the index is accumulated by this sequence in ascending chunk order from a zero accumulator, through one of
+// the two loops below; that is what makes them bit-identical to each other.
 __device__ __forceinline__ void mfma_chunk4(f32x4 &acc, const float4 &a, const float4 &b) {
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+}
+
+// One stored 16-row tile streamed against QT query tiles: at is this lane's float4 of the tile's chunk 0 (a tile is [d/4][16 rows]
+// [4 floats], so its chunks are 64 float4 = 1 KiB apart and adjacent in memory), f(q, kc, av) accumulates chunk kc, whose A operand
+// is av, into query tile q (mfma_chunk4 with the caller's B operand, usually read from LDS).  Eight chunks per trip, the eight
+// independent 1 KiB loads = 8 KiB contiguous in flight per wave before the first MFMA, then single chunks.  Per accumulator the
+// chunk order is ascending whatever the trip shape.
+template <int QT, typename F>
+__device__ __forceinline__ void stream_tile(const float4 *__restrict__ at, int kchunks, F &&f) {
+    int kc = 0;
+    for (; kc + 8 <= kchunks; kc += 8) {
+        float4 av[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) av[u] = at[(kc + u) * 64];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int q = 0; q < QT; ++q) f(q, kc + u, av[u]);
+    }
+    for (; kc < kchunks; ++kc) {
+        const float4 av = at[kc * 64];
+#pragma unroll
+        for (int q = 0; q < QT; ++q) f(q, kc, av);
+    }
+}
+
+// One 16-row tile against one query column, both operands in global memory: a and b are this lane's float4 of chunk 0 of the row tile
+// and of the tiled query tile (chunks 64 float4 apart in both).  pair_chunks: U chunks from kc0 on, every load of both operands
+// issued before the first MFMA.  pair_score: the whole row, 16 chunks at a time, then MID at a time when MID > 1, then single chunks.
+template <int U>
+__device__ __forceinline__ void pair_chunks(f32x4 &acc, const float4 *__restrict__ a, const float4 *__restrict__ b, int kc0) {
+    float4 av[U], bv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) av[u] = a[(kc0 + u) * 64];
+#pragma unroll
+    for (int u = 0; u < U; ++u) bv[u] = b[(kc0 + u) * 64];
+#pragma unroll
+    for (int u = 0; u < U; ++u) mfma_chunk4(acc, av[u], bv[u]);
+}
+template <int MID = 1>
+__device__ __forceinline__ f32x4 pair_score(const float4 *__restrict__ a, const float4 *__restrict__ b, int kchunks) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    int kc = 0;
+    for (; kc + 16 <= kchunks; kc += 16) pair_chunks<16>(acc, a, b, kc);
+    if constexpr (MID > 1)
+        for (; kc + MID <= kchunks; kc += MID) pair_chunks<MID>(acc, a, b, kc);
+    for (; kc < kchunks; ++kc) pair_chunks<1>(acc, a, b, kc);
+    return acc;
 }
 
 // One quad of a row-major float32 row for the tiled layouts: floats k0 .. k0 + 3 of `row`, zero past d.  vec: one 16-byte load (the
@@ -270,10 +328,11 @@ struct ivr_index {
     DevBuf<uint64_t> seq_keys;       // DEV [windows of a chunk][N - L + 1]: (ordered window score, ~start row), 0 for a start that is no candidate
     DevBuf<int64_t> seq_off;         // DEV [windows of a chunk][4096-key blocks of a stretch]: hits of each block, then their output positions
     DevBuf<int64_t> seq_total;       // DEV [1]: the running total of the range call, carried from chunk to chunk
+    // the self-joins (self_join.h); grow-only
+    DevBuf<int32_t> sj_seg;          // DEV [2][ntotal rounded up to 64]: start and end of each row's segment
     // frame clustering (ivr_index_dbscan, cluster.hip); grow-only
-    DevBuf<int32_t> cl_words;        // DEV [6][ntotal + 1 rounded up to 64]: segment start, degree, parent, root, border root, root prefix of each row
+    DevBuf<int32_t> cl_words;        // DEV [5][ntotal + 1 rounded up to 64]: degree, parent, root, border root, root prefix of each row
     // neighbour graph (ivr_index_knn_graph, knn.hip); grow-only
-    DevBuf<int32_t> kn_seg;          // DEV [2][ntotal rounded up to 64]: start and end of each row's segment
     DevBuf<uint64_t> kn_keys;        // DEV [query blocks of a chunk][parts of a walk][64][k]: the partial lists, at most 2^25 keys
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.

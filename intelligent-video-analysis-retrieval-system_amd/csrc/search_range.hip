@@ -80,26 +80,9 @@ __device__ __forceinline__ void range_pair_prefix(const uint32_t *__restrict__ n
     }
 }
 
-// One 16-row tile against the query column (lane & 15) of a tiled query tile with rescore_groups_kernel's accumulator sequence
-// (ascending K, x y z w per chunk): each score is bit-identical to the one ivr_index_search reports for that row.
-__device__ __forceinline__ f32x4 range_score_tile(const float4 *__restrict__ a, const float4 *__restrict__ b, int kchunks) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int kc = 0;
-    for (; kc + 16 <= kchunks; kc += 16) {
-        float4 av[16], bv[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) av[u] = a[(kc + u) * 64];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) bv[u] = b[(kc + u) * 64];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) mfma_chunk4(acc, av[u], bv[u]);
-    }
-    for (; kc < kchunks; ++kc) mfma_chunk4(acc, a[kc * 64], b[kc * 64]);
-    return acc;
-}
-
-// The 64 rows of group g against query q of the chunk (qtile = the chunk's first query tile).  In the lanes with (lane & 15) ==
-// (q & 15), acc[t][r] = score of row 64 g + 16 t + 4 (lane >> 4) + r.  Returns the hit mask (bit i: row 64 g + i exists and scores
+// The 64 rows of group g against query q of the chunk (qtile = the chunk's first query tile), scored by pair_score (search_internal.h)
+// as rescore_groups_kernel scores them: each score is bit-identical to the one ivr_index_search reports for that row.  In the lanes
+// with (lane & 15) == (q & 15), acc[t][r] = score of row 64 g + 16 t + 4 (lane >> 4) + r.  Returns the hit mask (bit i: row 64 g + i exists and scores
 // > radius), the same in every lane.
 // MASK: rows that are not allowed are never hits.
 template <bool MASK = false, typename... M>
@@ -114,7 +97,7 @@ __device__ __forceinline__ uint64_t range_group_scores(const float *__restrict__
     uint64_t m = 0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        acc[t] = range_score_tile(reinterpret_cast<const float4 *>(data) + ((int64_t)g * 4 + t) * per_tile + lane, b, kchunks);
+        acc[t] = pair_score(reinterpret_cast<const float4 *>(data) + ((int64_t)g * 4 + t) * per_tile + lane, b, kchunks);
         if constexpr (!MASK) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

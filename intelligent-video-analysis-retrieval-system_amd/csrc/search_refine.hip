@@ -32,22 +32,11 @@ struct RefineScore {
     float *D_all;                // [nq][kc] or NULL
 };
 
-// U chunks with every load issued before the first MFMA.  a: this lane's quad of chunk 0 of its candidate row, b: of the query
-template <int U>
-__device__ __forceinline__ void refine_chunks(f32x4 &acc, const float4 *__restrict__ a, const float4 *__restrict__ b, int kc0) {
-    float4 av[U], bv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) av[u] = a[(kc0 + u) * 64];
-#pragma unroll
-    for (int u = 0; u < U; ++u) bv[u] = b[(kc0 + u) * 64];
-#pragma unroll
-    for (int u = 0; u < U; ++u) mfma_chunk4(acc, av[u], bv[u]);
-}
-
 // Wave w: query w / groups, candidates 16 g .. 16 g + 15 of its list, g = w % groups.  Lane l holds quad l >> 4 of every chunk of the
-// row of candidate 16 g + (l & 15) (the A operand) and the same quad of the query (B: the query in all 16 columns), so after the
-// chunk loop acc[x] of lane l is the score of candidate 16 g + 4 (l >> 4) + x in every column; column 0 writes.  An absent lane
-// reads row 0 and its score is dropped.  The host launches nothing on an empty index.
+// row of candidate 16 g + (l & 15) (the A operand) and the same quad of the query (B: the query in all 16 columns), so after
+// pair_score (search_internal.h; pa, pb: this lane's quad of chunk 0 of its candidate row and of the query; trips of 16, 4, then
+// single chunks) acc[x] of lane l is the score of candidate 16 g + 4 (l >> 4) + x in every column; column 0 writes.  An absent
+// lane reads row 0 and its score is dropped.  The host launches nothing on an empty index.
 __global__ __launch_bounds__(256) void refine_score_kernel(RefineScore a) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -62,11 +51,7 @@ __global__ __launch_bounds__(256) void refine_score_kernel(RefineScore a) {
     const int per_tile = a.dp4 * 16, kchunks = a.dp4 >> 2;
     const float4 *pa = a.data + (r >> 4) * per_tile + qd * 16 + (r & 15);
     const float4 *pb = a.qtiled + (q >> 4) * per_tile + qd * 16 + (q & 15);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int kc = 0;
-    for (; kc + 16 <= kchunks; kc += 16) refine_chunks<16>(acc, pa, pb, kc);
-    for (; kc + 4 <= kchunks; kc += 4) refine_chunks<4>(acc, pa, pb, kc);
-    for (; kc < kchunks; ++kc) refine_chunks<1>(acc, pa, pb, kc);
+    const f32x4 acc = pair_score<4>(pa, pb, kchunks);
     uint32_t rows[4];                                            // the rows of candidates 16 g + 4 qd + x, from a lane that holds them
 #pragma unroll
     for (int x = 0; x < 4; ++x) rows[x] = __shfl(row32, 4 * qd + x, 64);

@@ -58,15 +58,7 @@ __global__ __launch_bounds__(256) void seq_score_kernel(SeqScore a) {
     for (int64_t t = t0 + wave; t < t1; t += 4) {
         const float4 *at = a.data + t * per_tile + lane;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        int kc = 0;
-        for (; kc + 8 <= kchunks; kc += 8) {
-            float4 av[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) av[u] = at[(kc + u) * 64];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) mfma_chunk4(acc, av[u], qs[(kc + u) * 64 + lane]);
-        }
-        for (; kc < kchunks; ++kc) mfma_chunk4(acc, at[kc * 64], qs[kc * 64 + lane]);
+        stream_tile<1>(at, kchunks, [&](int, int kc, const float4 &av) { mfma_chunk4(acc, av, qs[kc * 64 + lane]); });
         // acc[r] = <row 16 t + 4 (lane >> 4) + r, frame (lane & 15) of the tile>
         *reinterpret_cast<f32x4 *>(out + t * 16) = acc;
     }

@@ -142,9 +142,12 @@ def int_tensor(a, name, verb="be", np_dtype=None):
     return a
 
 
-def segment_offsets(seg_off, device, what):
-    """Segment offsets (integers [nseg+1], nseg >= 1, ascending) -> (contiguous int64 tensor on `device`, is_staged).  The order is
-    checked on a host array; a CUDA tensor is taken as it is (no host sync)."""
+def segments(seg_off, device, what):
+    """The segment argument of a library call: offsets (integers [nseg+1], nseg >= 1, ascending) or None -> (contiguous int64
+    tensor on `device`, is_staged, nseg), (None, False, 0) for None.  The order is checked on a host array; a CUDA tensor is taken
+    as it is (no host sync)."""
+    if seg_off is None:
+        return None, False, 0
     t = int_tensor(seg_off, f"{what}: seg_off")
     if t.dim() != 1 or t.shape[0] < 2:
         raise ValueError(f"{what}: seg_off must be [nseg+1] with nseg >= 1, got {tuple(t.shape)}")
@@ -154,7 +157,21 @@ def segment_offsets(seg_off, device, what):
             i = int(bad[0])
             raise ValueError(f"{what}: seg_off must ascend, got seg_off[{i}]={int(t[i])} > seg_off[{i + 1}]={int(t[i + 1])}")
     d = t.to(device=device, dtype=torch.int64).contiguous()
-    return d, is_staged(d, seg_off)
+    return d, is_staged(d, seg_off), len(d) - 1
+
+
+def segment_bounds(n, seg_off):
+    """The definition of the segments in numpy: (lo, hi) int64 [n], the run [lo, hi) of seg_off that holds row j, clipped to [0, n);
+    the empty range lo == hi == j + 1 for a row outside every run; [0, n) for every row without seg_off.  lo alone is the start array
+    of DBSCAN: it ascends with the row, and lo[j] <= j exactly for the rows inside a segment."""
+    j = np.arange(n, dtype=np.int64)
+    if seg_off is None:
+        return np.zeros(n, np.int64), np.full(n, n, np.int64)
+    off = np.asarray(seg_off).astype(np.int64).reshape(-1)
+    s = np.searchsorted(off, j, side="right") - 1                  # the last offset <= j: with empty segments the run that holds j
+    inside = (s >= 0) & (s < len(off) - 1)
+    s = np.clip(s, 0, len(off) - 2)
+    return np.where(inside, np.maximum(off[s], 0), j + 1), np.where(inside, np.minimum(off[s + 1], n), j + 1)
 
 
 def check_entries(t, n, name):

@@ -37,17 +37,6 @@ MIN_CLUSTER_SIZE = 2        # filter_research_update.py: MIN_CLUSTER_SIZE
 
 
 # -- the definition in numpy ---------------------------------------------------------------------------------------------------
-def _segment_starts(n, seg_off):
-    """int64 [n]: the start of the segment that holds row j, j + 1 for a row outside every segment."""
-    j = np.arange(n, dtype=np.int64)
-    if seg_off is None:
-        return np.zeros(n, np.int64)
-    off = np.asarray(seg_off).astype(np.int64).reshape(-1)
-    s = np.searchsorted(off, j, side="right") - 1                  # the last offset <= j: with empty segments the run that holds j
-    inside = (s >= 0) & (s < len(off) - 1)
-    return np.where(inside, np.maximum(off[np.clip(s, 0, len(off) - 1)], 0), j + 1)
-
-
 def dbscan_ref(S, eps, min_samples, seg_off=None):
     """S float32 [N,N] scores (S[q, r]: query row q, stored row r) -> (labels int32 [N], core uint8 [N], nclusters int32
     [max(nseg, 1)]): the definition of the module docstring."""
@@ -56,7 +45,7 @@ def dbscan_ref(S, eps, min_samples, seg_off=None):
         raise ValueError(f"dbscan_ref: S {S.shape} must be [N,N]")
     eps, min_samples = _staging.check_dbscan(eps, min_samples, "dbscan_ref")
     n = S.shape[0]
-    lo = _segment_starts(n, seg_off)
+    lo, _ = _staging.segment_bounds(n, seg_off)                    # the start of row j's segment, j + 1 outside every segment
     adj = np.zeros((n, n), bool)
     for j in range(n):
         if lo[j] < j:
@@ -177,10 +166,7 @@ def dbscan_device(index, eps, min_samples=2, seg_off=None):
     if not isinstance(index, FlatIPIndex):
         raise ValueError(f"dbscan: index must be a FlatIPIndex, got {type(index).__name__}")
     eps, min_samples = _staging.check_dbscan(eps, min_samples, "dbscan")
-    seg, staged, nseg = None, False, 0
-    if seg_off is not None:
-        seg, staged = _staging.segment_offsets(seg_off, index.device, "dbscan")
-        nseg = len(seg) - 1
+    seg, staged, nseg = _staging.segments(seg_off, index.device, "dbscan")
     n = index.ntotal
     labels = torch.empty(max(n, 1), dtype=torch.int32, device=index.device)            # never a NULL pointer, even for an empty index
     core = torch.empty(max(n, 1), dtype=torch.uint8, device=index.device)

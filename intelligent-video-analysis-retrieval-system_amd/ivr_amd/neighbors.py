@@ -39,20 +39,6 @@ def knn_max_k():
 
 
 # -- the definition in numpy ---------------------------------------------------------------------------------------------------
-def _segment_bounds(n, seg_off):
-    """(lo, hi) int64 [n]: the run [lo, hi) of seg_off that holds row j, clipped to [0, n); lo == hi for a row outside every run."""
-    j = np.arange(n, dtype=np.int64)
-    if seg_off is None:
-        return np.zeros(n, np.int64), np.full(n, n, np.int64)
-    off = np.asarray(seg_off).astype(np.int64).reshape(-1)
-    s = np.searchsorted(off, j, side="right") - 1                  # the last offset <= j: with empty segments the run that holds j
-    inside = (s >= 0) & (s < len(off) - 1)
-    s = np.clip(s, 0, len(off) - 2)
-    lo = np.where(inside, np.maximum(off[s], 0), 0)
-    hi = np.where(inside, np.minimum(off[s + 1], n), 0)
-    return lo, hi
-
-
 def knn_graph_ref(S, k, seg_off=None, threshold=None):
     """S float32 [N,N] scores (S[j, i]: query row j, stored row i) -> (D float32 [N,k], I int64 [N,k], count int32 [N]): the
     definition of the module docstring."""
@@ -61,7 +47,7 @@ def knn_graph_ref(S, k, seg_off=None, threshold=None):
         raise ValueError(f"knn_graph_ref: S {S.shape} must be [N,N]")
     n = S.shape[0]
     k, threshold = _staging.check_knn(k, threshold, _ffi.IVR_KNN_MAX_K, "knn_graph_ref")
-    lo, hi = _segment_bounds(n, seg_off)
+    lo, hi = _staging.segment_bounds(n, seg_off)
     D = np.full((n, k), NEG_FLT_MAX, np.float32)
     I = np.full((n, k), -1, np.int64)
     count = np.zeros(n, np.int32)
@@ -88,10 +74,7 @@ def knn_graph_device(index, k, seg_off=None, threshold=None):
     if not isinstance(index, FlatIPIndex):
         raise ValueError(f"knn_graph: index must be a FlatIPIndex, got {type(index).__name__}")
     k, threshold = _staging.check_knn(k, threshold, knn_max_k(), "knn_graph")
-    seg, staged, nseg = None, False, 0
-    if seg_off is not None:
-        seg, staged = _staging.segment_offsets(seg_off, index.device, "knn_graph")
-        nseg = len(seg) - 1
+    seg, staged, nseg = _staging.segments(seg_off, index.device, "knn_graph")
     n = index.ntotal
     D, I = _staging.alloc_DI(max(n, 1), k, index.device)             # never a NULL pointer, even for an empty index
     count = torch.empty(max(n, 1), dtype=torch.int32, device=index.device)
@@ -116,7 +99,7 @@ def similarity_graphs(index, seg_off, keys, top=SIMILAR_TOP, threshold=SIMILAR_T
     _, I, count = knn_graph_device(index, top, seg_off, threshold)
     host = torch.cat([I, count.to(torch.int64).reshape(-1, 1)], 1).cpu().numpy()
     off = seg_off.cpu().numpy() if isinstance(seg_off, torch.Tensor) else np.asarray(seg_off)
-    lo, hi = _segment_bounds(index.ntotal, off)
+    lo, hi = _staging.segment_bounds(index.ntotal, off)
     out = {}
     for r in np.flatnonzero(hi - lo >= 2).tolist():
         out[keys[r]] = [keys[i] for i in host[r, :host[r, -1]].tolist()]

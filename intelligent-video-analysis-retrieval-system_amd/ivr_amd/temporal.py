@@ -105,11 +105,8 @@ def _stage(index, x, L, seg_off, what):
         raise ValueError(f"{what}: index must be a FlatIPIndex, got {type(index).__name__}")
     t, staged = _staging.queries_f32(x, index.d, index.device)
     L = _staging.check_window(L, t.shape[0], SEQ_MAX_LEN, what)
-    seg = None
-    if seg_off is not None:
-        seg, seg_staged = _staging.segment_offsets(seg_off, index.device, what)
-        staged = staged or seg_staged
-    return t, staged, t.shape[0], L, seg, 0 if seg is None else len(seg) - 1
+    seg, seg_staged, nseg = _staging.segments(seg_off, index.device, what)
+    return t, staged or seg_staged, t.shape[0], L, seg, nseg
 
 
 def sequence_search_device(index, x, L, k, seg_off=None, normalize=False):
