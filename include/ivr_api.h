@@ -101,6 +101,32 @@ int ivr_preprocess(ivr_ctx *ctx, const uint8_t *src /*DEV*/, int n, int h, int w
  * blocks stay allocated until ivr_destroy because kernels in flight or a captured graph may still use them. */
 int64_t ivr_preprocess_scratch_bytes(int n, int h, int w, int flags, int out_size);
 
+/* The geometry stage of ivr_preprocess on its own: src DEV uint8 [n,h,w,3] -> dst DEV uint8 [n,S,S,3], S = out_size, the same
+ * Pillow-exact resampler (flags: one IVR_PP_MODE_* and IVR_PP_BILINEAR; every other bit is rejected).  The channel order is left as
+ * it came.  Replaces Image.fromarray(img_rgb).resize(FRAME_SIZE) at filter_research_update.py:246, whose result the reference both
+ * embeds and hashes.  Scratch: ivr_preprocess_scratch_bytes. */
+int ivr_resize_u8(ivr_ctx *ctx, const uint8_t *src /*DEV*/, int n, int h, int w, int flags, int out_size, uint8_t *dst /*DEV*/,
+                  ivr_stream stream);
+
+/* ---- perceptual hash ---------------------------------------------------------------------------------
+ * Replaces imagehash.phash(img) at filter_research_update.py:97-99 (called per frame at :250) for a batch of frames already in HBM.
+ * src: DEV uint8 [n,h,w,3], 1 <= h, w <= IVR_PHASH_MAX_SIDE; flags: 0 or IVR_PP_BGR.  Per frame:
+ *   grey    (R*19595 + G*38470 + B*7471 + 0x8000) >> 16                                   (Pillow convert('L'))
+ *   resize  to 32x32, Pillow's 8-bit resampler with the Lanczos filter (support 3): horizontal pass first, uint8 between the
+ *           passes, a pass skipped when that axis is already 32.  pixels (DEV uint8 [n,32,32], or NULL) receives this image
+ *   DCT     float64, type II, unnormalised, columns then rows, the low 8x8 block: with C[k][m] = cos(pi k (2m+1) / 64)
+ *           (ivr_phash_cos_table), A[k][x] = 2 sum_y C[k][y] p[y][x] and B[k][l] = 2 sum_x A[k][x] C[l][x], both sums in ascending
+ *           order, every product and sum rounded on its own (no fma)
+ *   bits    B[k][l] > (s[31] + s[32]) / 2 over the sorted 64 values s; packed row-major, most significant bit first
+ * hash: DEV uint8 [n,8]; its hex form is str(imagehash.phash(img)).  Two launches (grey + horizontal pass over bands of rows, then one
+ * workgroup per frame); the scratch between them ([n,h,32] bytes) lives in the context, per stream. */
+#define IVR_PHASH_MAX_SIDE 8192
+int64_t ivr_phash_scratch_bytes(int n, int h, int w);
+int ivr_phash(ivr_ctx *ctx, const uint8_t *src /*DEV*/, int n, int h, int w, int flags, uint8_t *hash /*DEV*/,
+              uint8_t *pixels /*DEV or NULL*/, ivr_stream stream);
+/* out[k * 32 + m] = C[k][m] for k < 8, m < 32: the 256 doubles the kernel multiplies with (computed on the host; needs no GPU) */
+int ivr_phash_cos_table(double *out /*HOST [256]*/);
+
 /* ---- E1 / E2 / E3 + N1: encoder towers --------------------------------------------------------
  * Replaces CLIPModel.get_image_features + F.normalize (core.py:1619-1620),
  * CLIPModel.get_text_features + F.normalize (core.py:1541-1542) and
@@ -841,6 +867,25 @@ int ivr_scene_keep_mask_window(ivr_ctx *ctx, const float *emb /*DEV*/, int n, in
  * cosine_similarity([x],[y])[0][0] calls of the keyframe filter (filter.py:147, filter.py:208). */
 int ivr_rowwise_cosine(ivr_ctx *ctx, const float *a /*DEV*/, const float *b /*DEV*/, int n, int d, float *out /*DEV*/,
                        ivr_stream stream);
+
+/* ---- look-back filters of the research keyframe extractor ---------------------------------------------
+ * Both walk the rows of every segment [seg_off[s], seg_off[s+1]) (seg_off: DEV int64 [nseg+1], ascending, clipped to [0, n); NULL
+ * with nseg = 0: one segment of all rows) in row order and hold a window of the last `window` KEPT rows of that segment,
+ * 1 <= window <= IVR_KEEPWIN_MAX_WINDOW; a kept row is appended, and the oldest leaves once the window holds more than `window`.
+ * keep: DEV uint8 [n]; rows outside every segment get 0.  Segments run in parallel, the rows of one segment are a serial chain.
+ *
+ * ivr_hash_keep_mask: the perceptual-duplicate filter of filter_research_update.py:157-162 and :289-298.  hashes: DEV uint8 [n,8];
+ * row i is kept iff no hash h in the window has popcount(hashes[i] xor h) <= threshold.
+ *
+ * ivr_kept_window_mask: the final temporal filter of filter_research_update.py:316-338.  emb: DEV float32 [n,d]; row i is kept iff
+ * no row j in the window has cos(emb[i], emb[j]) >= threshold, the cosine with the arithmetic of ivr_rowwise_cosine.  Unlike
+ * ivr_scene_keep_mask_window the window counts kept rows, not predecessors, so it reaches arbitrarily far back.  Scratch (the
+ * squared norms, n floats) lives in the context, per stream. */
+#define IVR_KEEPWIN_MAX_WINDOW 64
+int ivr_hash_keep_mask(ivr_ctx *ctx, const uint8_t *hashes /*DEV*/, int64_t n, const int64_t *seg_off /*DEV or NULL*/, int nseg,
+                       int threshold, int window, uint8_t *keep /*DEV*/, ivr_stream stream);
+int ivr_kept_window_mask(ivr_ctx *ctx, const float *emb /*DEV*/, int64_t n, int d, const int64_t *seg_off /*DEV or NULL*/, int nseg,
+                         float threshold, int window, uint8_t *keep /*DEV*/, ivr_stream stream);
 
 /* ---- frame quality gating of the keyframe filter ---------------------------------------------------
  * Replaces calculate_blur_score / calculate_edge_density at filter.py:63-92 (cv2.Laplacian(gray, CV_64F).var() and the share of

@@ -14,6 +14,7 @@
 // stores of 8 consecutive output elements; the patch-major layout makes every (patch, channel) run
 // 2 KiB contiguous for P = 32.
 #include "ivr_common.h"
+#include "resample_taps.h"
 
 #include <cmath>
 #include <cstring>
@@ -23,71 +24,9 @@
 
 namespace {
 
-constexpr int kPrecisionBits = 32 - 8 - 2;
-
-struct Taps {          // one resampling axis, for the surviving output positions only
-    int out_len = 0;   // positions computed
-    int ksize = 0;
-    int in_lo = 0, in_hi = 0;   // union of input positions touched
-    std::vector<int32_t> xmin, xcnt, kk;   // kk is [ksize][out_len] (tap-major: coalesced across positions)
-};
-
-double filt_bicubic(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-double filt_bilinear(double x) {
-    if (x < 0.0) x = -x;
-    return x < 1.0 ? 1.0 - x : 0.0;
-}
-
-// Pillow Resample.c precompute_coeffs + normalize_coeffs_8bpc for output positions [first, first+count)
-// of a full-axis resize in_size -> out_size.
-Taps make_taps(int in_size, int out_size, int first, int count, bool bilinear) {
-    Taps t;
-    double (*fn)(double) = bilinear ? filt_bilinear : filt_bicubic;
-    const double fsupport = bilinear ? 1.0 : 2.0;
-    const double scale = (double)in_size / out_size;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = fsupport * filterscale;
-    t.ksize = (int)std::ceil(support) * 2 + 1;
-    t.out_len = count;
-    t.xmin.resize(count);
-    t.xcnt.resize(count);
-    t.kk.assign((size_t)t.ksize * count, 0);
-    t.in_lo = in_size;
-    t.in_hi = 0;
-    const double ss = 1.0 / filterscale;
-    std::vector<double> k(t.ksize);
-    for (int i = 0; i < count; ++i) {
-        const int xx = first + i;
-        const double center = (xx + 0.5) * scale;
-        int lo = (int)(center - support + 0.5);
-        if (lo < 0) lo = 0;
-        int hi = (int)(center + support + 0.5);
-        if (hi > in_size) hi = in_size;
-        const int n = hi - lo;
-        double ww = 0.0;
-        for (int x = 0; x < n; ++x) {
-            const double w = fn((x + lo - center + 0.5) * ss);
-            k[x] = w;
-            ww += w;
-        }
-        for (int x = 0; x < n; ++x) {
-            if (ww != 0.0) k[x] /= ww;
-            const double v = k[x] * (1 << kPrecisionBits);
-            t.kk[(size_t)x * count + i] = k[x] < 0 ? (int)(-0.5 + v) : (int)(0.5 + v);
-        }
-        t.xmin[i] = lo;
-        t.xcnt[i] = n;
-        if (lo < t.in_lo) t.in_lo = lo;
-        if (hi > t.in_hi) t.in_hi = hi;
-    }
-    return t;
-}
+using ivr_resample::kPrecisionBits;
+using ivr_resample::make_taps;
+using ivr_resample::Taps;
 
 struct Plan {            // geometry of one (h, w, mode) on the device
     bool need_h = false, need_v = false;
@@ -168,7 +107,7 @@ int get_plan(int device, int h, int w, int mode, bool bilinear, int S, const Pla
     p.need_h = rw != w;
     p.need_v = rh != h;
     if (p.need_v) {
-        p.tv = make_taps(h, rh, first_y, p.out_h, bilinear);
+        p.tv = make_taps(h, rh, first_y, p.out_h, bilinear ? ivr_resample::kBilinear : ivr_resample::kBicubic);
         p.rows_lo = p.tv.in_lo;
         p.rows_n = p.tv.in_hi - p.tv.in_lo;
         for (auto &m : p.tv.xmin) m -= p.rows_lo;   // relative to the intermediate image
@@ -179,7 +118,7 @@ int get_plan(int device, int h, int w, int mode, bool bilinear, int S, const Pla
         p.rows_n = p.out_h;
     }
     if (p.need_h) {
-        p.th = make_taps(w, rw, first_x, p.out_w, bilinear);
+        p.th = make_taps(w, rw, first_x, p.out_w, bilinear ? ivr_resample::kBilinear : ivr_resample::kBicubic);
         int rc = upload_taps(p.th, &p.d_h);
         if (rc != IVR_OK) return rc;
     } else {
@@ -350,6 +289,47 @@ float bf16_round(float f) {
     return f;
 }
 
+// The geometry stage: src uint8 [n,h,w,3] -> the SxS canvas cv uint8 [n,S,S,3] by plan p (resample, crop, letterbox).  tmp: the
+// horizontal intermediate [n, rows_n, out_w, 3] when both axes are resampled.  Shared by ivr_preprocess and ivr_resize_u8.
+int run_geometry(const Plan *p, const uint8_t *src, int n, int h, int w, int S, uint8_t *cv, uint8_t *tmp, hipStream_t s) {
+    const int64_t cv_frame = (int64_t)S * S * 3;
+    if (p->out_w != S || p->out_h != S) IVR_HIP(hipMemsetAsync(cv, 0, (size_t)n * cv_frame, s));
+    uint8_t *cv_org = cv + ((int64_t)p->off_y * S + p->off_x) * 3;
+    if (p->need_h && p->need_v) {
+        // horizontal over the rows the vertical pass needs, then vertical
+        const int64_t t_frame = (int64_t)p->rows_n * p->out_w * 3;
+        int64_t total = (int64_t)n * t_frame;
+        hipLaunchKernelGGL(resample_axis_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s,
+                           src + (int64_t)p->rows_lo * w * 3, tmp, n, p->rows_n, p->out_w, (int64_t)h * w * 3,
+                           (int64_t)w * 3, (int64_t)3, t_frame, (int64_t)p->out_w * 3, (int64_t)3, p->d_h, p->th.ksize);
+        IVR_LAUNCH_CHECK();
+        total = (int64_t)n * p->out_h * p->out_w * 3;
+        hipLaunchKernelGGL(resample_axis_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s, tmp, cv_org, n,
+                           p->out_w, p->out_h, t_frame, (int64_t)3, (int64_t)p->out_w * 3, cv_frame, (int64_t)3,
+                           (int64_t)S * 3, p->d_v, p->tv.ksize);
+        IVR_LAUNCH_CHECK();
+    } else if (p->need_h) {
+        const int64_t total = (int64_t)n * p->out_h * p->out_w * 3;
+        hipLaunchKernelGGL(resample_axis_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s,
+                           src + (int64_t)p->rows_lo * w * 3, cv_org, n, p->out_h, p->out_w, (int64_t)h * w * 3,
+                           (int64_t)w * 3, (int64_t)3, cv_frame, (int64_t)S * 3, (int64_t)3, p->d_h, p->th.ksize);
+        IVR_LAUNCH_CHECK();
+    } else if (p->need_v) {
+        const int64_t total = (int64_t)n * p->out_h * p->out_w * 3;
+        hipLaunchKernelGGL(resample_axis_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s,
+                           src + (int64_t)p->rows_lo * w * 3 + (int64_t)p->cols_lo * 3, cv_org, n, p->out_w, p->out_h,
+                           (int64_t)h * w * 3, (int64_t)3, (int64_t)w * 3, cv_frame, (int64_t)3, (int64_t)S * 3, p->d_v,
+                           p->tv.ksize);
+        IVR_LAUNCH_CHECK();
+    } else {
+        const int64_t total = (int64_t)n * p->out_h * p->out_w * 3;
+        hipLaunchKernelGGL(crop_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s, src, cv, n, h, w,
+                           p->rows_lo, p->cols_lo, p->out_h, p->out_w, S, p->off_y, p->off_x);
+        IVR_LAUNCH_CHECK();
+    }
+    return IVR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -359,6 +339,34 @@ int64_t ivr_preprocess_scratch_bytes(int n, int h, int w, int flags, int out_siz
     if (mode == IVR_PP_MODE_IDENTITY) return 0;
     // worst case: horizontal intermediate [n, h, S, 3] + SxS canvas [n, S, S, 3]
     return (int64_t)n * h * out_size * 3 + ivr_round_up((int64_t)n * out_size * out_size * 3, 256) + 4096;
+}
+
+int ivr_resize_u8(ivr_ctx *ctx, const uint8_t *src, int n, int h, int w, int flags, int out_size, uint8_t *dst, ivr_stream stream) {
+    IVR_REQUIRE(ctx, "ivr_resize_u8: NULL argument");
+    IVR_REQUIRE(n >= 0 && h >= 1 && w >= 1, "ivr_resize_u8: n=%d h=%d w=%d", n, h, w);
+    IVR_REQUIRE(n == 0 || (src && dst), "ivr_resize_u8: NULL frame buffer");
+    const int S = out_size;
+    const int mode = flags & IVR_PP_MODE_MASK;
+    IVR_REQUIRE((flags & ~(IVR_PP_MODE_MASK | IVR_PP_BILINEAR)) == 0, "ivr_resize_u8: flags=0x%x (a mode and IVR_PP_BILINEAR only)", flags);
+    IVR_REQUIRE(S >= 16 && S % 16 == 0 && S <= 1024, "ivr_resize_u8: out_size=%d must be a multiple of 16 in [16,1024]", S);
+    IVR_REQUIRE(mode <= IVR_PP_MODE_LETTERBOX, "ivr_resize_u8: unknown mode %d", mode);
+    IVR_REQUIRE(mode != IVR_PP_MODE_IDENTITY || (h == S && w == S), "ivr_resize_u8: identity mode needs %dx%d frames, got %dx%d", S, S,
+                h, w);
+    if (n == 0) return IVR_OK;
+    IVR_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h == S && w == S) {
+        IVR_HIP(hipMemcpyAsync(dst, src, (size_t)n * S * S * 3, hipMemcpyDeviceToDevice, s));
+        return IVR_OK;
+    }
+    std::lock_guard<std::mutex> enqueue(ctx->enqueue_mu);           // the launches share the stream's scratch block
+    const Plan *p = nullptr;
+    int rc = get_plan(ctx->device, h, w, mode, (flags & IVR_PP_BILINEAR) != 0, S, &p);
+    if (rc != IVR_OK) return rc;
+    void *tmp = nullptr;                                            // only the horizontal intermediate: the canvas is dst
+    rc = ivr_ctx_scratch(ctx, s, (size_t)((int64_t)n * h * S * 3 + 4096), &tmp);
+    if (rc != IVR_OK) return rc;
+    return run_geometry(p, src, n, h, w, S, dst, reinterpret_cast<uint8_t *>(tmp), s);
 }
 
 int ivr_preprocess(ivr_ctx *ctx, const uint8_t *src, int n, int h, int w, int flags, const float mean[3], const float std[3],
@@ -395,42 +403,8 @@ int ivr_preprocess(ivr_ctx *ctx, const uint8_t *src, int n, int h, int w, int fl
         rc = ivr_ctx_scratch(ctx, s, (size_t)ivr_preprocess_scratch_bytes(n, h, w, flags, S), &scratch);
         if (rc != IVR_OK) return rc;
         uint8_t *cv = reinterpret_cast<uint8_t *>(scratch);
-        uint8_t *tmp = cv + ivr_round_up((int64_t)n * S * S * 3, 256);
-        const int64_t cv_frame = (int64_t)S * S * 3;
-        if (p->out_w != S || p->out_h != S) IVR_HIP(hipMemsetAsync(cv, 0, (size_t)n * cv_frame, s));
-        uint8_t *cv_org = cv + ((int64_t)p->off_y * S + p->off_x) * 3;
-        if (p->need_h && p->need_v) {
-            // horizontal over the rows the vertical pass needs, then vertical
-            const int64_t t_frame = (int64_t)p->rows_n * p->out_w * 3;
-            int64_t total = (int64_t)n * t_frame;
-            hipLaunchKernelGGL(resample_axis_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s,
-                               src + (int64_t)p->rows_lo * w * 3, tmp, n, p->rows_n, p->out_w, (int64_t)h * w * 3,
-                               (int64_t)w * 3, (int64_t)3, t_frame, (int64_t)p->out_w * 3, (int64_t)3, p->d_h, p->th.ksize);
-            IVR_LAUNCH_CHECK();
-            total = (int64_t)n * p->out_h * p->out_w * 3;
-            hipLaunchKernelGGL(resample_axis_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s, tmp, cv_org, n,
-                               p->out_w, p->out_h, t_frame, (int64_t)3, (int64_t)p->out_w * 3, cv_frame, (int64_t)3,
-                               (int64_t)S * 3, p->d_v, p->tv.ksize);
-            IVR_LAUNCH_CHECK();
-        } else if (p->need_h) {
-            const int64_t total = (int64_t)n * p->out_h * p->out_w * 3;
-            hipLaunchKernelGGL(resample_axis_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s,
-                               src + (int64_t)p->rows_lo * w * 3, cv_org, n, p->out_h, p->out_w, (int64_t)h * w * 3,
-                               (int64_t)w * 3, (int64_t)3, cv_frame, (int64_t)S * 3, (int64_t)3, p->d_h, p->th.ksize);
-            IVR_LAUNCH_CHECK();
-        } else if (p->need_v) {
-            const int64_t total = (int64_t)n * p->out_h * p->out_w * 3;
-            hipLaunchKernelGGL(resample_axis_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s,
-                               src + (int64_t)p->rows_lo * w * 3 + (int64_t)p->cols_lo * 3, cv_org, n, p->out_w, p->out_h,
-                               (int64_t)h * w * 3, (int64_t)3, (int64_t)w * 3, cv_frame, (int64_t)3, (int64_t)S * 3, p->d_v,
-                               p->tv.ksize);
-            IVR_LAUNCH_CHECK();
-        } else {
-            const int64_t total = (int64_t)n * p->out_h * p->out_w * 3;
-            hipLaunchKernelGGL(crop_kernel, dim3((unsigned)ivr_ceil_div(total, 256)), dim3(256), 0, s, src, cv, n, h, w,
-                               p->rows_lo, p->cols_lo, p->out_h, p->out_w, S, p->off_y, p->off_x);
-            IVR_LAUNCH_CHECK();
-        }
+        rc = run_geometry(p, src, n, h, w, S, cv, cv + ivr_round_up((int64_t)n * S * S * 3, 256), s);
+        if (rc != IVR_OK) return rc;
         canvas = cv;
     }
 

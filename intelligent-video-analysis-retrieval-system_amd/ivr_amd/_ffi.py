@@ -21,6 +21,8 @@ IVR_PQFS_MAX_M = 256
 IVR_SQ_MAX_D = 1024
 IVR_SEQ_MAX_LEN = 64
 IVR_KNN_MAX_K = 64
+IVR_PHASH_MAX_SIDE = 8192
+IVR_KEEPWIN_MAX_WINDOW = 64
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -65,6 +67,10 @@ _SIGS = {
     "ivr_profile_json": (_i, [_p, C.c_char_p, _i]),
     "ivr_preprocess": (_i, [_p, _p, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _i, _i, _p, _p]),
     "ivr_preprocess_scratch_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "ivr_resize_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "ivr_phash_scratch_bytes": (_i64, [_i, _i, _i]),
+    "ivr_phash": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "ivr_phash_cos_table": (_i, [C.POINTER(C.c_double)]),
     "ivr_tower_create": (_i, [_p, C.POINTER(TowerDesc), C.POINTER(_p)]),
     "ivr_tower_set_weight": (_i, [_p, C.c_char_p, _p, _i64]),
     "ivr_tower_finalize": (_i, [_p, _i]),
@@ -179,6 +185,8 @@ _SIGS = {
     "ivr_dedup_keep_mask": (_i, [_p, _p, _i, _i, _f, _p, _p, _p]),
     "ivr_scene_keep_mask": (_i, [_p, _p, _i, _i, _f, _i, _p, _p]),
     "ivr_scene_keep_mask_window": (_i, [_p, _p, _i, _i, _f, _i, _p, _p]),
+    "ivr_hash_keep_mask": (_i, [_p, _p, _i64, _p, _i, _i, _i, _p, _p]),
+    "ivr_kept_window_mask": (_i, [_p, _p, _i64, _i, _p, _i, _f, _i, _p, _p]),
     "ivr_frame_quality_scratch_bytes": (_i64, [_i, _i, _i]),
     "ivr_frame_quality": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
@@ -188,7 +196,8 @@ _VALUE = frozenset(("ivr_api_version", "ivr_last_error", "ivr_preprocess_scratch
                     "ivr_index_dim", "ivr_index_capacity", "ivr_index_has_ids", "ivr_bin_index_ntotal", "ivr_bin_index_block_rows",
                     "ivr_graph_max_ef", "ivr_graph_max_cand", "ivr_graph_ntotal", "ivr_frame_quality_scratch_bytes",
                     "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries", "ivr_ivfsq_ntotal",
-                    "ivr_pqfs_pass_queries", "ivr_pqfs_index_ntotal", "ivr_knn_max_k", "ivr_knn_piece_rows"))
+                    "ivr_pqfs_pass_queries", "ivr_pqfs_index_ntotal", "ivr_knn_max_k", "ivr_knn_piece_rows",
+                    "ivr_phash_scratch_bytes"))
 # the slot of the ivr_stream argument (the last one wherever there is one): call() fills it when the caller leaves it out
 _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_release_stream_scratch", "ivr_preprocess", "ivr_tower_encode_image", "ivr_tower_encode_text", "ivr_tower_debug_hidden",
@@ -204,7 +213,7 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_pqfs_index_get_codes", "ivr_pqfs_index_search", "ivr_graph_set_rows", "ivr_graph_prune",
     "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
-    "ivr_scene_keep_mask_window", "ivr_frame_quality")}
+    "ivr_scene_keep_mask_window", "ivr_frame_quality", "ivr_resize_u8", "ivr_phash", "ivr_hash_keep_mask", "ivr_kept_window_mask")}
 
 _lib = None
 _lock = threading.Lock()

@@ -11,18 +11,36 @@ from . import _ffi
 from .config import CLIP_MEAN, CLIP_STD
 
 
-def preprocess_frames(frames, mode="identity", mean=CLIP_MEAN, std=CLIP_STD, bgr=False, size=224, patch=None,
-                      out_dtype=torch.bfloat16, bilinear=False, out=None):
-    """frames: uint8 [n,h,w,3] (numpy or CUDA tensor).  Returns a CUDA tensor:
-    patch=None -> [n,3,size,size] (NCHW);  patch=P -> patch-major [n*(size/P)^2, Kpad], Kpad = 3*P*P rounded up to 64.
-    """
+def _frames_on_device(frames):
     if isinstance(frames, np.ndarray):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise ValueError("frames must be uint8 [n,h,w,3]")
     if not frames.is_cuda:
         frames = frames.cuda()
-    frames = frames.contiguous()
+    return frames.contiguous()
+
+
+def resize_frames_u8(frames, mode="stretch", size=224, bilinear=False):
+    """The geometry stage of preprocess_frames on its own (ivr_resize_u8): uint8 [n,h,w,3] (numpy or CUDA tensor) -> uint8 CUDA tensor
+    [n,size,size,3], byte for byte what Pillow's resize gives (bicubic, or bilinear); the channel order is left as it came.  The
+    reference hashes and embeds this image: Image.fromarray(img_rgb).resize(FRAME_SIZE), filter_research_update.py:246."""
+    frames = _frames_on_device(frames)
+    n, h, w, _ = frames.shape
+    if mode not in _ffi.PP_MODE:
+        raise ValueError(f"unknown mode {mode}")
+    out = torch.empty((n, int(size), int(size), 3), dtype=torch.uint8, device=frames.device)
+    _ffi.call("ivr_resize_u8", _ffi.CTX, frames, n, h, w, _ffi.PP_MODE[mode] | (_ffi.PP_BILINEAR if bilinear else 0), int(size), out,
+              device=frames.device)
+    return out
+
+
+def preprocess_frames(frames, mode="identity", mean=CLIP_MEAN, std=CLIP_STD, bgr=False, size=224, patch=None,
+                      out_dtype=torch.bfloat16, bilinear=False, out=None):
+    """frames: uint8 [n,h,w,3] (numpy or CUDA tensor).  Returns a CUDA tensor:
+    patch=None -> [n,3,size,size] (NCHW);  patch=P -> patch-major [n*(size/P)^2, Kpad], Kpad = 3*P*P rounded up to 64.
+    """
+    frames = _frames_on_device(frames)
     n, h, w, _ = frames.shape
     if mode not in _ffi.PP_MODE:
         raise ValueError(f"unknown mode {mode}")
