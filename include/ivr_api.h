@@ -177,6 +177,38 @@ int ivr_tower_encode_text(ivr_tower *t, const int64_t *ids /*DEV*/, int q, int T
 /* bring-up / parity: arm a one-shot capture - the NEXT encode call copies the residual stream after
  * `layer` blocks (0 = embeddings) into out as f32 [n,T,width]. */
 int ivr_tower_debug_hidden(ivr_tower *t, int layer, int n, float *out /*DEV*/, ivr_stream stream);
+/* bring-up / parity: stage capture.  Each call arms one more copy for the NEXT encode call of this tower: straight after the launch
+ * that produced the buffer of (layer, site), the encode call copies it to dst on its own stream (the workspace buffers are reused
+ * from stage to stage, so the copy sits at that point of the stream), raw, in the buffer's own dtype (float32, bf16 or e4m3; eos_pos
+ * int32).  The armed set clears when that call returns.  Unlike ivr_tower_debug_hidden at layer == layers, an armed capture never
+ * changes the path the call takes: a pruned last block stays pruned.  With nothing armed the encode path pays one test per stage.
+ * Extent copied (n = the call's batch, T its tokens, B = max_batch): the full-size buffers their n*T rows; the compact buffers
+ * (LN2 of a pruned block, LN2_CLS, HID_CLS, HID_CLS8, EOS_POS, POOL_LN, POOLED) all B rows, so that the rows behind the n written
+ * ones can be seen to keep their bits.  dst_bytes below that extent fails the encode call with IVR_ERR_INVALID.
+ * layer: block index in [0, layers) for the per-block sites; [0, layers] for STREAM; 0 for EMBED, EOS_POS, POOL_LN, POOLED. */
+enum {
+    IVR_SITE_EMBED = 0,     /* f32 [n*T, width]: the residual stream after the embedding kernels, before the pre-LN */
+    IVR_SITE_EOS_POS = 1,   /* int32 [B] (text towers) */
+    IVR_SITE_STREAM = 2,    /* f32 [n*T, width]: the residual stream after `layer` blocks, as ivr_tower_debug_hidden gives it */
+    IVR_SITE_LN1 = 3,       /* [n*T, width]: LN1 output, in the dtype of the QKV site's operand */
+    IVR_SITE_QKV = 4,       /* [n*T, 3 width]; not materialised by the fused QKV + attention kernel */
+    IVR_SITE_ATT = 5,       /* [n*T, width]: attention output, dtype of the attn-out operand (pruned + fused: compact rows [0, n)) */
+    IVR_SITE_ATTN_OUT = 6,  /* f32 [n*T, width]: the residual stream after attn-out */
+    IVR_SITE_LN2 = 7,       /* LN2 output, dtype of the fc1 operand: [n*T, width], or the token-0 rows [B, width] in a pruned block */
+    IVR_SITE_LN2_CLS = 8,   /* bf16 [B, width]: LN2 of the token-0 rows for the fp8 side path */
+    IVR_SITE_HID = 9,       /* [n*T, mlp]: fc1 output (e4m3 where fc1 and fc2 both are) */
+    IVR_SITE_HID8 = 10,     /* e4m3 [n*T, mlp]: converted copy of a bf16 HID for an e4m3 fc2, behind B * tokens bf16 rows */
+    IVR_SITE_HID_CLS = 11,  /* [B, mlp]: fc1 output of the token-0 rows (side path, pruned block) */
+    IVR_SITE_HID_CLS8 = 12, /* e4m3 [B, mlp]: its converted copy, behind B bf16 rows */
+    IVR_SITE_FC2 = 13,      /* f32 [n*T, width]: the residual stream after the full-size fc2, before the side path adds its rows */
+    IVR_SITE_POOL_LN = 14,  /* [B, width]: the pooled rows after the final LN (bf16 / f32; f32 for IVR_POOL_LN_ALL_CLS) */
+    IVR_SITE_POOLED = 15,   /* f32 [B, embed_dim]: the embedding before F.normalize */
+    IVR_SITE_COUNT = 16
+};
+int ivr_tower_debug_capture(ivr_tower *t, int layer, int site, void *dst /*DEV*/, int64_t dst_bytes);
+/* capture `index` (arming order) of the last encode call that had captures armed: bytes copied (0: the path the call took does not
+ * materialise that site) and the bytes per element of the buffer's dtype. */
+int ivr_tower_debug_capture_result(ivr_tower *t, int index, int64_t *bytes /*HOST*/, int *elem_bytes /*HOST*/);
 int64_t ivr_tower_workspace_bytes(ivr_tower *t);
 
 /* Building block of the towers, exposed for parity tests and kernel benchmarks: y = x W^T (+ bias), i.e. the

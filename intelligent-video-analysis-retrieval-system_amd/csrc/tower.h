@@ -12,6 +12,15 @@ struct TowerTensor {
     int bytes_per = 4;        // 4 = f32, 2 = bf16
 };
 
+// one armed stage capture (ivr_tower_debug_capture): the next encode call copies the buffer of (layer, site) into dst
+struct TowerCapture {
+    int layer = 0, site = 0;
+    void *dst = nullptr;     // device
+    int64_t cap = 0;         // bytes dst can take
+    int64_t got = 0;         // bytes the call copied (0: the path taken does not materialise the site)
+    int elem = 0;            // bytes per element of the buffer as the call left it (4 f32 / int32, 2 bf16, 1 e4m3)
+};
+
 struct ivr_tower {
     ivr_ctx *ctx = nullptr;
     ivr_tower_desc d{};
@@ -21,6 +30,8 @@ struct ivr_tower {
     bool finalized = false;
     int debug_layer = -1;
     float *debug_out = nullptr;
+    std::vector<TowerCapture> cap;        // armed for the next encode call (empty on the product path)
+    std::vector<TowerCapture> cap_done;   // what the last encode call made of them, in arming order
     int max_batch = 0;
     int kpad = 0;            // vision: 3*P*P rounded up to 64
     // activation workspace (one allocation, carved)

@@ -206,12 +206,10 @@ int layer_gemm(ivr_tower *t, bool site_fp8, int epi, GemmArgs &g, const std::str
     return ivr_launch_gemm(t->d.compute == IVR_COMPUTE_F32, epi, g, s);
 }
 
+// read on every encode call, like IVR_PRUNE_LAST (A/B runs, tests)
 int env_zigzag() {
-    static const int v = [] {
-        const char *e = getenv("IVR_ZIGZAG");
-        return e ? (atoi(e) != 0) : 1;
-    }();
-    return v;
+    const char *e = getenv("IVR_ZIGZAG");
+    return e ? (atoi(e) != 0) : 1;
 }
 
 // IVR_PRUNE_LAST=0 runs the last block of a vision tower on every row (A/B runs, tests); read on every encode call
@@ -219,6 +217,39 @@ bool env_prune_last() {
     const char *e = getenv("IVR_PRUNE_LAST");
     return e ? (atoi(e) != 0) : true;
 }
+
+// Stage capture (ivr_tower_debug_capture).  Called straight after the launch that produced `src`: the workspace buffers are reused
+// from stage to stage, so the copy has to sit at this point of the stream.  `bytes` is the extent a launch over this batch may write
+// (full-size buffers: the batch's n*T rows; the compact token-0 and pooled buffers: all max_batch rows, so that the rows behind the
+// n written ones are seen to keep their bits).
+int capture(ivr_tower *t, int layer, int site, const void *src, size_t bytes, int elem, hipStream_t s) {
+    for (TowerCapture &c : t->cap) {
+        if (c.layer != layer || c.site != site) continue;
+        IVR_REQUIRE((int64_t)bytes <= c.cap, "ivr_tower_debug_capture: site %d of block %d holds %lld bytes, the destination %lld", site, layer,
+                    (long long)bytes, (long long)c.cap);
+        IVR_HIP(hipMemcpyAsync(c.dst, src, bytes, hipMemcpyDeviceToDevice, s));
+        c.got = (int64_t)bytes;
+        c.elem = elem;
+    }
+    return IVR_OK;
+}
+// with nothing armed a stage pays this one test
+#define IVR_CAPTURE(layer, site, src, bytes, elem)                                        \
+    if (!t->cap.empty()) {                                                                \
+        if (int crc = capture(t, layer, site, src, (size_t)(bytes), elem, s)) return crc; \
+    }
+
+// the armed set is one-shot: whatever way the encode call ends, its captures move to cap_done
+struct CaptureScope {
+    ivr_tower *t;
+    ~CaptureScope() {
+        if (t->cap.empty()) return;
+        t->cap_done.swap(t->cap);
+        t->cap.clear();
+    }
+};
+
+int kind_bytes(int out_kind) { return out_kind == OUT_F32 ? 4 : out_kind == OUT_FP8 ? 1 : 2; }
 
 // one transformer stack over `rows` = n*T residual rows already in t->resid.  prune_last: only row i*T of image i (token 0) of the
 // final residual stream is read afterwards, so the last block runs everything after LN1 + QKV on those n rows alone: attention
@@ -231,6 +262,7 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
     // dtype of each site's A operand (LN output / attention output / MLP hidden): e4m3 where the consuming site is
     auto kind = [&](bool site8) { return f32 ? OUT_F32 : site8 ? OUT_FP8 : OUT_BF16; };
     const int D = d.width, rows = n * T;
+    const size_t es = f32 ? 4 : 2;       // qkv
     // Producer / consumer order.  Every kernel of a block streams a few hundred MB that the next one reads back; the Infinity
     // Cache (256 MiB) still holds what a kernel wrote LAST.  So consecutive kernels walk the rows in opposite directions: the
     // consumer starts where its producer just finished and takes that part from the cache instead of HBM (IVR_ZIGZAG=0: all
@@ -246,9 +278,11 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
         const bool last = prune_last && i == d.layers - 1;
         if (t->debug_out && t->debug_layer == i)
             IVR_HIP(hipMemcpyAsync(t->debug_out, t->resid, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, s));
+        IVR_CAPTURE(i, IVR_SITE_STREAM, t->resid, (size_t)rows * D * 4, 4);
         rc = ivr_launch_layernorm(kind(q8), t->resid, 1, nullptr, wptr<float>(t, p + "ln1_g"), wptr<float>(t, p + "ln1_b"), d.ln_eps,
                                   t->xn, rows, D, s, zz);
         if (rc) return rc;
+        IVR_CAPTURE(i, IVR_SITE_LN1, t->xn, (size_t)rows * D * kind_bytes(kind(q8)), kind_bytes(kind(q8)));
         GemmArgs g;
         int att_ld = D;                  // row stride of the attention rows attn-out reads (pruned + unfused: every T-th row of att)
         if (!f32 && !q8 && ivr_fused_qkv_attention_ok(rows, T, D, d.heads, d.causal)) {
@@ -271,9 +305,11 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
             g.tag = "gemm_qkv";
             rc = layer_gemm(t, q8, EPI_STORE, g, p + "qkv_w", s);                  // ascending, and so is the attention kernel
             if (rc) return rc;
+            IVR_CAPTURE(i, IVR_SITE_QKV, t->qkv, (size_t)rows * 3 * D * es, (int)es);
             rc = ivr_launch_attention(f32, t->qkv, t->att, n, T, D, d.heads, d.causal, s, o8);
             if (rc) return rc;
         }
+        IVR_CAPTURE(i, IVR_SITE_ATT, t->att, (size_t)rows * D * kind_bytes(kind(o8)), kind_bytes(kind(o8)));
         g = GemmArgs();
         g.A = t->att;
         g.lda = att_ld;
@@ -288,6 +324,7 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
         g.reverse_m = zz;
         rc = layer_gemm(t, o8, EPI_RESID, g, p + "o_w", s);
         if (rc) return rc;
+        IVR_CAPTURE(i, IVR_SITE_ATTN_OUT, t->resid, (size_t)rows * D * 4, 4);
         if (last) {
             // LN2 -> fc1 -> fc2 on the n token-0 rows.  The sites keep their dtypes, except that with the fp8 side path (mlp_cls)
             // these rows run in bf16, as they always did: the block launches no e4m3 MLP GEMM at all then.
@@ -295,6 +332,7 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
             rc = ivr_launch_layernorm(kind(c18), t->resid, T, nullptr, wptr<float>(t, p + "ln2_g"), wptr<float>(t, p + "ln2_b"), d.ln_eps,
                                       t->xn_cls, n, D, s);
             if (rc) return rc;
+            IVR_CAPTURE(i, IVR_SITE_LN2, t->xn_cls, (size_t)t->max_batch * D * kind_bytes(kind(c18)), kind_bytes(kind(c18)));
             g = GemmArgs();
             g.A = t->xn_cls;
             g.lda = D;
@@ -310,11 +348,18 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
             g.tag = "gemm_fc1_cls";
             rc = layer_gemm(t, c18, EPI_STORE, g, p + "fc1_w", s);
             if (rc) return rc;
+            {
+                const int hb = f32 ? 4 : g.out8 ? 1 : 2;
+                IVR_CAPTURE(i, IVR_SITE_HID_CLS, t->hid_cls, (size_t)t->max_batch * d.mlp * hb, hb);
+            }
             const void *hc_a = t->hid_cls;
             if (!c18 && c28) {           // bf16 fc1 feeding an e4m3 fc2: converted copy behind the bf16 rows, as for t->hid
                 unsigned char *h8 = reinterpret_cast<unsigned char *>(t->hid_cls) + (size_t)t->max_batch * d.mlp * 2;
                 rc = ivr_launch_bf16_to_e4m3(t->hid_cls, h8, (int64_t)n * d.mlp, s);
                 if (rc) return rc;
+                // the layout of tower.h, restated: the e4m3 rows start behind max_batch bf16 rows
+                IVR_CAPTURE(i, IVR_SITE_HID_CLS8, reinterpret_cast<unsigned char *>(t->hid_cls) + (size_t)t->max_batch * d.mlp * 2,
+                            (size_t)t->max_batch * d.mlp, 1);
                 hc_a = h8;
             }
             g = GemmArgs();
@@ -330,15 +375,17 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
             g.tag = "gemm_fc2_cls";
             rc = layer_gemm(t, c28, EPI_RESID, g, p + "fc2_w", s);
             if (rc) return rc;
-            continue;
+            continue;                    // the block's output stream is the STREAM site of i + 1
         }
         rc = ivr_launch_layernorm(kind(f18), t->resid, 1, nullptr, wptr<float>(t, p + "ln2_g"), wptr<float>(t, p + "ln2_b"), d.ln_eps,
                                   t->xn, rows, D, s);
         if (rc) return rc;
+        IVR_CAPTURE(i, IVR_SITE_LN2, t->xn, (size_t)rows * D * kind_bytes(kind(f18)), kind_bytes(kind(f18)));
         if (mlp_cls) {                   // token-0 rows of the same LayerNorm in bf16 for the side path
             rc = ivr_launch_layernorm(OUT_BF16, t->resid, T, nullptr, wptr<float>(t, p + "ln2_g"), wptr<float>(t, p + "ln2_b"), d.ln_eps,
                                       t->xn_cls, n, D, s);
             if (rc) return rc;
+            IVR_CAPTURE(i, IVR_SITE_LN2_CLS, t->xn_cls, (size_t)t->max_batch * D * 2, 2);
         }
         g = GemmArgs();
         g.A = t->xn;
@@ -356,11 +403,18 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
         g.tag = "gemm_fc1";
         rc = layer_gemm(t, f18, EPI_STORE, g, p + "fc1_w", s);
         if (rc) return rc;
+        {
+            const int hb = f32 ? 4 : g.out8 ? 1 : 2;
+            IVR_CAPTURE(i, IVR_SITE_HID, t->hid, (size_t)rows * d.mlp * hb, hb);
+        }
         const void *hid_a = t->hid;
         if (!f18 && f28) {               // bf16 fc1 feeding an e4m3 fc2 (error-budget configurations only): converted copy behind it
             unsigned char *h8 = reinterpret_cast<unsigned char *>(t->hid) + (size_t)t->max_batch * d.tokens * d.mlp * 2;
             rc = ivr_launch_bf16_to_e4m3(t->hid, h8, (int64_t)rows * d.mlp, s);
             if (rc) return rc;
+            // the layout of tower.h, restated: the e4m3 rows start behind max_batch * tokens bf16 rows
+            IVR_CAPTURE(i, IVR_SITE_HID8, reinterpret_cast<unsigned char *>(t->hid) + (size_t)t->max_batch * d.tokens * d.mlp * 2,
+                        (size_t)rows * d.mlp, 1);
             hid_a = h8;
         }
         g = GemmArgs();
@@ -377,6 +431,7 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
         g.tag = "gemm_fc2";
         rc = layer_gemm(t, f28, EPI_RESID, g, p + "fc2_w", s);
         if (rc) return rc;
+        IVR_CAPTURE(i, IVR_SITE_FC2, t->resid, (size_t)rows * D * 4, 4);
         if (mlp_cls) {
             // side path: the n token-0 rows through fc1 / fc2 in bf16 (rows of image i sit T*D apart in the residual stream)
             g = GemmArgs();
@@ -393,6 +448,7 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
             g.tag = "gemm_fc1_cls";
             rc = layer_gemm(t, false, EPI_STORE, g, p + "fc1_w", s);
             if (rc) return rc;
+            IVR_CAPTURE(i, IVR_SITE_HID_CLS, t->hid_cls, (size_t)t->max_batch * d.mlp * 2, 2);
             g = GemmArgs();
             g.A = t->hid_cls;
             g.lda = d.mlp;
@@ -410,6 +466,7 @@ int run_layers(ivr_tower *t, int n, int T, bool prune_last, hipStream_t s) {
     }
     if (t->debug_out && t->debug_layer == d.layers)
         IVR_HIP(hipMemcpyAsync(t->debug_out, t->resid, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, s));
+    IVR_CAPTURE(d.layers, IVR_SITE_STREAM, t->resid, (size_t)rows * D * 4, 4);
     t->debug_out = nullptr;
     return IVR_OK;
 }
@@ -424,11 +481,14 @@ int run_pool(ivr_tower *t, int n, int T, const int *offs, int normalize, float *
         rc = ivr_launch_layernorm(OUT_F32, t->resid, T, offs, wptr<float>(t, "post_ln_g"), wptr<float>(t, "post_ln_b"), d.ln_eps,
                                   t->pooled_f32, n, D, s);
         if (rc) return rc;
+        IVR_CAPTURE(0, IVR_SITE_POOL_LN, t->pooled_f32, (size_t)t->max_batch * D * 4, 4);
+        IVR_CAPTURE(0, IVR_SITE_POOLED, t->pooled_f32, (size_t)t->max_batch * D * 4, 4);
         return ivr_launch_f_normalize(t->pooled_f32, out, n, D, normalize, s);
     }
     rc = ivr_launch_layernorm(f32 ? OUT_F32 : OUT_BF16, t->resid, T, offs, wptr<float>(t, "post_ln_g"), wptr<float>(t, "post_ln_b"), d.ln_eps, t->pool, n,
                               D, s);
     if (rc) return rc;
+    IVR_CAPTURE(0, IVR_SITE_POOL_LN, t->pool, (size_t)t->max_batch * D * (f32 ? 4 : 2), f32 ? 4 : 2);
     GemmArgs g;
     g.A = t->pool;
     g.lda = D;
@@ -442,6 +502,7 @@ int run_pool(ivr_tower *t, int n, int T, const int *offs, int normalize, float *
     g.tag = "gemm_proj";
     rc = ivr_launch_gemm(f32, EPI_F32, g, s);
     if (rc) return rc;
+    IVR_CAPTURE(0, IVR_SITE_POOLED, t->pooled_f32, (size_t)t->max_batch * d.out_dim * 4, 4);
     return ivr_launch_f_normalize(t->pooled_f32, out, n, d.out_dim, normalize, s);
 }
 
@@ -575,6 +636,7 @@ int ivr_tower_encode_image(ivr_tower *t, const void *patches, int n, int normali
     const ivr_tower_desc &d = t->d;
     IVR_REQUIRE(d.kind == IVR_KIND_VISION, "ivr_tower_encode_image: not a vision tower");
     IVR_REQUIRE(n >= 0 && n <= t->max_batch, "ivr_tower_encode_image: n=%d exceeds max_batch=%d", n, t->max_batch);
+    CaptureScope scope{t};
     if (n == 0) return IVR_OK;
     IVR_HIP(hipSetDevice(t->ctx->device));
     hipStream_t s = (hipStream_t)stream;
@@ -599,6 +661,7 @@ int ivr_tower_encode_image(ivr_tower *t, const void *patches, int n, int normali
     g.tag = "gemm_patch";
     rc = ivr_launch_gemm(f32, EPI_PATCH, g, s);
     if (rc) return rc;
+    IVR_CAPTURE(0, IVR_SITE_EMBED, t->resid, (size_t)n * T * D * 4, 4);
     if (d.pre_ln) {
         rc = ivr_launch_layernorm(OUT_F32, t->resid, 1, nullptr, wptr<float>(t, "pre_ln_g"), wptr<float>(t, "pre_ln_b"), d.ln_eps, t->resid,
                                   n * T, D, s);
@@ -620,12 +683,15 @@ int ivr_tower_encode_text(ivr_tower *t, const int64_t *ids, int q, int T, int no
     IVR_REQUIRE(T >= 1 && T <= d.tokens, "ivr_tower_encode_text: T=%d outside [1,%d]", T, d.tokens);
     IVR_REQUIRE(q >= 0 && (int64_t)q * T <= (int64_t)t->max_batch * d.tokens && q <= t->max_batch,
                 "ivr_tower_encode_text: q=%d exceeds max_batch=%d", q, t->max_batch);
+    CaptureScope scope{t};
     if (q == 0) return IVR_OK;
     IVR_HIP(hipSetDevice(t->ctx->device));
     hipStream_t s = (hipStream_t)stream;
     int rc = ivr_launch_text_embed(t->resid, ids, wptr<float>(t, "tok"), wptr<float>(t, "pos"), q, T, d.width, d.vocab, d.eos_id,
                                    t->eos_pos, s);
     if (rc) return rc;
+    IVR_CAPTURE(0, IVR_SITE_EMBED, t->resid, (size_t)q * T * d.width * 4, 4);
+    IVR_CAPTURE(0, IVR_SITE_EOS_POS, t->eos_pos, (size_t)t->max_batch * 4, 4);
     rc = run_layers(t, q, T, false, s);      // the pooled row sits at a device-side EOS offset: no pruning
     if (rc) return rc;
     return run_pool(t, q, T, t->eos_pos, normalize, out, s);
@@ -820,6 +886,33 @@ int ivr_tower_debug_hidden(ivr_tower *t, int layer, int n, float *out, ivr_strea
     // one-shot: the NEXT encode call copies the residual stream after `layer` blocks into `out`
     t->debug_layer = layer;
     t->debug_out = out;
+    return IVR_OK;
+}
+
+int ivr_tower_debug_capture(ivr_tower *t, int layer, int site, void *dst, int64_t dst_bytes) {
+    IVR_REQUIRE(t && dst && dst_bytes > 0, "ivr_tower_debug_capture: NULL argument");
+    std::lock_guard<std::mutex> lk(t->mu);
+    IVR_REQUIRE(site >= 0 && site < IVR_SITE_COUNT, "ivr_tower_debug_capture: site=%d", site);
+    const bool whole = site == IVR_SITE_EMBED || site == IVR_SITE_EOS_POS || site == IVR_SITE_POOL_LN || site == IVR_SITE_POOLED;
+    const int hi = whole ? 0 : site == IVR_SITE_STREAM ? t->d.layers : t->d.layers - 1;
+    IVR_REQUIRE(layer >= 0 && layer <= hi, "ivr_tower_debug_capture: layer=%d outside [0,%d] for site %d", layer, hi, site);
+    IVR_REQUIRE(t->cap.size() < 4096, "ivr_tower_debug_capture: too many armed captures");
+    TowerCapture c;
+    c.layer = layer;
+    c.site = site;
+    c.dst = dst;
+    c.cap = dst_bytes;
+    t->cap.push_back(c);
+    return IVR_OK;
+}
+
+int ivr_tower_debug_capture_result(ivr_tower *t, int index, int64_t *bytes, int *elem_bytes) {
+    IVR_REQUIRE(t && bytes && elem_bytes, "ivr_tower_debug_capture_result: NULL argument");
+    std::lock_guard<std::mutex> lk(t->mu);
+    IVR_REQUIRE(index >= 0 && (size_t)index < t->cap_done.size(), "ivr_tower_debug_capture_result: index=%d, the last call had %d captures",
+                index, (int)t->cap_done.size());
+    *bytes = t->cap_done[(size_t)index].got;
+    *elem_bytes = t->cap_done[(size_t)index].elem;
     return IVR_OK;
 }
 

@@ -51,6 +51,9 @@ class IdFilter(C.Structure):
 
 API_VERSION = 11
 FP8_SITE = {"qkv": 1, "o": 2, "fc1": 4, "fc2": 8}
+# IVR_SITE_* of ivr_tower_debug_capture
+TOWER_SITE = {"embed": 0, "eos_pos": 1, "stream": 2, "ln1": 3, "qkv": 4, "att": 5, "attn_out": 6, "ln2": 7, "ln2_cls": 8, "hid": 9,
+              "hid8": 10, "hid_cls": 11, "hid_cls8": 12, "fc2": 13, "pool_ln": 14, "pooled": 15}
 
 
 _p = C.c_void_p
@@ -78,6 +81,8 @@ _SIGS = {
     "ivr_tower_encode_image": (_i, [_p, _p, _i, _i, _p, _p]),
     "ivr_tower_encode_text": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "ivr_tower_debug_hidden": (_i, [_p, _i, _i, _p, _p]),
+    "ivr_tower_debug_capture": (_i, [_p, _i, _i, _p, _i64]),
+    "ivr_tower_debug_capture_result": (_i, [_p, _i, C.POINTER(_i64), C.POINTER(_i)]),
     "ivr_tower_workspace_bytes": (_i64, [_p]),
     "ivr_linear": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "ivr_quantize_e4m3_host": (_i, [_p, _p, _i64]),

@@ -18,6 +18,8 @@ is reachable offline.  Activations are cast to e4m3 at unit scale (saturation at
 outlier stress test of tests/test_fp8_gpu.py exercises: trained CLIP towers have outlier channels, so re-run tools/fp8_error_budget.py
 on the real checkpoint (model_path= directory) before trusting a preset with it.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -77,9 +79,38 @@ class Tower(_ffi.Handle):
     def workspace_bytes(self):
         return int(_ffi.call("ivr_tower_workspace_bytes", self._h))
 
+    # -- stage capture (bring-up / parity) -----------------------------------------------------
+    def _capture_cols(self, site):
+        c = self.cfg
+        return {"eos_pos": 1, "qkv": 3 * c.width, "hid": c.mlp, "hid8": c.mlp, "hid_cls": c.mlp, "hid_cls8": c.mlp,
+                "pooled": self.embed_dim}.get(site, c.width)
+
+    def _arm(self, capture, rows):
+        """Arm ivr_tower_debug_capture for [(layer, site), ...]; the destinations are sized for float32 (the widest dtype)."""
+        bufs = []
+        for layer, site in capture:
+            buf = torch.zeros(max(rows, self.max_batch) * self._capture_cols(site) * 4, dtype=torch.uint8, device=self.device)
+            self._call("ivr_tower_debug_capture", int(layer), _ffi.TOWER_SITE[site], buf, buf.numel())
+            bufs.append(buf)
+        return bufs
+
+    def _captured(self, capture, bufs):
+        """{(layer, site): tensor [rows, cols] in the buffer's own dtype, or None where the path taken does not materialise it}."""
+        got = {}
+        for i, ((layer, site), buf) in enumerate(zip(capture, bufs)):
+            nbytes, elem = ctypes.c_int64(), ctypes.c_int()
+            self._call("ivr_tower_debug_capture_result", i, nbytes, elem)
+            if nbytes.value == 0:
+                got[(layer, site)] = None
+                continue
+            dt = torch.int32 if site == "eos_pos" else {4: torch.float32, 2: torch.bfloat16, 1: torch.float8_e4m3fn}[elem.value]
+            got[(layer, site)] = buf[:nbytes.value].view(dt).view(-1, self._capture_cols(site))
+        return got
+
     # -- vision --------------------------------------------------------------------------------
-    def encode_patches(self, patches, n, normalize=True, out=None, capture_hidden=None):
-        """patches: CUDA patch-major pixels [n*g*g, Kpad] in the tower's activation dtype."""
+    def encode_patches(self, patches, n, normalize=True, out=None, capture_hidden=None, capture=None):
+        """patches: CUDA patch-major pixels [n*g*g, Kpad] in the tower's activation dtype.
+        capture=[(layer, site), ...] (site names: _ffi.TOWER_SITE, include/ivr_api.h) also returns the stage captures of this call."""
         if patches.dtype != self.act_dtype or not patches.is_cuda or not patches.is_contiguous():
             raise ValueError(f"patches must be a contiguous CUDA {self.act_dtype} tensor")
         if out is None:
@@ -88,7 +119,10 @@ class Tower(_ffi.Handle):
         if capture_hidden is not None:
             hidden = torch.empty((n, self.cfg.tokens, self.cfg.width), dtype=torch.float32, device=self.device)
             self._call("ivr_tower_debug_hidden", int(capture_hidden), n, hidden)
+        bufs = self._arm(capture, n * self.cfg.tokens) if capture is not None else None
         self._call("ivr_tower_encode_image", patches, int(n), bool(normalize), out)
+        if capture is not None:
+            return out, self._captured(capture, bufs)
         return (out, hidden) if capture_hidden is not None else out
 
     def encode_frames(self, frames, mode="identity", mean=None, std=None, bgr=False, normalize=True, out=None):
@@ -111,13 +145,20 @@ class Tower(_ffi.Handle):
         return out
 
     # -- text ----------------------------------------------------------------------------------
-    def encode_ids(self, ids, normalize=True):
-        """int64 token ids [q,T] (numpy or tensor) -> float32 CUDA [q, embed_dim]."""
+    def encode_ids(self, ids, normalize=True, capture=None):
+        """int64 token ids [q,T] (numpy or tensor) -> float32 CUDA [q, embed_dim].
+        capture=[(layer, site), ...]: also the stage captures, as for encode_patches (q <= max_batch: one call)."""
         if isinstance(ids, np.ndarray):
             ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64))
         ids = ids.to(device=self.device, dtype=torch.int64).contiguous()
         q, T = ids.shape
         out = torch.empty((q, self.embed_dim), dtype=torch.float32, device=self.device)
+        if capture is not None:
+            if q > self.max_batch:
+                raise ValueError("capture needs q <= max_batch")
+            bufs = self._arm(capture, q * T)
+            self._call("ivr_tower_encode_text", ids, q, T, bool(normalize), out)
+            return out, self._captured(capture, bufs)
         for i in range(0, q, self.max_batch):
             sub = ids[i:i + self.max_batch].contiguous()
             self._call("ivr_tower_encode_text", sub, sub.shape[0], T, bool(normalize), out[i:])
