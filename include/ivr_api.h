@@ -516,6 +516,47 @@ int ivr_index_range_search_sequences(ivr_index *idx, const float *q /*DEV [T,d]*
                                      int64_t *lims /*DEV [T-L+2]*/, float *D /*DEV [cap]*/, int64_t *I /*DEV [cap]*/, int64_t cap,
                                      ivr_stream stream);
 
+/* ---- event search: chains of query events with bounded gaps over the flat index ------------------------
+ * Where in the stored rows do m query events occur IN ORDER, not too far apart ("a door opens, THEN a dog jumps out, THEN the car drives
+ * off")?  The gapped form of the clip search, which scores consecutive rows only.  q: DEV float32 [B][m][d], B >= 1 chains of
+ * 1 <= m <= IVR_EVENT_MAX_LEN events each; 1 <= min_gap <= max_gap <= IVR_EVENT_MAX_GAP, in rows; ntotal < 2^31.
+ *   frame score   S[j, r] = the float32 inner product ivr_index_search reports for (event j of the chain, stored row r), to the bit
+ *   segments      seg_off as for the clip search: DEV int64 [nseg + 1], ascending, or NULL (nseg is not read, the index is one segment).
+ *                 A row outside [seg_off[0], seg_off[nseg]) belongs to no segment and is no candidate of any step; empty segments are
+ *                 allowed; a chain never leaves the segment of its end row
+ *   step 0        C[0, r] = S[0, r] for every row inside a segment
+ *   step j >= 1   the window of row r is [max(lo(r), r - max_gap), r - min_gap], lo(r) the start of r's segment.  No candidate of step
+ *                 j - 1 in it: r is no candidate of step j.  Otherwise its predecessor P[j, r] is the candidate of the window with the
+ *                 greatest C[j-1, .], -0.0 equal to +0.0, equal values the LOWER row (the order of every result key of the library), and
+ *                 C[j, r] = (C[j-1, P[j, r]] + 0.0f) + S[j, r]: one float32 addition, rounded once
+ *   chain score   W[r] = C[m-1, r] / (float)m of end row r: one correctly rounded division, written as every search writes scores
+ *                 (-0.0 as +0.0).  Float32 addition is monotone, so C[m-1, r] is the maximum over ALL admissible chains that end in r of
+ *                 the left-to-right sum ((S[0, r0] + 0 + S[1, r1]) + 0 + ...)
+ *   path          r[m-1] = r, r[j-1] = P[j, r[j]]; reported in event order, as row numbers, or as stored ids on an id-mapped index
+ * ivr_index_search_events: D DEV [B][k], I DEV [B][k][m]: per chain the k best end rows by W, descending, equal scores the lower END
+ * row first, and the path behind each; unused slots -FLT_MAX and -1 in all m entries.  1 <= k <= IVR_MAX_K.
+ * ivr_index_best_events_per_segment: D DEV [B][nseg], I DEV [B][nseg][m] (nseg = 1 without seg_off): for every segment its best end row
+ * by the same order and its path, -FLT_MAX / -1 for a segment without a chain: which videos hold the sequence, all videos in one call.
+ * Here B * nseg < 2^31.
+ *
+ * Launches per chunk of chains, all on `stream`, no host round trip: the score pass of the clip search over the chunk's frames; m - 1
+ * step launches (a workgroup owns 1024 rows of one chain, holds the keys of the rows its windows reach in LDS and takes every window
+ * maximum from block prefix / suffix maxima: the work per row does not grow with max_gap); the top-k selection or a key maximum per
+ * segment; one backtrack launch that follows the stored 16-bit predecessor distances.  The segment bounds are one launch per call.
+ * A chunk holds as many chains as IVR_SEQ_CHUNK_SLOTS / ntotal (one at least, 4096 / m at most).  Scratch on the index, grow-only:
+ * per (chain of a chunk, stored row) 16 bytes of keys and 2 (m - 1) bytes of distances, 4 bytes per (frame of a chunk rounded up to
+ * whole 16-frame tiles plus one tile, stored row) shared with the clip search, 8 bytes per stored row of segment bounds, 8 bytes per
+ * result slot of a chunk.  m = 1 is ivr_index_search.  Enqueue-only, no host synchronisation, once the scratch has grown (a call that
+ * grows it allocates); not graph-capturable then. */
+#define IVR_EVENT_MAX_LEN 8
+#define IVR_EVENT_MAX_GAP 4096
+int ivr_index_search_events(ivr_index *idx, const float *q /*DEV [B,m,d]*/, int B, int m, int min_gap, int max_gap,
+                            const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, int k, int normalize_q, float *D /*DEV [B,k]*/,
+                            int64_t *I /*DEV [B,k,m]*/, ivr_stream stream);
+int ivr_index_best_events_per_segment(ivr_index *idx, const float *q /*DEV [B,m,d]*/, int B, int m, int min_gap, int max_gap,
+                                      const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, int normalize_q,
+                                      float *D /*DEV [B,nseg]*/, int64_t *I /*DEV [B,nseg,m]*/, ivr_stream stream);
+
 /* ---- frame clustering: DBSCAN over the stored rows of the flat index ----------------------------------
  * Which stored frames are the same shot?  The reference's AdvancedKeyframeExtractor.cluster_similar_frames
  * (filter_research_update.py:113-134: sklearn DBSCAN on the precomputed 1 - cosine matrix) without the N x N matrix: a tiled self-join

@@ -15,8 +15,8 @@
 //   bin_load_row, bin_with_words  the loaders of the binary-code layout (search_binary.hip, search_pq.hip, search_ivfpq.hip; the
 //                                 coded-index structs themselves are in search_coded.h)
 // Users: search_index.hip (the index object and its storage), search.hip (group-maximum scans and the top-k driver), search_range.hip,
-// search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_ivf.hip and the other list scans, and
-// through self_join.h cluster.hip and knn.hip.
+// search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_events.hip, search_ivf.hip and the other
+// list scans, and through self_join.h cluster.hip and knn.hip.
 #pragma once
 #include "ivr_common.h"
 
@@ -330,6 +330,10 @@ struct ivr_index {
     DevBuf<int64_t> seq_total;       // DEV [1]: the running total of the range call, carried from chunk to chunk
     // the self-joins (self_join.h); grow-only
     DevBuf<int32_t> sj_seg;          // DEV [2][ntotal rounded up to 64]: start and end of each row's segment
+    // event search (ivr_index_search_events, search_events.hip), one chunk of chains; grow-only.  The frame scores go to seq_scores
+    DevBuf<uint64_t> ev_keys;        // DEV [2][chains of a chunk][ntotal]: (ordered C[j], ~row) of the previous and of this step, 0 = no candidate
+    DevBuf<uint16_t> ev_pred;        // DEV [chains of a chunk][m - 1][ntotal]: r - P[j, r] of every candidate of step j >= 1
+    DevBuf<int64_t> ev_rows;         // DEV [chains of a chunk][k or nseg]: the end row behind every result slot, -1 for an unused one
     // frame clustering (ivr_index_dbscan, cluster.hip); grow-only
     DevBuf<int32_t> cl_words;        // DEV [5][ntotal + 1 rounded up to 64]: degree, parent, root, border root, root prefix of each row
     // neighbour graph (ivr_index_knn_graph, knn.hip); grow-only
@@ -411,6 +415,10 @@ int ivr_reserve_queries(ivr_index *x, int qtiles);
 int ivr_reserve_gmax(ivr_index *x);
 void ivr_launch_scan_qt(ivr_index *x, const View &v, int qt, const float *qtile, hipStream_t s, const int *tile_flag = nullptr);
 void ivr_launch_fast_scan(ivr_index *x, const View &v, int qt, int64_t tile0, hipStream_t s);
+// search_seq.hip.  The score pass of the clip search and the event search: the 16-frame tiles qtile0 .. qtile0 + qtiles - 1 of
+// x->qtiled against every stored row -> x->seq_scores [16 qtiles][ntotal rounded up to 16], line f = frame 16 qtile0 + f.  The caller
+// holds x->mu, has reserved seq_scores and keeps ceil(ntotal / 1024) * qtiles below 2^31 (the grid)
+int ivr_launch_seq_score(ivr_index *x, int qtile0, int qtiles, hipStream_t s);
 // search_sq.hip.  t int16 [nq][d] -> the int8 halves t = 128 h + l of the int8 MFMA scans, tiled per 16 queries: qh and ql
 // [qtiles][ksteps][64], zeros past d and past nq
 void ivr_launch_sq_stage(const int16_t *t, int nq, int d, int ksteps, int64_t qtiles, uint4 *qh, uint4 *ql, hipStream_t s);

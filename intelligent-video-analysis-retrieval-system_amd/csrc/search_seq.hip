@@ -64,6 +64,24 @@ __global__ __launch_bounds__(256) void seq_score_kernel(SeqScore a) {
     }
 }
 
+}  // namespace
+
+// search_internal.h: the score pass as the clip search and the event search (search_events.hip) launch it
+int ivr_launch_seq_score(ivr_index *x, int qtile0, int qtiles, hipStream_t s) {
+    const size_t lds = (size_t)16 * x->dp * 4;
+    const int rc = ivr_func_max_lds(reinterpret_cast<const void *>(seq_score_kernel), (int)lds);
+    if (rc != IVR_OK) return rc;
+    const int64_t ntiles = ivr_ceil_div(x->ntotal, 16);
+    IvrProf prof("seq_score", s, (double)qtiles * 16 * x->ntotal * 2.0 * x->dp);
+    const SeqScore sc{reinterpret_cast<const float4 *>(x->data), reinterpret_cast<const float4 *>((const float *)x->qtiled) + (int64_t)qtile0 * x->dp4 * 16,
+                      x->dp4, qtiles, ntiles, x->seq_scores, ntiles * 16};
+    hipLaunchKernelGGL(seq_score_kernel, dim3((unsigned)(ivr_ceil_div(ntiles, kSeqTilesPerBlock) * qtiles)), dim3(256), lds, s, sc);
+    IVR_LAUNCH_CHECK();
+    return IVR_OK;
+}
+
+namespace {
+
 struct SeqWindow {
     const float *S;
     int64_t sstride;
@@ -164,21 +182,12 @@ int seq_search(ivr_index *x, const SeqArgs &a, hipStream_t s) {
     if (rc != IVR_OK) return rc;
     rc = ivr_launch_tile_rows(x, x->qtiled, a.q, 0, a.T, a.normalize_q, nullptr, s);
     if (rc != IVR_OK) return rc;
-    const size_t lds = (size_t)16 * x->dp * 4;
-    rc = ivr_func_max_lds(reinterpret_cast<const void *>(seq_score_kernel), (int)lds);
-    if (rc != IVR_OK) return rc;
-    const int per_tile = x->dp4 * 16;
     const int64_t *ids = x->has_ids ? x->ids : nullptr;
     for (int w0 = 0; w0 < nwin; w0 += wc) {
         const int wcnt = std::min(wc, nwin - w0);
         const int qtile0 = w0 >> 4, qtiles = ((w0 + wcnt + a.L - 2) >> 4) - qtile0 + 1;
-        {
-            IvrProf prof("seq_score", s, (double)qtiles * 16 * x->ntotal * 2.0 * x->dp);
-            const SeqScore sc{reinterpret_cast<const float4 *>(x->data), reinterpret_cast<const float4 *>((const float *)x->qtiled) + (int64_t)qtile0 * per_tile,
-                              x->dp4, qtiles, ntiles, x->seq_scores, sstride};
-            hipLaunchKernelGGL(seq_score_kernel, dim3((unsigned)(ivr_ceil_div(ntiles, kSeqTilesPerBlock) * qtiles)), dim3(256), lds, s, sc);
-            IVR_LAUNCH_CHECK();
-        }
+        rc = ivr_launch_seq_score(x, qtile0, qtiles, s);
+        if (rc != IVR_OK) return rc;
         const int64_t nslots = (int64_t)wcnt * nstart;
         {
             IvrProf prof("seq_window", s, (double)nslots * (4.0 * a.L + 8));

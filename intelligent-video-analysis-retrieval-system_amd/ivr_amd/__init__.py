@@ -1,6 +1,6 @@
 """ivr_amd: the HIP-backed pieces of the retrieval system.  The submodules are imported by name (ivr_amd.index, ivr_amd.tower, ...);
 the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index, the product-quantisation (8- and 4-bit codes) and scalar-quantisation indexes
-and the clip search, the frame clustering, the neighbour graph and the perceptual hash with its look-back filters are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
+and the clip search, the event search, the frame clustering, the neighbour graph and the perceptual hash with its look-back filters are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
 _IVF = ("IVFFlatIndex", "IndexIVFFlat", "SearchParametersIVF", "METRIC_INNER_PRODUCT", "METRIC_L2")
 _BINARY = ("BinaryFlatIndex", "IndexBinaryFlat", "IndexLSH", "lsh_rotation")
 _GRAPH = ("GraphFlatIndex", "IndexHNSWFlat", "SearchParametersHNSW", "graph_prune_ref", "graph_link_ref", "graph_build_ref",
@@ -13,7 +13,9 @@ _SQ = ("SQIndex", "IndexScalarQuantizer", "ScalarQuantizer", "sq_encode_ref", "s
 _IVFPQ = ("IVFPQIndex", "IndexIVFPQ", "ivfpq_scan_ref", "ivfpq_pack_ref", "ivfpq_unpack_ref")
 _IVFSQ = ("IVFSQIndex", "IndexIVFScalarQuantizer", "ivfsq_scan_ref", "ivfsq_pack_ref", "ivfsq_unpack_ref", "ivfsq_score_bound")
 _TEMPORAL = ("TemporalAnalyzer", "sequence_search", "sequence_search_device", "sequence_range_search", "sequence_range_search_device",
-             "sequence_scores_ref", "sequence_search_ref", "sequence_range_ref")
+             "sequence_scores_ref", "sequence_search_ref", "sequence_range_ref", "event_search", "event_search_device",
+             "event_best_per_segment", "event_best_per_segment_device", "event_scores_ref", "event_search_ref",
+             "event_best_per_segment_ref")
 _CLUSTER = ("dbscan", "dbscan_device", "dbscan_ref", "cluster_members", "select_representatives", "representatives_ref",
             "cluster_similar_frames", "select_representative_frame")
 _NEIGHBORS = ("knn_graph", "knn_graph_device", "knn_graph_ref", "similarity_graphs", "build_similarity_relationships")

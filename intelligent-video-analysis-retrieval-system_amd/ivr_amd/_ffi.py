@@ -20,6 +20,8 @@ IVR_PQ_MAX_M = 128
 IVR_PQFS_MAX_M = 256
 IVR_SQ_MAX_D = 1024
 IVR_SEQ_MAX_LEN = 64
+IVR_EVENT_MAX_LEN = 8
+IVR_EVENT_MAX_GAP = 4096
 IVR_KNN_MAX_K = 64
 IVR_PHASH_MAX_SIDE = 8192
 IVR_KEEPWIN_MAX_WINDOW = 64
@@ -121,6 +123,8 @@ _SIGS = {
     "ivr_index_rescore": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
     "ivr_index_search_sequences": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_index_range_search_sequences": (_i, [_p, _p, _i, _i, _p, _i, _f, _i, _p, _p, _p, _i64, _p]),
+    "ivr_index_search_events": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
+    "ivr_index_best_events_per_segment": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
     "ivr_index_dbscan": (_i, [_p, _f, _i, _p, _i, _p, _p, _p, _p]),
     "ivr_segment_best_cosine": (_i, [_p, _p, _i64, _p, _i, _i, _p, _p, _p, _p]),
     "ivr_knn_max_k": (_i, []),
@@ -211,7 +215,7 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_index_search_filtered", "ivr_index_range_search_filtered", "ivr_index_remove_ids", "ivr_index_add_with_ids",
     "ivr_index_get_ids", "ivr_index_find_ids", "ivr_index_gather", "ivr_index_scatter", "ivr_index_search_reconstruct",
     "ivr_index_search_lists", "ivr_segment_mean", "ivr_index_rescore", "ivr_index_search_sequences",
-    "ivr_index_range_search_sequences", "ivr_index_dbscan", "ivr_segment_best_cosine", "ivr_index_knn_graph", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
+    "ivr_index_range_search_sequences", "ivr_index_search_events", "ivr_index_best_events_per_segment", "ivr_index_dbscan", "ivr_segment_best_cosine", "ivr_index_knn_graph", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
     "ivr_sign_encode", "ivr_pq_encode", "ivr_pq_tables", "ivr_bin_index_search_pq", "ivr_ivfpq_set_lists", "ivr_ivfpq_get_codes",
     "ivr_ivfpq_search", "ivr_ivfsq_set_lists", "ivr_ivfsq_get_codes", "ivr_ivfsq_search", "ivr_sq_encode", "ivr_sq_query", "ivr_sq_index_add",
     "ivr_sq_index_get_codes", "ivr_sq_index_search", "ivr_pqfs_encode", "ivr_pqfs_tables", "ivr_pqfs_quantize", "ivr_pqfs_index_add",

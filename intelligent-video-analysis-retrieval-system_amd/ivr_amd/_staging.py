@@ -93,6 +93,32 @@ def check_window(L, T, lmax, what):
     return L
 
 
+def chains_f32(x, d, device, mmax, what):
+    """The chains of an event search: [B,m,d], or [m,d] for one chain, 1 <= m <= mmax -> (contiguous float32 tensor [B*m,d] on
+    `device`, is_staged, B, m)."""
+    t = dev_f32(x, device)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.shape[2] != d:
+        raise ValueError(f"{what}: events must be [B,m,{d}] or [m,{d}], got {tuple(getattr(x, 'shape', ()))}")
+    B, m = int(t.shape[0]), int(t.shape[1])
+    if B < 1:
+        raise ValueError(f"{what}: no chains")
+    if m < 1 or m > mmax:
+        raise ValueError(f"{what}: m={m} events outside [1,{mmax}]")
+    return t.reshape(B * m, d), is_staged(t, x), B, m
+
+
+def check_gaps(min_gap, max_gap, gmax, what):
+    """The gaps of an event search: integers with 1 <= min_gap <= max_gap <= gmax -> (int min_gap, int max_gap)."""
+    for name, g in (("min_gap", min_gap), ("max_gap", max_gap)):
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+            raise ValueError(f"{what}: {name} must be an integer, got {type(g).__name__}")
+    if not 1 <= min_gap <= max_gap <= gmax:
+        raise ValueError(f"{what}: gaps [{min_gap},{max_gap}] outside 1 <= min_gap <= max_gap <= {gmax}")
+    return int(min_gap), int(max_gap)
+
+
 def check_dbscan(eps, min_samples, what):
     """The parameters of a DBSCAN call: eps a number >= 0 (not NaN), min_samples an integer >= 1 -> (float eps, int min_samples)."""
     if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)):
@@ -127,6 +153,11 @@ def check_knn(k, threshold, kmax, what):
 def alloc_DI(nq, k, device, dtype=torch.float32):
     """The (D, I) pair of a search: D `dtype` [nq,k], I int64 [nq,k]."""
     return torch.empty((nq, k), dtype=dtype, device=device), torch.empty((nq, k), dtype=torch.int64, device=device)
+
+
+def alloc_DI_paths(nq, k, m, device):
+    """The (D, I) pair of an event search: D float32 [nq,k], I int64 [nq,k,m] (one row per event of the path)."""
+    return torch.empty((nq, k), dtype=torch.float32, device=device), torch.empty((nq, k, m), dtype=torch.int64, device=device)
 
 
 # -- caller-supplied integer tables ----------------------------------------------------------------------------------------------

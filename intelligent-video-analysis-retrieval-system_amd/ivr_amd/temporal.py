@@ -17,6 +17,10 @@ Definition (the `*_ref` functions below are this in numpy, to the bit, given the
 Results are labelled with the start row, or with the stored id of that row on an id-mapped index.  Equal scores rank the lower start
 ROW first; -0.0 is reported as +0.0.  The threshold test of the range call is `>=`, as the reference's is, not the strict `>` of
 `FlatIPIndex.range_search`.
+
+Event search (event_search, event_best_per_segment; the `event_*_ref` functions are its definition) is the gapped form: m query events
+in order, consecutive events between min_gap and max_gap rows apart, inside one segment; a result is an end row's chain score and the
+path of m rows behind it.
 """
 import numpy as np
 import torch
@@ -27,6 +31,8 @@ from .index import FlatIPIndex
 from .refine import _ordered
 
 SEQ_MAX_LEN = _ffi.IVR_SEQ_MAX_LEN
+EVENT_MAX_LEN = _ffi.IVR_EVENT_MAX_LEN
+EVENT_MAX_GAP = _ffi.IVR_EVENT_MAX_GAP
 
 
 # -- the definition in numpy ---------------------------------------------------------------------------------------------------
@@ -98,7 +104,162 @@ def sequence_range_ref(S, L, threshold, seg_off=None, ids=None):
             np.concatenate(I).astype(np.int64) if I else np.zeros(0, np.int64))
 
 
+# -- event search: the definition in numpy ----------------------------------------------------------------------------------------
+# m query events in order, consecutive events min_gap .. max_gap rows apart, all inside the segment of the end row
+# (ivr_index_search_events / ivr_index_best_events_per_segment, csrc/search_events.hip; the definition is in include/ivr_api.h):
+#   C[0, r] = S[0, r] for the rows inside a segment
+#   P[j, r] = the candidate p of step j-1 in [max(lo(r), r - max_gap), r - min_gap] with the greatest C[j-1, p], -0.0 equal to +0.0,
+#             equal values the lower row; no candidate in the window: r is no candidate of step j
+#   C[j, r] = float32((C[j-1, P[j, r]] + 0.0) + S[j, r]),   W[r] = C[m-1, r] / float32(m)
+def _event_args(S, min_gap, max_gap, what):
+    S = np.asarray(S, np.float32)
+    if S.ndim != 2 or not 1 <= S.shape[0] <= EVENT_MAX_LEN:
+        raise ValueError(f"{what}: S {S.shape} must be [m,N] with 1 <= m <= {EVENT_MAX_LEN}")
+    min_gap, max_gap = _staging.check_gaps(min_gap, max_gap, EVENT_MAX_GAP, what)
+    return S, min_gap, max_gap
+
+
+def event_scores_ref(S, min_gap, max_gap, seg_off=None):
+    """S float32 [m,N] frame scores of one chain -> (C float32 [m,N], P int64 [m,N], ok bool [m,N]): the best left-to-right float32
+    sum of an admissible chain whose event j lies on row r, the row of its event j-1 (-1 in row 0 and for a row that is no candidate)
+    and which (step, row) pairs are candidates."""
+    S, min_gap, max_gap = _event_args(S, min_gap, max_gap, "event_scores_ref")
+    m, N = S.shape
+    lo, _ = _staging.segment_bounds(N, seg_off)
+    rows = np.arange(N, dtype=np.int64)
+    C = np.zeros((m, N), np.float32)
+    P = np.full((m, N), -1, np.int64)
+    ok = np.zeros((m, N), bool)
+    ok[0] = lo <= rows
+    C[0, ok[0]] = S[0, ok[0]]
+    zero = np.float32(0.0)
+    for j in range(1, m):
+        keys = np.where(ok[j - 1], _ordered(C[j - 1]).astype(np.int64), -1)
+        for r in range(N):
+            a, b = max(int(lo[r]), r - max_gap), r - min_gap
+            if a > b:
+                continue
+            i = int(np.argmax(keys[a:b + 1]))                      # the first of equal maxima: the lower row
+            if keys[a + i] < 0:
+                continue
+            ok[j, r], P[j, r] = True, a + i
+            C[j, r] = np.float32(np.float32(C[j - 1, a + i] + zero) + S[j, r])
+    return C, P, ok
+
+
+def _event_paths(P, ends, ids):
+    """int64 [len(ends), m]: the path behind every end row, in event order."""
+    m = P.shape[0]
+    out = np.empty((len(ends), m), np.int64)
+    r = np.asarray(ends, np.int64).copy()
+    for j in range(m - 1, -1, -1):
+        out[:, j] = r
+        if j:
+            r = P[j, r]
+    return _labels(out, ids)
+
+
+def _event_chains(S, what):
+    S = np.asarray(S, np.float32)
+    if S.ndim == 2:
+        S = S[None]
+    if S.ndim != 3:
+        raise ValueError(f"{what}: S {S.shape} must be [B,m,N] or [m,N]")
+    return S
+
+
+def _event_ranked(Sb, min_gap, max_gap, seg_off):
+    """(W float32 [N] + 0.0, P, the candidate end rows by (W descending, row ascending)) of one chain."""
+    C, P, ok = event_scores_ref(Sb, min_gap, max_gap, seg_off)
+    m = C.shape[0]
+    W = (C[m - 1] / np.float32(m)).astype(np.float32)
+    rows = np.flatnonzero(ok[m - 1]).astype(np.int64)
+    order = np.lexsort((rows, -_ordered(W[rows]).astype(np.int64)))
+    return W + np.float32(0.0), P, rows[order]
+
+
+def event_search_ref(S, k, min_gap, max_gap, seg_off=None, ids=None):
+    """S float32 [B,m,N] (or [m,N]: one chain) -> (D float32 [B,k], I int64 [B,k,m]): per chain the k best end rows by W, descending,
+    equal scores the lower end row first, with the path behind each in event order; (-FLT_MAX, -1 in all m entries) in unused
+    slots.  ids: the labels of an id-mapped index."""
+    S = _event_chains(S, "event_search_ref")
+    k = int(k)
+    B, m = S.shape[:2]
+    D = np.full((B, k), -FLT_MAX, np.float32)
+    I = np.full((B, k, m), -1, np.int64)
+    for b in range(B):
+        W, P, ends = _event_ranked(S[b], min_gap, max_gap, seg_off)
+        ends = ends[:k]
+        D[b, :len(ends)] = W[ends]
+        I[b, :len(ends)] = _event_paths(P, ends, ids)
+    return D, I
+
+
+def event_best_per_segment_ref(S, min_gap, max_gap, seg_off=None, ids=None):
+    """(D float32 [B,nseg], I int64 [B,nseg,m]): for every segment its best end row by the order of event_search_ref and the path behind
+    it; (-FLT_MAX, -1) for a segment without a chain.  nseg = 1 without seg_off."""
+    S = _event_chains(S, "event_best_per_segment_ref")
+    B, m, N = S.shape
+    off = np.array([0, N], np.int64) if seg_off is None else np.asarray(seg_off).astype(np.int64).reshape(-1)
+    nseg = len(off) - 1
+    D = np.full((B, nseg), -FLT_MAX, np.float32)
+    I = np.full((B, nseg, m), -1, np.int64)
+    for b in range(B):
+        W, P, ends = _event_ranked(S[b], min_gap, max_gap, seg_off)
+        for s in range(nseg):
+            inside = ends[(ends >= off[s]) & (ends < off[s + 1])]
+            if len(inside):
+                D[b, s] = W[inside[0]]
+                I[b, s] = _event_paths(P, inside[:1], ids)[0]
+    return D, I
+
+
 # -- the library calls ---------------------------------------------------------------------------------------------------------
+def _stage_events(index, x, min_gap, max_gap, seg_off, what):
+    """The checked arguments of both event calls: (frames tensor [B*m,d], staged, B, m, min_gap, max_gap, seg_off tensor or None,
+    nseg)."""
+    if not isinstance(index, FlatIPIndex):
+        raise ValueError(f"{what}: index must be a FlatIPIndex, got {type(index).__name__}")
+    t, staged, B, m = _staging.chains_f32(x, index.d, index.device, EVENT_MAX_LEN, what)
+    min_gap, max_gap = _staging.check_gaps(min_gap, max_gap, EVENT_MAX_GAP, what)
+    seg, seg_staged, nseg = _staging.segments(seg_off, index.device, what)
+    return t, staged or seg_staged, B, m, min_gap, max_gap, seg, nseg
+
+
+def event_search_device(index, x, k, max_gap, min_gap=1, seg_off=None, normalize=False):
+    """Top-k event search on the device: x float32 [B,m,d] chains of m events (numpy or torch; [m,d] is one chain) -> (D float32
+    [B,k], I int64 [B,k,m]) CUDA tensors, the definition of event_search_ref.  seg_off as for sequence_search_device.  No host
+    synchronisation unless an argument had to be staged."""
+    t, staged, B, m, min_gap, max_gap, seg, nseg = _stage_events(index, x, min_gap, max_gap, seg_off, "event_search")
+    k = _staging.check_k(k, _ffi.IVR_MAX_K)
+    D, I = _staging.alloc_DI_paths(B, k, m, index.device)
+    index._call("ivr_index_search_events", t, B, m, min_gap, max_gap, seg, nseg, k, bool(normalize), D, I)
+    _staging.sync_if_staged(staged, index.device)
+    return D, I
+
+
+def event_search(index, x, k, max_gap, min_gap=1, seg_off=None, normalize=False):
+    """event_search_device as numpy arrays (D, I)."""
+    D, I = event_search_device(index, x, k, max_gap, min_gap, seg_off, normalize)
+    return D.cpu().numpy(), I.cpu().numpy()
+
+
+def event_best_per_segment_device(index, x, max_gap, min_gap=1, seg_off=None, normalize=False):
+    """The best chain of every segment on the device: (D float32 [B,nseg], I int64 [B,nseg,m]) CUDA tensors, the definition of
+    event_best_per_segment_ref: which videos hold the sequence, all videos in one call.  nseg = 1 without seg_off."""
+    t, staged, B, m, min_gap, max_gap, seg, nseg = _stage_events(index, x, min_gap, max_gap, seg_off, "event_best_per_segment")
+    D, I = _staging.alloc_DI_paths(B, max(nseg, 1), m, index.device)
+    index._call("ivr_index_best_events_per_segment", t, B, m, min_gap, max_gap, seg, nseg, bool(normalize), D, I)
+    _staging.sync_if_staged(staged, index.device)
+    return D, I
+
+
+def event_best_per_segment(index, x, max_gap, min_gap=1, seg_off=None, normalize=False):
+    """event_best_per_segment_device as numpy arrays (D, I)."""
+    D, I = event_best_per_segment_device(index, x, max_gap, min_gap, seg_off, normalize)
+    return D.cpu().numpy(), I.cpu().numpy()
+
+
 def _stage(index, x, L, seg_off, what):
     """The checked arguments of both calls: (frames tensor, staged, T, L, seg_off tensor or None, nseg)."""
     if not isinstance(index, FlatIPIndex):
@@ -226,6 +387,27 @@ class TemporalAnalyzer:
         similar_sequences = [(int(s), float(w)) for s, w in zip(I, D)]      # (target start, db start) order
         similar_sequences.sort(key=lambda x: x[1], reverse=True)
         return similar_sequences
+
+    def find_event_sequences(self, event_features, database_features, max_gap, min_gap=1, k=10, validate_inputs=True):
+        """Not in the reference: [(path, score), ...], best first, for the k best places where the m rows of event_features occur in
+        order in database_features, consecutive events min_gap .. max_gap rows apart.  path is a tuple of m database rows, score the mean
+        cosine along it.  Both arrays go through a temporary FlatIPIndex with normalize=True, as find_similar_sequences does; fewer
+        than k chains give a shorter list."""
+        if validate_inputs:
+            if not isinstance(event_features, np.ndarray) or not isinstance(database_features, np.ndarray):
+                raise ValueError("Features must be numpy arrays")
+            if event_features.ndim != 2 or database_features.ndim != 2:
+                raise ValueError("Features must be 2D arrays")
+        if len(event_features) < 1 or len(database_features) < 1:
+            self.logger.warning("Insufficient features for event search")
+            return []
+        index = FlatIPIndex(database_features.shape[1])
+        try:
+            index.add(database_features, normalize=True)
+            D, I = event_search(index, event_features, k, max_gap, min_gap, normalize=True)
+        finally:
+            index.close()
+        return [(tuple(int(r) for r in path), float(w)) for path, w in zip(I[0], D[0]) if path[0] >= 0]
 
     def get_transition_frames(self, features, scene_boundaries, validate_inputs=True):
         """core.py:3704-3739: the frames within two before and three after every cut between consecutive scenes, ascending."""
