@@ -557,6 +557,44 @@ int ivr_index_best_events_per_segment(ivr_index *idx, const float *q /*DEV [B,m,
                                       const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, int normalize_q,
                                       float *D /*DEV [B,nseg]*/, int64_t *I /*DEV [B,nseg,m]*/, ivr_stream stream);
 
+/* ---- grouped search: the best segments per query with their best rows -----------------------------------
+ * Which VIDEOS answer a query, and with which frames?  Every other search ranks rows, and the keyframes of one shot fill the head of
+ * such a list; vector stores call this grouping search (Milvus) or collapse with inner hits (Elasticsearch).  q: DEV float32 [nq,d].
+ *   frame score   S[q, r] = the float32 inner product ivr_index_search reports for (query q, stored row r), to the bit
+ *   row key       K[q, r] = (ordered S[q, r], ~r), the result key of every top-k of the library: the larger key ranks first, equal scores
+ *                 the LOWER row, -0.0 equal to +0.0
+ *   segments      seg_off as for the clip search: DEV int64 [nseg + 1], ascending, or NULL (nseg is not read, the index is one segment).
+ *                 Empty segments are allowed and form no group; rows outside [seg_off[0], seg_off[nseg]) belong to no group; offsets
+ *                 beyond ntotal are clipped
+ *   group key     of segment j for query q: the greatest K[q, r] over the rows of j.  Groups rank by it, descending; among equal best
+ *                 scores the segment that holds the lower best row comes first, which is the lower segment
+ *   result        per query the best G groups, and within each the g best rows of that segment by K, descending
+ * ivr_index_search_groups: Gseg DEV int64 [nq][G] the segment NUMBER of each chosen group; D DEV [nq][G][g] and I DEV [nq][G][g] the
+ * scores and the rows, as row numbers, or as stored ids on an id-mapped index.  Unused group slots hold -1 in Gseg and -FLT_MAX / -1 in
+ * all g entries; unused row slots of a short segment -FLT_MAX / -1.  1 <= G, 1 <= g <= IVR_GROUP_MAX_ROWS, G * g <= IVR_MAX_K, nq >= 1,
+ * ntotal < 2^31; anything else is IVR_ERR_INVALID.  An empty index yields unused slots only.  Without seg_off, G = 1 and g = k is
+ * ivr_index_search at k; with every row its own segment, G = k and g = 1 is ivr_index_search at k: both to the bit.
+ * ivr_index_best_per_segment: D DEV [nq][nseg], I DEV [nq][nseg] (nseg = 1 without seg_off): the best row of EVERY segment and its
+ * score, -FLT_MAX / -1 for an empty segment: the video-level score of every video in one call.  Here nq * nseg < 2^31.
+ *
+ * Launches, all on `stream`, no host round trip: the row -> segment table once per call; then per chunk of queries a fill of the
+ * segment keys with 0 ("no row"), the segment-best pass (the score pass of the clip search, whose epilogue writes no score: it folds
+ * the rows of a tile per segment in registers and issues one 64-bit atomic maximum per (query, segment touched) and wave), the top-G
+ * selection over the segment keys (ivr_index_best_per_segment decodes them instead), a label pass, and for g > 1 the rows pass (one
+ * workgroup per (query, group, piece of ivr_group_piece_rows() rows)) and its merge.  A maximum does not depend on the order of
+ * arrival and the keys are unique: the same bits on every run and stream.  Scratch on the index, grow-only: 8 bytes per (query of a
+ * chunk, segment), 4 bytes per stored row, 12 bytes per result slot (query of a chunk, group) and, for g > 1, 32 g bytes per (result
+ * slot, piece; 16 pieces at most).  A chunk holds whole 16-query tiles, as many queries as keep the segment keys and the row lists
+ * within IVR_SEQ_CHUNK_SLOTS slots each (16 at least, 4096 at most).  Enqueue-only, no host synchronisation, once the scratch has grown
+ * (a call that grows it allocates); not graph-capturable then. */
+#define IVR_GROUP_MAX_ROWS 64
+int ivr_group_piece_rows(void);   /* stored rows one workgroup's piece of a long segment covers at least: tests size their cases from it */
+int ivr_index_search_groups(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg,
+                            int G, int g, int normalize_q, int64_t *Gseg /*DEV [nq,G]*/, float *D /*DEV [nq,G,g]*/,
+                            int64_t *I /*DEV [nq,G,g]*/, ivr_stream stream);
+int ivr_index_best_per_segment(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, const int64_t *seg_off /*DEV [nseg+1] or NULL*/,
+                               int nseg, int normalize_q, float *D /*DEV [nq,nseg]*/, int64_t *I /*DEV [nq,nseg]*/, ivr_stream stream);
+
 /* ---- frame clustering: DBSCAN over the stored rows of the flat index ----------------------------------
  * Which stored frames are the same shot?  The reference's AdvancedKeyframeExtractor.cluster_similar_frames
  * (filter_research_update.py:113-134: sklearn DBSCAN on the precomputed 1 - cosine matrix) without the N x N matrix: a tiled self-join

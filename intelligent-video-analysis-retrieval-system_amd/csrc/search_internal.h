@@ -15,8 +15,8 @@
 //   bin_load_row, bin_with_words  the loaders of the binary-code layout (search_binary.hip, search_pq.hip, search_ivfpq.hip; the
 //                                 coded-index structs themselves are in search_coded.h)
 // Users: search_index.hip (the index object and its storage), search.hip (group-maximum scans and the top-k driver), search_range.hip,
-// search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_events.hip, search_ivf.hip and the other
-// list scans, and through self_join.h cluster.hip and knn.hip.
+// search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_events.hip, search_groups.hip,
+// search_ivf.hip and the other list scans, and through self_join.h cluster.hip and knn.hip.
 #pragma once
 #include "ivr_common.h"
 
@@ -338,6 +338,11 @@ struct ivr_index {
     DevBuf<int32_t> cl_words;        // DEV [5][ntotal + 1 rounded up to 64]: degree, parent, root, border root, root prefix of each row
     // neighbour graph (ivr_index_knn_graph, knn.hip); grow-only
     DevBuf<uint64_t> kn_keys;        // DEV [query blocks of a chunk][parts of a walk][64][k]: the partial lists, at most 2^25 keys
+    // grouped search (ivr_index_search_groups, search_groups.hip), one chunk of queries; grow-only, each on its own
+    DevBuf<int32_t> gr_seg;          // DEV [ntotal rounded up to 16]: the segment of each row, -1 in front of the first and nseg behind the last
+    DevBuf<uint64_t> gr_best;        // DEV [queries of a chunk][nseg]: the greatest (ordered score, ~row) of each segment, 0 = no row
+    DevBuf<int64_t> gr_rows;         // DEV [queries of a chunk][G]: the best row of each chosen group (-1: unused), then as many floats
+    DevBuf<uint64_t> gr_lists;       // DEV [queries of a chunk][G][pieces][4 waves][g]: the partial row lists, at most IVR_SEQ_CHUNK_SLOTS keys
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

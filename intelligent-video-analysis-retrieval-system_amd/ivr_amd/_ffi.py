@@ -23,6 +23,7 @@ IVR_SEQ_MAX_LEN = 64
 IVR_EVENT_MAX_LEN = 8
 IVR_EVENT_MAX_GAP = 4096
 IVR_KNN_MAX_K = 64
+IVR_GROUP_MAX_ROWS = 64
 IVR_PHASH_MAX_SIDE = 8192
 IVR_KEEPWIN_MAX_WINDOW = 64
 # flags of ivr_preprocess
@@ -125,6 +126,9 @@ _SIGS = {
     "ivr_index_range_search_sequences": (_i, [_p, _p, _i, _i, _p, _i, _f, _i, _p, _p, _p, _i64, _p]),
     "ivr_index_search_events": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "ivr_index_best_events_per_segment": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
+    "ivr_group_piece_rows": (_i, []),
+    "ivr_index_search_groups": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "ivr_index_best_per_segment": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p]),
     "ivr_index_dbscan": (_i, [_p, _f, _i, _p, _i, _p, _p, _p, _p]),
     "ivr_segment_best_cosine": (_i, [_p, _p, _i64, _p, _i, _i, _p, _p, _p, _p]),
     "ivr_knn_max_k": (_i, []),
@@ -206,7 +210,7 @@ _VALUE = frozenset(("ivr_api_version", "ivr_last_error", "ivr_preprocess_scratch
                     "ivr_graph_max_ef", "ivr_graph_max_cand", "ivr_graph_ntotal", "ivr_frame_quality_scratch_bytes",
                     "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries", "ivr_ivfsq_ntotal",
                     "ivr_pqfs_pass_queries", "ivr_pqfs_index_ntotal", "ivr_knn_max_k", "ivr_knn_piece_rows",
-                    "ivr_phash_scratch_bytes"))
+                    "ivr_phash_scratch_bytes", "ivr_group_piece_rows"))
 # the slot of the ivr_stream argument (the last one wherever there is one): call() fills it when the caller leaves it out
 _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_release_stream_scratch", "ivr_preprocess", "ivr_tower_encode_image", "ivr_tower_encode_text", "ivr_tower_debug_hidden",
@@ -215,7 +219,8 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_index_search_filtered", "ivr_index_range_search_filtered", "ivr_index_remove_ids", "ivr_index_add_with_ids",
     "ivr_index_get_ids", "ivr_index_find_ids", "ivr_index_gather", "ivr_index_scatter", "ivr_index_search_reconstruct",
     "ivr_index_search_lists", "ivr_segment_mean", "ivr_index_rescore", "ivr_index_search_sequences",
-    "ivr_index_range_search_sequences", "ivr_index_search_events", "ivr_index_best_events_per_segment", "ivr_index_dbscan", "ivr_segment_best_cosine", "ivr_index_knn_graph", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
+    "ivr_index_range_search_sequences", "ivr_index_search_events", "ivr_index_best_events_per_segment",
+    "ivr_index_search_groups", "ivr_index_best_per_segment", "ivr_index_dbscan", "ivr_segment_best_cosine", "ivr_index_knn_graph", "ivr_bin_index_add", "ivr_bin_index_get_codes", "ivr_bin_index_search",
     "ivr_sign_encode", "ivr_pq_encode", "ivr_pq_tables", "ivr_bin_index_search_pq", "ivr_ivfpq_set_lists", "ivr_ivfpq_get_codes",
     "ivr_ivfpq_search", "ivr_ivfsq_set_lists", "ivr_ivfsq_get_codes", "ivr_ivfsq_search", "ivr_sq_encode", "ivr_sq_query", "ivr_sq_index_add",
     "ivr_sq_index_get_codes", "ivr_sq_index_search", "ivr_pqfs_encode", "ivr_pqfs_tables", "ivr_pqfs_quantize", "ivr_pqfs_index_add",

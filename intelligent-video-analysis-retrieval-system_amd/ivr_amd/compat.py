@@ -559,6 +559,47 @@ class FAISSRetriever:
                         results.append(SearchResult(metadata=md, similarity_score=s, rank=rank + 1, query_relevance=s))
             return results
 
+    def search_grouped(self, query_features, n_groups: int = 10, group_size: int = 3, validate_results=True) -> List[List[SearchResult]]:
+        """Not in the reference: the n_groups best VIDEOS of the first query row, each a list of its group_size best frames as
+        SearchResult (rank = the frame's place inside its video), best video first.  A video is a run of equal folder_name in the
+        metadata (ivr_amd.grouping.seg_off_from_labels; folders whose rows are not contiguous raise ValueError).  Scores get the
+        post-processing of search()."""
+        if not self.is_trained or not self.index:
+            raise RuntimeError("Index not trained. Call build_index first.")
+        if len(self.id_to_metadata) == 0:
+            return []
+        from .grouping import group_search_device, seg_off_from_labels
+        with self._lock:
+            q = self._normalize_and_validate_features(query_features)
+            if q.shape[1] != self.dimension:
+                raise ValueError(f"Query dimension ({q.shape[1]}) != index dimension ({self.dimension})")
+            seg_off = seg_off_from_labels(self.id_to_metadata[i].folder_name for i in range(self.index.ntotal))
+            try:
+                _, _, I = group_search_device(self.index, q[:1], n_groups, group_size, seg_off=seg_off)
+                indices = I[0].cpu().numpy()
+            except ValueError:
+                raise
+            except Exception as e:
+                raise RuntimeError(f"Search operation failed: {e}")
+            qn = q[0].cpu().numpy()
+            groups = []
+            for idxs in indices:
+                results = []
+                for rank, idx in enumerate(idxs):
+                    idx = int(idx)
+                    if idx >= 0 and idx in self.id_to_metadata:
+                        md = self.id_to_metadata[idx]
+                        if validate_results:
+                            try:
+                                md._validate()
+                            except Exception:
+                                continue
+                        s = self._calculate_proper_similarity(qn, md.clip_features)
+                        results.append(SearchResult(metadata=md, similarity_score=s, rank=rank + 1, query_relevance=s))
+                if results:
+                    groups.append(results)
+            return groups
+
     def save_index(self, index_path: str, validate_before_save: bool = True) -> None:
         """core.py:960: <index_path>/index.faiss (flat FAISS container, ivr_amd.faiss_io) + metadata.json."""
         if not self.is_trained:
