@@ -1009,6 +1009,42 @@ int64_t ivr_frame_quality_scratch_bytes(int n, int h, int w);
 int ivr_frame_quality(ivr_ctx *ctx, const uint8_t *frames /*DEV*/, int n, int h, int w, int bgr, int canny_low, int canny_high,
                       int64_t *lap_sums /*DEV*/, int64_t *edge_count /*DEV*/, ivr_stream stream);
 
+/* ---- diversified search: maximal marginal relevance and near-duplicate suppression over candidate lists ----
+ * Which k of the kc candidates of a query answer it without showing one picture k times?  Adjacent keyframes of a shot, the same scene
+ * in two videos and a recurring shot lie within a hair of each other in cosine and fill the head of a relevance-ranked list.  Vector
+ * stores answer with MMR (LangChain's max_marginal_relevance_search, Qdrant, Elasticsearch, OpenSearch) or by dropping a hit that is
+ * nearly the same as a better one.  cand is positional like ivr_index_rescore, on plain and id-mapped indexes alike; an entry outside
+ * [0, ntotal), -1 included, is absent; a row named twice is two candidates.
+ *   relevance   R[j] = the float32 score ivr_index_rescore reports for (query q, row cand[q][j]), so the bits of ivr_index_search
+ *   pair score  P[i, j] = the float32 score ivr_index_rescore reports for (query = the stored float32 row cand[q][i], row cand[q][j]):
+ *               the chosen row is the query operand.  Both enter the arithmetic as reported, -0.0 as +0.0
+ *   order       candidates rank by (value descending, -0.0 equal to +0.0; row ascending; position in cand ascending)
+ *   selection   greedy, t = 0 .. k - 1; m[j] = the greatest P[s, j] over the candidates s chosen so far, by float compare
+ *   IVR_DIVERSE_MMR       param = lambda in [0, 1], mu = 1.0f - lambda.  The first choice is the best candidate by R, what
+ *                         ivr_index_search returns first whatever lambda is; from the second on the value of a candidate not yet chosen
+ *                         is (lambda * R[j]) - (mu * m[j]): two float32 products and one float32 subtraction, each rounded, no fused
+ *                         multiply-add.  lambda = 1 is the order of ivr_index_rescore
+ *   IVR_DIVERSE_SUPPRESS  param = threshold.  The value is R[j]; a candidate with m[j] >= threshold is out for good, and the selection
+ *                         ends early when nothing is left.  A threshold above every P is the order of ivr_index_rescore, one below every
+ *                         P returns one result
+ * D DEV [nq][k]: R of each chosen candidate, in the order chosen; I DEV [nq][k]: its row, or its stored id on an id-mapped index; M DEV
+ * [nq][k] or NULL: m of the chosen candidate at the moment it was chosen (how redundant is this hit?), -FLT_MAX in slot 0.  Unused slots
+ * hold -FLT_MAX / -1 / -FLT_MAX.  1 <= k <= kc <= IVR_MAX_K, nq >= 1, nq kc < 2^31, mode one of the two constants, param not NaN and
+ * within [0, 1] for IVR_DIVERSE_MMR; anything else is IVR_ERR_INVALID, checked before any device call.  An empty index gives unused
+ * slots only.
+ *
+ * Two launches on `stream`: the relevance scores (the first launch of ivr_index_rescore), then one workgroup per query that keeps R, m,
+ * the rows and a state byte of its candidates in LDS (13 bytes each) and runs the k steps: pick the best candidate, then score the
+ * chosen row, read from the storage tiles as it lies, against the candidates still in play.  P is scored lazily, k kc d multiply-adds
+ * per query instead of kc kc d; the steps of a query are sequential on one compute unit, so a single query at large k is the worst
+ * case.  Scratch: 4 bytes per (query, candidate), grow-only.  Enqueue-only once the scratch has grown (a call that grows it allocates);
+ * not graph-capturable then.  The same bits on every run and stream. */
+#define IVR_DIVERSE_MMR      0
+#define IVR_DIVERSE_SUPPRESS 1
+int ivr_index_diversify(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, const int64_t *cand /*DEV [nq][kc]*/, int kc, int k,
+                        int mode, float param, int normalize_q, float *D /*DEV [nq][k]*/, int64_t *I /*DEV [nq][k]*/,
+                        float *M /*DEV [nq][k] or NULL*/, ivr_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@
 //                                 coded-index structs themselves are in search_coded.h)
 // Users: search_index.hip (the index object and its storage), search.hip (group-maximum scans and the top-k driver), search_range.hip,
 // search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_events.hip, search_groups.hip,
-// search_ivf.hip and the other list scans, and through self_join.h cluster.hip and knn.hip.
+// search_diverse.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip and knn.hip.
 #pragma once
 #include "ivr_common.h"
 
@@ -343,6 +343,8 @@ struct ivr_index {
     DevBuf<uint64_t> gr_best;        // DEV [queries of a chunk][nseg]: the greatest (ordered score, ~row) of each segment, 0 = no row
     DevBuf<int64_t> gr_rows;         // DEV [queries of a chunk][G]: the best row of each chosen group (-1: unused), then as many floats
     DevBuf<uint64_t> gr_lists;       // DEV [queries of a chunk][G][pieces][4 waves][g]: the partial row lists, at most IVR_SEQ_CHUNK_SLOTS keys
+    // diversified search (ivr_index_diversify, search_diverse.hip); grow-only
+    DevBuf<float> dv_scores;         // DEV [nq][kc]: the relevance score of every candidate, -FLT_MAX for an absent one
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity
@@ -410,6 +412,11 @@ int ivr_launch_tile_rows(ivr_index *x, float *dst, const float *src, int64_t sta
 // search_rows.hip.  out[i] = stored row row_base + rows[i] (row-major float32); NaN rows for negative entries and for rows outside
 // [0, ntotal); the caller holds x->mu
 int ivr_launch_gather(ivr_index *x, const int64_t *rows, int64_t row_base, int64_t n, float *out, hipStream_t s);
+// search_refine.hip.  The first launch of ivr_index_rescore for the diversified search too: stages the queries in x->qtiled and scores
+// every (query, candidate) pair -> keys [nq][kc] (ordered score, ~row; 0 for an absent entry) and / or D_all [nq][kc] (-FLT_MAX for an
+// absent entry), either may be NULL.  The caller holds x->mu, has checked the sizes and launches nothing on an empty index
+int ivr_launch_refine_score(ivr_index *x, const float *q, int nq, const int64_t *cand, int kc, int normalize_q, uint64_t *keys, float *D_all,
+                            hipStream_t s);
 // search.hip.  The search of ivr_index_search_filtered over view v that also leaves the row behind every result slot in x->rpos (DEV
 // [nq][k]: its number in the view, -1 for an unused slot); the caller holds x->mu
 int ivr_search_view_pos(ivr_index *x, const View &v, const float *q, int nq, int k, int normalize_q, float *D, int64_t *I, hipStream_t s);

@@ -114,6 +114,25 @@ int order_threads(int P) { return P <= 512 ? 256 : 1024; }
 
 }  // namespace
 
+// search_internal.h.  Stages the queries and launches refine_score over the whole lists
+int ivr_launch_refine_score(ivr_index *x, const float *q, int nq, const int64_t *cand, int kc, int normalize_q, uint64_t *keys, float *D_all,
+                            hipStream_t s) {
+    int rc = ivr_reserve_queries(x, (int)ivr_ceil_div(nq, 16));
+    if (rc != IVR_OK) return rc;
+    rc = ivr_launch_tile_rows(x, x->qtiled, q, 0, nq, normalize_q, nullptr, s);
+    if (rc != IVR_OK) return rc;
+    const int64_t nall = (int64_t)nq * kc;
+    const int groups = (int)ivr_ceil_div(kc, 16);
+    const int64_t nwaves = (int64_t)nq * groups;
+    // algorithmic bytes: every candidate row once + its table entry, key and score (the lines that move are 16 times the rows)
+    IvrProf prof("refine_score", s, (double)nall * x->dp * 4 + (double)nall * 20);
+    const RefineScore a{reinterpret_cast<const float4 *>(x->data), reinterpret_cast<const float4 *>((const float *)x->qtiled), x->dp4, x->ntotal,
+                        cand, kc, groups, nwaves, keys, D_all};
+    hipLaunchKernelGGL(refine_score_kernel, dim3((unsigned)ivr_ceil_div(nwaves, 4)), dim3(256), 0, s, a);
+    IVR_LAUNCH_CHECK();
+    return IVR_OK;
+}
+
 extern "C" {
 
 int ivr_index_rescore(ivr_index *x, const float *q, int nq, const int64_t *cand, int kc, int k, int normalize_q, float *D_all, float *D,
@@ -134,21 +153,10 @@ int ivr_index_rescore(ivr_index *x, const float *q, int nq, const int64_t *cand,
         IVR_LAUNCH_CHECK();
         return IVR_OK;
     }
-    int rc = ivr_reserve_queries(x, (int)ivr_ceil_div(nq, 16));
-    if (rc == IVR_OK && D) rc = ivr_reserve({{&x->refine_keys, (size_t)nall * 8}});
+    int rc = D ? ivr_reserve({{&x->refine_keys, (size_t)nall * 8}}) : IVR_OK;
     if (rc != IVR_OK) return rc;
-    rc = ivr_launch_tile_rows(x, x->qtiled, q, 0, nq, normalize_q, nullptr, s);
+    rc = ivr_launch_refine_score(x, q, nq, cand, kc, normalize_q, D ? (uint64_t *)x->refine_keys : nullptr, D_all, s);
     if (rc != IVR_OK) return rc;
-    const int groups = (int)ivr_ceil_div(kc, 16);
-    const int64_t nwaves = (int64_t)nq * groups;
-    {
-        // algorithmic bytes: every candidate row once + its table entry, key and score (the lines that move are 16 times the rows)
-        IvrProf prof("refine_score", s, (double)nall * x->dp * 4 + (double)nall * 20);
-        const RefineScore a{reinterpret_cast<const float4 *>(x->data), reinterpret_cast<const float4 *>((const float *)x->qtiled), x->dp4, x->ntotal,
-                            cand, kc, groups, nwaves, D ? (uint64_t *)x->refine_keys : nullptr, D_all};
-        hipLaunchKernelGGL(refine_score_kernel, dim3((unsigned)ivr_ceil_div(nwaves, 4)), dim3(256), 0, s, a);
-        IVR_LAUNCH_CHECK();
-    }
     if (D) {
         int P = 2;
         while (P < kc) P <<= 1;

@@ -26,6 +26,7 @@ IVR_KNN_MAX_K = 64
 IVR_GROUP_MAX_ROWS = 64
 IVR_PHASH_MAX_SIDE = 8192
 IVR_KEEPWIN_MAX_WINDOW = 64
+IVR_DIVERSE_MMR, IVR_DIVERSE_SUPPRESS = 0, 1              # mode of ivr_index_diversify
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -202,6 +203,7 @@ _SIGS = {
     "ivr_kept_window_mask": (_i, [_p, _p, _i64, _i, _p, _i, _f, _i, _p, _p]),
     "ivr_frame_quality_scratch_bytes": (_i64, [_i, _i, _i]),
     "ivr_frame_quality": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ivr_index_diversify": (_i, [_p, _p, _i, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p]),
 }
 EXPORTS = tuple(_SIGS)
 # the exports that return a value; every other one returns a status that call() hands to check()
@@ -227,7 +229,8 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_pqfs_index_get_codes", "ivr_pqfs_index_search", "ivr_graph_set_rows", "ivr_graph_prune",
     "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
-    "ivr_scene_keep_mask_window", "ivr_frame_quality", "ivr_resize_u8", "ivr_phash", "ivr_hash_keep_mask", "ivr_kept_window_mask")}
+    "ivr_scene_keep_mask_window", "ivr_frame_quality", "ivr_resize_u8", "ivr_phash", "ivr_hash_keep_mask", "ivr_kept_window_mask",
+    "ivr_index_diversify")}
 
 _lib = None
 _lock = threading.Lock()

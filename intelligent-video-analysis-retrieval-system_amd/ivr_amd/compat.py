@@ -559,6 +559,22 @@ class FAISSRetriever:
                         results.append(SearchResult(metadata=md, similarity_score=s, rank=rank + 1, query_relevance=s))
             return results
 
+    def _frame_results(self, qn, idxs, validate_results):
+        """One result list of search_grouped / search_diverse: the rows idxs (-1: unused) as SearchResult, rank = the place in idxs."""
+        results = []
+        for rank, idx in enumerate(idxs):
+            idx = int(idx)
+            if idx >= 0 and idx in self.id_to_metadata:
+                md = self.id_to_metadata[idx]
+                if validate_results:
+                    try:
+                        md._validate()
+                    except Exception:
+                        continue
+                s = self._calculate_proper_similarity(qn, md.clip_features)
+                results.append(SearchResult(metadata=md, similarity_score=s, rank=rank + 1, query_relevance=s))
+        return results
+
     def search_grouped(self, query_features, n_groups: int = 10, group_size: int = 3, validate_results=True) -> List[List[SearchResult]]:
         """Not in the reference: the n_groups best VIDEOS of the first query row, each a list of its group_size best frames as
         SearchResult (rank = the frame's place inside its video), best video first.  A video is a run of equal folder_name in the
@@ -582,23 +598,31 @@ class FAISSRetriever:
             except Exception as e:
                 raise RuntimeError(f"Search operation failed: {e}")
             qn = q[0].cpu().numpy()
-            groups = []
-            for idxs in indices:
-                results = []
-                for rank, idx in enumerate(idxs):
-                    idx = int(idx)
-                    if idx >= 0 and idx in self.id_to_metadata:
-                        md = self.id_to_metadata[idx]
-                        if validate_results:
-                            try:
-                                md._validate()
-                            except Exception:
-                                continue
-                        s = self._calculate_proper_similarity(qn, md.clip_features)
-                        results.append(SearchResult(metadata=md, similarity_score=s, rank=rank + 1, query_relevance=s))
-                if results:
-                    groups.append(results)
-            return groups
+            groups = [self._frame_results(qn, idxs, validate_results) for idxs in indices]
+            return [results for results in groups if results]
+
+    def search_diverse(self, query_features, k: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, validate_results=True) -> List[SearchResult]:
+        """Not in the reference: the k hits of the first query row by maximal marginal relevance over its fetch_k best frames
+        (ivr_amd.diversify.mmr_search; LangChain's max_marginal_relevance_search), in the order chosen (rank = that order).
+        lambda_mult = 1 is search(); lower values trade relevance for frames that do not look like the ones already chosen.
+        Scores get the post-processing of search()."""
+        if not self.is_trained or not self.index:
+            raise RuntimeError("Index not trained. Call build_index first.")
+        if len(self.id_to_metadata) == 0:
+            return []
+        from .diversify import mmr_search_device
+        with self._lock:
+            q = self._normalize_and_validate_features(query_features)
+            if q.shape[1] != self.dimension:
+                raise ValueError(f"Query dimension ({q.shape[1]}) != index dimension ({self.dimension})")
+            try:
+                _, I, _ = mmr_search_device(self.index, q[:1], k, max(int(fetch_k), int(k)), lambda_mult)
+                indices = I[0].cpu().numpy()
+            except ValueError:
+                raise
+            except Exception as e:
+                raise RuntimeError(f"Search operation failed: {e}")
+            return self._frame_results(q[0].cpu().numpy(), indices, validate_results)
 
     def save_index(self, index_path: str, validate_before_save: bool = True) -> None:
         """core.py:960: <index_path>/index.faiss (flat FAISS container, ivr_amd.faiss_io) + metadata.json."""
