@@ -1045,6 +1045,59 @@ int ivr_index_diversify(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, c
                         int mode, float param, int normalize_q, float *D /*DEV [nq][k]*/, int64_t *I /*DEV [nq][k]*/,
                         float *M /*DEV [nq][k] or NULL*/, ivr_stream stream);
 
+/* ---- fused search: one ranking of the stored rows from a set of query vectors per query ---------------
+ * Several expansions of one text, a text and an example image, "like these frames but not like that one", "all of these concepts in
+ * one frame": every other search ranks the rows against ONE vector per query, and joining m result lists on the host invents a score
+ * for a row that misses a list and, for a minimum, looks in the wrong place altogether.  Here every stored row is scored against every
+ * member and folded in registers; the result is exact over all rows.  This is the library's own definition (vector stores have
+ * relatives: multi-vector queries, Qdrant's recommend API with its best_score strategy), not parity with any of them.
+ * q: DEV float32 [nq][slots][d], slots one of 1, 2, 4, 8, 16 (IVR_FUSE_MAX_MEMBERS): the member vectors of fused query f are rows
+ * f * slots .. f * slots + slots - 1.  w: DEV float32 [nq][slots], every entry finite.  role: DEV int8 [nq][slots]: 1 a positive member,
+ * -1 a negative one, 0 an absent slot (its vector and weight are not used; pass zeros).  Every set needs a positive member.
+ *   member score  S[j, r] = the float32 inner product ivr_index_search reports for (member j, stored row r), to the bit (-0.0 as +0.0)
+ *   T[j]          = w[j] * S[j, r]: one float32 product, rounded on its own, never fused with what follows
+ *   P             the fold of T over the positive members.  IVR_FUSE_MAX: the maximum (expansion, OR).  IVR_FUSE_MIN: the minimum (AND).
+ *                 IVR_FUSE_SUM: the balanced pairwise tree over the `slots` slots of the set, ((T0 + T1) + (T2 + T3)) + ..., in which a
+ *                 slot that is absent or negative contributes +0.0f: NOT an ascending sum, and the same set staged at another `slots` or
+ *                 in another slot order may differ in the last bit
+ *   Nn            the maximum of T over the negative members
+ *   F             a set without negative members: P.  IVR_FUSE_MARGIN: P - Nn, one float32 subtraction.  IVR_FUSE_VETO: P when P > Nn,
+ *                 else -(Nn * Nn), one product and one negation: a row that resembles a negative example at least as much as any
+ *                 positive one sinks, the further the more it resembles it
+ *   order         rows rank by (F descending, -0.0 equal to +0.0; row ascending), the result key of every top-k of the library
+ * Results are labelled with the row, or with its stored id on an id-mapped index; scores are written as every search writes them
+ * (-0.0 as +0.0).  normalize_q scales every member vector to unit length first, as everywhere else.
+ * ivr_index_search_fused: D / I DEV [nq][k], the k best rows of each fused query; unused slots (-FLT_MAX, -1).  1 <= k <= IVR_MAX_K.
+ * ivr_index_range_search_fused: every row with F >= threshold, in the form of ivr_index_range_search_sequences: lims DEV int64
+ * [nq + 1], lims[0] = 0, the rows of fused query f at [lims[f], lims[f + 1]) in ascending row order; entries at positions >= cap are
+ * counted but not written.  A NaN threshold is IVR_ERR_INVALID (+-inf are allowed).
+ * IVR_ERR_INVALID with a message in ivr_last_error, before anything is launched: slots not one of 1, 2, 4, 8, 16; nq < 1; nq * slots
+ * >= 2^31; an unknown fold or combine; k outside [1, IVR_MAX_K]; a role outside {1, -1, 0}; a weight that is not finite; a set without
+ * a positive member; ntotal >= 2^31.  An empty index gives unused slots / lims of zeros.
+ *
+ * Launches per chunk of fused queries, all on `stream`: the score pass of the clip search, whose epilogue writes no score: a set is an
+ * aligned group of `slots` columns of the 16-column query tile, each lane forms T for its column, the positive and the negative
+ * accumulator are folded across the set with log2(slots) cross-lane exchanges, and one lane per set writes the 64-bit keys of its four
+ * rows into the fused query's stretch of the key scratch; then the top-k selection over the stretch, or the count / prefix / write
+ * passes of the range form with the running total carried on the device.  Scratch on the index, grow-only: 8 bytes per (fused query of
+ * a chunk, stored row rounded up to 16) with at most IVR_SEQ_CHUNK_SLOTS slots per chunk, in whole query tiles (one tile = 16 / slots
+ * fused queries at least, 4,096 columns at most).  The role and weight tables are checked on the host: the call copies them back (5
+ * bytes per slot) and waits for `stream` once, before its first launch; after that it only enqueues (a call that grows the scratch
+ * allocates).  Not graph-capturable.  The same bits on every run and stream. */
+#define IVR_FUSE_MAX_MEMBERS 16
+#define IVR_FUSE_MAX    0
+#define IVR_FUSE_MIN    1
+#define IVR_FUSE_SUM    2
+#define IVR_FUSE_MARGIN 0
+#define IVR_FUSE_VETO   1
+int ivr_index_search_fused(ivr_index *idx, const float *q /*DEV [nq*slots,d]*/, int nq, int slots, const float *w /*DEV [nq*slots]*/,
+                           const int8_t *role /*DEV [nq*slots]: 1, -1, 0*/, int fold, int combine, int k, int normalize_q,
+                           float *D /*DEV [nq,k]*/, int64_t *I /*DEV [nq,k]*/, ivr_stream stream);
+int ivr_index_range_search_fused(ivr_index *idx, const float *q /*DEV [nq*slots,d]*/, int nq, int slots, const float *w /*DEV [nq*slots]*/,
+                                 const int8_t *role /*DEV [nq*slots]: 1, -1, 0*/, int fold, int combine, float threshold, int normalize_q,
+                                 int64_t *lims /*DEV [nq+1]*/, float *D /*DEV [cap]*/, int64_t *I /*DEV [cap]*/, int64_t cap,
+                                 ivr_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

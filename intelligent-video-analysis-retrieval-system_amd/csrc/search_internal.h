@@ -16,7 +16,7 @@
 //                                 coded-index structs themselves are in search_coded.h)
 // Users: search_index.hip (the index object and its storage), search.hip (group-maximum scans and the top-k driver), search_range.hip,
 // search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_events.hip, search_groups.hip,
-// search_diverse.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip and knn.hip.
+// search_diverse.hip, search_fused.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip and knn.hip.
 #pragma once
 #include "ivr_common.h"
 
@@ -345,6 +345,10 @@ struct ivr_index {
     DevBuf<uint64_t> gr_lists;       // DEV [queries of a chunk][G][pieces][4 waves][g]: the partial row lists, at most IVR_SEQ_CHUNK_SLOTS keys
     // diversified search (ivr_index_diversify, search_diverse.hip); grow-only
     DevBuf<float> dv_scores;         // DEV [nq][kc]: the relevance score of every candidate, -FLT_MAX for an absent one
+    // fused search (ivr_index_search_fused, search_fused.hip), one chunk of fused queries; grow-only
+    DevBuf<uint64_t> fu_keys;        // DEV [fused queries of a chunk][ntotal rounded up to 16]: (ordered F, ~row), 0 for a padding row
+    DevBuf<int64_t> fu_off;          // DEV [fused queries of a chunk][4096-key blocks of a stretch]: hits of each block, then their output positions
+    DevBuf<int64_t> fu_total;        // DEV [1]: the running total of the range call, carried from chunk to chunk
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

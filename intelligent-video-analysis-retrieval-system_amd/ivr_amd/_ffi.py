@@ -27,6 +27,9 @@ IVR_GROUP_MAX_ROWS = 64
 IVR_PHASH_MAX_SIDE = 8192
 IVR_KEEPWIN_MAX_WINDOW = 64
 IVR_DIVERSE_MMR, IVR_DIVERSE_SUPPRESS = 0, 1              # mode of ivr_index_diversify
+IVR_FUSE_MAX_MEMBERS = 16
+IVR_FUSE_FOLD = {"max": 0, "min": 1, "sum": 2}            # fold / combine of ivr_index_search_fused
+IVR_FUSE_COMBINE = {"margin": 0, "veto": 1}
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -130,6 +133,8 @@ _SIGS = {
     "ivr_group_piece_rows": (_i, []),
     "ivr_index_search_groups": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ivr_index_best_per_segment": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p]),
+    "ivr_index_search_fused": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "ivr_index_range_search_fused": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _f, _i, _p, _p, _p, _i64, _p]),
     "ivr_index_dbscan": (_i, [_p, _f, _i, _p, _i, _p, _p, _p, _p]),
     "ivr_segment_best_cosine": (_i, [_p, _p, _i64, _p, _i, _i, _p, _p, _p, _p]),
     "ivr_knn_max_k": (_i, []),
@@ -230,7 +235,7 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
     "ivr_scene_keep_mask_window", "ivr_frame_quality", "ivr_resize_u8", "ivr_phash", "ivr_hash_keep_mask", "ivr_kept_window_mask",
-    "ivr_index_diversify")}
+    "ivr_index_diversify", "ivr_index_search_fused", "ivr_index_range_search_fused")}
 
 _lib = None
 _lock = threading.Lock()

@@ -624,6 +624,53 @@ class FAISSRetriever:
                 raise RuntimeError(f"Search operation failed: {e}")
             return self._frame_results(q[0].cpu().numpy(), indices, validate_results)
 
+    def search_fused(self, query_features_list, k: int = 50, fold: str = "max", weights=None, negative_features=None,
+                     validate_results=True) -> List[SearchResult]:
+        """Not in the reference as one call: ONE ranking from several query vectors (ivr_amd.fusion.fused_search), for one fused
+        query.  query_features_list: a list of [d] vectors or an array [m,d], e.g. the CLIP features of every expansion of the
+        user's text, or of a text and an example image; negative_features likewise ("not like this one", combine="margin").  It
+        replaces the loops of _search_llm_enhanced (system.py:1844-1866: one search per expansion, then merge_results, which
+        keeps one occurrence of every frame: fold="max" ranks a frame by its best expansion) and of _search_hybrid / _combine_search_results
+        (system.py:1893-1895: 0.7 / 0.3 weighted lists: fold="sum" with weights=[0.7, 0.3]).  Where it differs: the ranking is exact
+        over all stored rows, not a join of per-query top-k lists, so no frame is cut off by a list's length and none that misses
+        one list is counted there with score 0.  similarity_score is the fused score with the post-processing of search(): clamped
+        to [0, 1]; rank is the place in the fused ranking."""
+        if not self.is_trained or not self.index:
+            raise RuntimeError("Index not trained. Call build_index first.")
+        if len(self.id_to_metadata) == 0:
+            return []
+        from .fusion import fused_search_device
+        with self._lock:
+            def members(x):
+                t = self._normalize_and_validate_features(np.stack([np.asarray(v, np.float32).reshape(-1) for v in x])
+                                                          if isinstance(x, (list, tuple)) else x)
+                if t.shape[1] != self.dimension:
+                    raise ValueError(f"Query dimension ({t.shape[1]}) != index dimension ({self.dimension})")
+                return t.unsqueeze(0)
+            pos = members(query_features_list)
+            neg = members(negative_features) if negative_features is not None else None
+            w = None if weights is None else np.asarray(weights, np.float32).reshape(1, -1)
+            try:
+                D, I = fused_search_device(self.index, pos, k, fold=fold, weights=w, negatives=neg)
+                scores, indices = D[0].cpu().numpy(), I[0].cpu().numpy()
+            except ValueError:
+                raise
+            except Exception as e:
+                raise RuntimeError(f"Search operation failed: {e}")
+            results = []
+            for rank, (score, idx) in enumerate(zip(scores, indices)):
+                idx = int(idx)
+                if idx >= 0 and idx in self.id_to_metadata:
+                    md = self.id_to_metadata[idx]
+                    if validate_results:
+                        try:
+                            md._validate()
+                        except Exception:
+                            continue
+                    s = max(0.0, min(1.0, float(score)))
+                    results.append(SearchResult(metadata=md, similarity_score=s, rank=rank + 1, query_relevance=s))
+            return results
+
     def save_index(self, index_path: str, validate_before_save: bool = True) -> None:
         """core.py:960: <index_path>/index.faiss (flat FAISS container, ivr_amd.faiss_io) + metadata.json."""
         if not self.is_trained:
