@@ -595,6 +595,55 @@ int ivr_index_search_groups(ivr_index *idx, const float *q /*DEV [nq,d]*/, int n
 int ivr_index_best_per_segment(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, const int64_t *seg_off /*DEV [nseg+1] or NULL*/,
                                int nseg, int normalize_q, float *D /*DEV [nq,nseg]*/, int64_t *I /*DEV [nq,nseg]*/, ivr_stream stream);
 
+/* ---- moment search: ranked time intervals per query ------------------------------------------------------
+ * WHERE in a video does the query hold, and for how long?  A text query that matches a shot matches a run of adjacent keyframes: the
+ * row searches fill their list with that run, the grouped search collapses it to the video.  A moment is the run itself, "video X,
+ * frames 412 - 447", with its best frame: the scored form of the reference's unscored temporal_context (system.py:1967-1974).
+ * q: DEV float32 [nq,d].
+ *   frame score   S[q, r] = the float32 inner product ivr_index_search reports for (query q, stored row r), to the bit
+ *   segments      seg_off as for the grouped search: DEV int64 [nseg + 1], ascending, or NULL (nseg is not read, the index is one
+ *                 segment).  Empty segments are allowed; rows outside [seg_off[0], seg_off[nseg]) belong to nothing; offsets beyond
+ *                 ntotal are clipped
+ *   hot           row r is hot for q when it belongs to a segment and S[q, r] >= threshold (>=, as the clip search tests; a NaN score is
+ *                 never hot)
+ *   head          prev(r) = the greatest hot row below r.  A hot row is a head when prev(r) is none, lies in another segment, or
+ *                 r - prev(r) > max_gap + 1: more than max_gap cold rows lie between them.  max_gap = 0: runs of consecutive hot rows
+ *   moment        a head and the hot rows behind it up to the next head: lo = the head, hi = its last hot row (inclusive), cnt = its
+ *                 hot rows, peak = its best hot row by (ordered S, ~row), the result key of every top-k of the library: score descending,
+ *                 equal scores the LOWER row, -0.0 equal to +0.0
+ * Per moment: D = S[q, peak] + 0.0f, I = the peak as a row number, or as its stored id on an id-mapped index; Lo, Hi and Cnt are
+ * always row numbers and counts.
+ * ivr_index_range_search_moments: every moment of every query in ascending lo, in the lims / cap contract of ivr_index_range_search:
+ * lims DEV int64 [nq + 1], the moments of query i at positions lims[i] .. lims[i + 1]; entries at positions >= cap are counted and not
+ * written.  D / I / Lo / Hi / Cnt DEV [cap] (never NULL, even for cap 0).
+ * ivr_index_search_moments: per query the best k moments among those with cnt >= min_count, D / I / Lo / Hi / Cnt DEV [nq][k].
+ * IVR_MOMENT_RANK_PEAK ranks by the peak key (equal scores: the lower peak row first), IVR_MOMENT_RANK_COUNT by cnt descending (equal
+ * counts: the lower lo first).  Unused slots hold -FLT_MAX / -1 / -1 / -1 / 0.
+ * nq >= 1, threshold not NaN, 0 <= max_gap <= 2^31 - 2, min_count >= 1, 1 <= k <= IVR_MAX_K, cap >= 0, nseg >= 1 with seg_off,
+ * ntotal < 2^31; anything else is IVR_ERR_INVALID.  An empty index yields unused slots and lims of zeros.
+ *
+ * Launches, all on `stream`, no host round trip: the row -> segment table once per call; then per chunk of queries the score pass of
+ * the clip search, a count pass (one workgroup per (query, block of ivr_moment_block_rows() rows): first hot row, last hot row and
+ * the heads behind the first), a prefix pass per query (the prev every block enters with, the number of its first moment), the
+ * totals (lims; the running total stays on the device from chunk to chunk), a fill of the chunk's moments with 0, the write pass (the
+ * count pass's grid: every hot row learns its moment, a block folds each of its moments in LDS and contributes once per moment: plain
+ * stores for a moment that lies inside the block, integer atomic maxima and sums for the two that may not), and the tail: a decode
+ * pass (range), or the top-k selection over the rank keys and a gather.  Only integer maxima and sums cross workgroups, so the result
+ * has the same bits on every run and stream; no launch waits on another workgroup.  The cost does not depend on max_gap.  Scratch on
+ * the index, grow-only: 4 bytes per (query of a chunk, row), 16 per (query of a chunk, block), 24 per moment a chunk may hold (per
+ * query min(ntotal, ntotal / (max_gap + 2) + nseg)), 12 per result slot.  A chunk holds whole 16-query tiles, as many queries as keep
+ * the scores within IVR_SEQ_CHUNK_SLOTS floats (16 at least, 2048 at most).  Enqueue-only, no host synchronisation, once the scratch
+ * has grown (a call that grows it allocates); not graph-capturable then. */
+#define IVR_MOMENT_RANK_PEAK  0
+#define IVR_MOMENT_RANK_COUNT 1
+int ivr_moment_block_rows(void);   /* rows one workgroup of the run passes covers: tests size their cases from it */
+int ivr_index_search_moments(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg,
+                             float threshold, int max_gap, int min_count, int rank, int k, int normalize_q,
+                             float *D /*DEV [nq,k]*/, int64_t *I /*DEV [nq,k]*/, int64_t *Lo, int64_t *Hi, int64_t *Cnt, ivr_stream stream);
+int ivr_index_range_search_moments(ivr_index *idx, const float *q, int nq, const int64_t *seg_off, int nseg, float threshold, int max_gap,
+                                   int normalize_q, int64_t *lims /*DEV [nq+1]*/, float *D /*DEV [cap]*/, int64_t *I, int64_t *Lo,
+                                   int64_t *Hi, int64_t *Cnt, int64_t cap, ivr_stream stream);
+
 /* ---- frame clustering: DBSCAN over the stored rows of the flat index ----------------------------------
  * Which stored frames are the same shot?  The reference's AdvancedKeyframeExtractor.cluster_similar_frames
  * (filter_research_update.py:113-134: sklearn DBSCAN on the precomputed 1 - cosine matrix) without the N x N matrix: a tiled self-join

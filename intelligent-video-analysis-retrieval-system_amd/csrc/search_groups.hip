@@ -68,6 +68,21 @@ __global__ __launch_bounds__(256) void grp_rowseg_kernel(int n, int64_t nrows, c
     rowseg[i] = s;
 }
 
+}  // namespace
+
+// search_internal.h: the table as the grouped search and the moment search (search_moments.hip) launch it
+int ivr_launch_rowseg(ivr_index *x, const int64_t *seg_off, int nseg, hipStream_t s) {
+    const int64_t nrows = ivr_ceil_div(x->ntotal, 16) * 16;
+    const int rc = ivr_reserve({{&x->gr_seg, (size_t)nrows * 4}});
+    if (rc != IVR_OK) return rc;
+    hipLaunchKernelGGL(grp_rowseg_kernel, dim3((unsigned)ivr_ceil_div(nrows, 256)), dim3(256), 0, s, (int)x->ntotal, nrows, seg_off, seg_off ? nseg : 1,
+                       x->gr_seg);
+    IVR_LAUNCH_CHECK();
+    return IVR_OK;
+}
+
+namespace {
+
 struct GrBest {
     const float4 *data;          // the float32 tiles of the storage
     const float4 *qtile;         // the first 16-query tile of the chunk in the tiled query buffer
@@ -344,7 +359,6 @@ int grp_search(const char *what, ivr_index *x, const GrArgs &a, hipStream_t s) {
     const int64_t slots = cb * std::max(a.G, 1);
     int rc = ivr_reserve_queries(x, (int)ivr_ceil_div(a.nq, 16));
     // each buffer grows on its own: calls of different shapes must not shrink one another's scratch
-    if (rc == IVR_OK) rc = ivr_reserve({{&x->gr_seg, (size_t)ntiles * 16 * 4}});
     if (rc == IVR_OK) rc = ivr_reserve({{&x->gr_best, (size_t)cb * nseg * 8}});
     if (rc == IVR_OK && a.G) rc = ivr_reserve({{&x->gr_rows, (size_t)slots * 12}});
     if (rc == IVR_OK && rows_pass) rc = ivr_reserve({{&x->gr_lists, (size_t)slots * per_slot * 8}});
@@ -353,8 +367,8 @@ int grp_search(const char *what, ivr_index *x, const GrArgs &a, hipStream_t s) {
     if (rc != IVR_OK) return rc;
     rc = ivr_launch_tile_rows(x, x->qtiled, a.q, 0, a.nq, a.normalize_q, nullptr, s);
     if (rc != IVR_OK) return rc;
-    hipLaunchKernelGGL(grp_rowseg_kernel, dim3((unsigned)ivr_ceil_div(ntiles * 16, 256)), dim3(256), 0, s, n, ntiles * 16, a.seg_off, nseg, x->gr_seg);
-    IVR_LAUNCH_CHECK();
+    rc = ivr_launch_rowseg(x, a.seg_off, nseg, s);
+    if (rc != IVR_OK) return rc;
     const int64_t *ids = x->has_ids ? x->ids : nullptr;
     const float4 *data = reinterpret_cast<const float4 *>(x->data), *qtiled = reinterpret_cast<const float4 *>((const float *)x->qtiled);
     int64_t *rows = x->gr_rows;

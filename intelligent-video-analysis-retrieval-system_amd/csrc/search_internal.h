@@ -16,7 +16,7 @@
 //                                 coded-index structs themselves are in search_coded.h)
 // Users: search_index.hip (the index object and its storage), search.hip (group-maximum scans and the top-k driver), search_range.hip,
 // search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_events.hip, search_groups.hip,
-// search_diverse.hip, search_fused.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip and knn.hip.
+// search_moments.hip, search_diverse.hip, search_fused.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip and knn.hip.
 #pragma once
 #include "ivr_common.h"
 
@@ -349,6 +349,13 @@ struct ivr_index {
     DevBuf<uint64_t> fu_keys;        // DEV [fused queries of a chunk][ntotal rounded up to 16]: (ordered F, ~row), 0 for a padding row
     DevBuf<int64_t> fu_off;          // DEV [fused queries of a chunk][4096-key blocks of a stretch]: hits of each block, then their output positions
     DevBuf<int64_t> fu_total;        // DEV [1]: the running total of the range call, carried from chunk to chunk
+    // moment search (ivr_index_search_moments, search_moments.hip), one chunk of queries; grow-only.  The frame scores go to seq_scores,
+    // the row -> segment table to gr_seg
+    DevBuf<int32_t> mo_blk;          // DEV [queries of a chunk][row blocks][4]: first hot row, last hot row, heads, then the prev it enters with
+    DevBuf<int64_t> mo_q;            // DEV [queries of a chunk][2]: the moments of each query, then the number of its first moment in the chunk;
+                                     // behind them int64 [3]: the running total of the call, the total in front of the chunk, the chunk's moments
+    DevBuf<uint64_t> mo_mom;         // DEV, 24 bytes per moment a chunk may hold: peak keys (uint64), lo (int64), hi (int32), cnt (int32), one array each
+    DevBuf<int64_t> mo_rows;         // DEV [queries of a chunk][k]: the low word of every chosen rank key (-1: unused), then as many floats
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity
@@ -435,6 +442,10 @@ void ivr_launch_fast_scan(ivr_index *x, const View &v, int qt, int64_t tile0, hi
 // x->qtiled against every stored row -> x->seq_scores [16 qtiles][ntotal rounded up to 16], line f = frame 16 qtile0 + f.  The caller
 // holds x->mu, has reserved seq_scores and keeps ceil(ntotal / 1024) * qtiles below 2^31 (the grid)
 int ivr_launch_seq_score(ivr_index *x, int qtile0, int qtiles, hipStream_t s);
+// search_groups.hip.  The segment number of every stored row -> x->gr_seg [ntotal rounded up to 16] (reserved here): -1 in front of
+// seg_off[0], nseg behind seg_off[nseg] and for the padding rows, 0 for every stored row without seg_off (nseg is then taken as 1).
+// The caller holds x->mu
+int ivr_launch_rowseg(ivr_index *x, const int64_t *seg_off, int nseg, hipStream_t s);
 // search_sq.hip.  t int16 [nq][d] -> the int8 halves t = 128 h + l of the int8 MFMA scans, tiled per 16 queries: qh and ql
 // [qtiles][ksteps][64], zeros past d and past nq
 void ivr_launch_sq_stage(const int16_t *t, int nq, int d, int ksteps, int64_t qtiles, uint4 *qh, uint4 *ql, hipStream_t s);

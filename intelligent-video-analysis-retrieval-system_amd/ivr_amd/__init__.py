@@ -1,6 +1,6 @@
 """ivr_amd: the HIP-backed pieces of the retrieval system.  The submodules are imported by name (ivr_amd.index, ivr_amd.tower, ...);
 the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index, the product-quantisation (8- and 4-bit codes) and scalar-quantisation indexes
-and the clip search, the event search, the grouped search, the diversified search, the fused search, the frame clustering, the neighbour graph and the perceptual hash with its look-back filters are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
+and the clip search, the event search, the grouped search, the moment search, the diversified search, the fused search, the frame clustering, the neighbour graph and the perceptual hash with its look-back filters are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
 _IVF = ("IVFFlatIndex", "IndexIVFFlat", "SearchParametersIVF", "METRIC_INNER_PRODUCT", "METRIC_L2")
 _BINARY = ("BinaryFlatIndex", "IndexBinaryFlat", "IndexLSH", "lsh_rotation")
 _GRAPH = ("GraphFlatIndex", "IndexHNSWFlat", "SearchParametersHNSW", "graph_prune_ref", "graph_link_ref", "graph_build_ref",
@@ -18,6 +18,8 @@ _TEMPORAL = ("TemporalAnalyzer", "sequence_search", "sequence_search_device", "s
              "event_best_per_segment_ref")
 _GROUPING = ("group_search", "group_search_device", "best_per_segment", "best_per_segment_device", "group_search_ref",
              "best_per_segment_ref", "seg_off_from_labels")
+_MOMENTS = ("moment_search", "moment_search_device", "moment_range_search", "moment_range_search_device", "moments_ref",
+            "moment_search_ref", "moment_range_search_ref", "moment_block_rows")
 _DIVERSIFY = ("mmr_search", "mmr_search_device", "dedup_search", "dedup_search_device", "mmr_rerank", "mmr_rerank_device",
               "suppress_rerank", "suppress_rerank_device", "mmr_ref", "suppress_ref")
 _FUSION = ("fused_search", "fused_search_device", "fused_range_search", "fused_range_search_device", "fused_scores_ref",
@@ -28,7 +30,7 @@ _NEIGHBORS = ("knn_graph", "knn_graph_device", "knn_graph_ref", "similarity_grap
 _KEYFRAMES = ("phash", "phash_device", "phash_ref", "hash_keep_mask", "hash_keep_mask_device", "hash_keep_mask_ref", "kept_window_mask",
               "kept_window_mask_device", "kept_window_mask_ref", "select_keyframes", "select_keyframes_ref", "AdvancedKeyframeExtractor",
               "PerceptualHash")
-__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _PQFS + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL + _GROUPING + _DIVERSIFY + _FUSION + _CLUSTER + _NEIGHBORS + _KEYFRAMES)
+__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _PQFS + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL + _GROUPING + _MOMENTS + _DIVERSIFY + _FUSION + _CLUSTER + _NEIGHBORS + _KEYFRAMES)
 
 
 def __getattr__(name):
@@ -65,6 +67,9 @@ def __getattr__(name):
     if name in _GROUPING:
         from . import grouping
         return getattr(grouping, name)
+    if name in _MOMENTS:
+        from . import moments
+        return getattr(moments, name)
     if name in _DIVERSIFY:
         from . import diversify
         return getattr(diversify, name)

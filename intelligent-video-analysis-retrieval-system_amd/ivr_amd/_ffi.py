@@ -30,6 +30,7 @@ IVR_DIVERSE_MMR, IVR_DIVERSE_SUPPRESS = 0, 1              # mode of ivr_index_di
 IVR_FUSE_MAX_MEMBERS = 16
 IVR_FUSE_FOLD = {"max": 0, "min": 1, "sum": 2}            # fold / combine of ivr_index_search_fused
 IVR_FUSE_COMBINE = {"margin": 0, "veto": 1}
+IVR_MOMENT_RANK = {"peak": 0, "count": 1}                 # rank of ivr_index_search_moments
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -133,6 +134,9 @@ _SIGS = {
     "ivr_group_piece_rows": (_i, []),
     "ivr_index_search_groups": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ivr_index_best_per_segment": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p]),
+    "ivr_moment_block_rows": (_i, []),
+    "ivr_index_search_moments": (_i, [_p, _p, _i, _p, _i, _f, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "ivr_index_range_search_moments": (_i, [_p, _p, _i, _p, _i, _f, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "ivr_index_search_fused": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "ivr_index_range_search_fused": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _f, _i, _p, _p, _p, _i64, _p]),
     "ivr_index_dbscan": (_i, [_p, _f, _i, _p, _i, _p, _p, _p, _p]),
@@ -217,7 +221,7 @@ _VALUE = frozenset(("ivr_api_version", "ivr_last_error", "ivr_preprocess_scratch
                     "ivr_graph_max_ef", "ivr_graph_max_cand", "ivr_graph_ntotal", "ivr_frame_quality_scratch_bytes",
                     "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries", "ivr_ivfsq_ntotal",
                     "ivr_pqfs_pass_queries", "ivr_pqfs_index_ntotal", "ivr_knn_max_k", "ivr_knn_piece_rows",
-                    "ivr_phash_scratch_bytes", "ivr_group_piece_rows"))
+                    "ivr_phash_scratch_bytes", "ivr_group_piece_rows", "ivr_moment_block_rows"))
 # the slot of the ivr_stream argument (the last one wherever there is one): call() fills it when the caller leaves it out
 _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_release_stream_scratch", "ivr_preprocess", "ivr_tower_encode_image", "ivr_tower_encode_text", "ivr_tower_debug_hidden",
@@ -235,7 +239,8 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_graph_set_neighbors", "ivr_graph_search", "ivr_topk_merge",
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
     "ivr_scene_keep_mask_window", "ivr_frame_quality", "ivr_resize_u8", "ivr_phash", "ivr_hash_keep_mask", "ivr_kept_window_mask",
-    "ivr_index_diversify", "ivr_index_search_fused", "ivr_index_range_search_fused")}
+    "ivr_index_diversify", "ivr_index_search_fused", "ivr_index_range_search_fused", "ivr_index_search_moments",
+    "ivr_index_range_search_moments")}
 
 _lib = None
 _lock = threading.Lock()

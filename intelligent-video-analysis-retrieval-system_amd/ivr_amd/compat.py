@@ -601,6 +601,41 @@ class FAISSRetriever:
             groups = [self._frame_results(qn, idxs, validate_results) for idxs in indices]
             return [results for results in groups if results]
 
+    def search_moments(self, query_features, k: int = 10, threshold: float = 0.25, max_gap: int = 1, min_count: int = 1,
+                       validate_results=True) -> List[SearchResult]:
+        """Not in the reference: the k best MOMENTS of the first query row (ivr_amd.moments.moment_search, rank="peak"): runs of
+        frames of one video that score `threshold` or more, bridging up to max_gap colder frames, with at least min_count such
+        frames.  The scored form of the reference's temporal_context (system.py:1967-1974: the +-3 neighbouring frames of a hit as
+        SearchResult(neighbor, 0.0, 0)).  Per moment the peak frame as a SearchResult (rank = the moment's place), with the
+        moment's first and last frame attached as its temporal_context in the reference's unscored form.  A video is a run of equal
+        folder_name in the metadata, as for search_grouped.  The threshold is tested on the raw cosine; the reported scores get
+        the post-processing of search()."""
+        if not self.is_trained or not self.index:
+            raise RuntimeError("Index not trained. Call build_index first.")
+        if len(self.id_to_metadata) == 0:
+            return []
+        from .grouping import seg_off_from_labels
+        from .moments import moment_search_device
+        with self._lock:
+            q = self._normalize_and_validate_features(query_features)
+            if q.shape[1] != self.dimension:
+                raise ValueError(f"Query dimension ({q.shape[1]}) != index dimension ({self.dimension})")
+            seg_off = seg_off_from_labels(self.id_to_metadata[i].folder_name for i in range(self.index.ntotal))
+            try:
+                _, I, Lo, Hi, _ = moment_search_device(self.index, q[:1], k, threshold, max_gap, min_count, "peak", seg_off=seg_off)
+                peaks, first, last = (t[0].cpu().numpy() for t in (I, Lo, Hi))
+            except ValueError:
+                raise
+            except Exception as e:
+                raise RuntimeError(f"Search operation failed: {e}")
+            results = self._frame_results(q[0].cpu().numpy(), peaks, validate_results)
+            ends = {int(p): (int(a), int(b)) for p, a, b in zip(peaks, first, last)}
+            row_of = {id(self.id_to_metadata[int(p)]): int(p) for p in peaks if int(p) in self.id_to_metadata}
+            for res in results:
+                res.temporal_context = [SearchResult(self.id_to_metadata[r], 0.0, 0) for r in ends[row_of[id(res.metadata)]]
+                                        if r in self.id_to_metadata]
+            return results
+
     def search_diverse(self, query_features, k: int = 10, fetch_k: int = 50, lambda_mult: float = 0.5, validate_results=True) -> List[SearchResult]:
         """Not in the reference: the k hits of the first query row by maximal marginal relevance over its fetch_k best frames
         (ivr_amd.diversify.mmr_search; LangChain's max_marginal_relevance_search), in the order chosen (rank = that order).
