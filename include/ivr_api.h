@@ -702,6 +702,47 @@ int ivr_knn_piece_rows(void);   /* stored rows one workgroup's piece of a walk c
 int ivr_index_knn_graph(ivr_index *idx, int k, const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, float threshold,
                         float *D /*DEV [ntotal][k]*/, int64_t *I /*DEV [ntotal][k]*/, int32_t *count /*DEV [ntotal]*/, ivr_stream stream);
 
+/* ---- zero-shot tagging: the best labels of every stored row with their softmax probabilities, and of every segment ----------
+ * CLIP's logits_per_image.softmax(dim=1) for the stored rows of the flat index against C label vectors (usually encoded texts): what
+ * fills the reference's KeyframeMetadata.scene_tags (core.py:101, add_semantic_tags core.py:3278) without its remote vision call.
+ *   labels      DEV float32 [C][d], 1 <= C <= IVR_TAG_MAX_LABELS; normalize: L2-normalised on the way in exactly as ivr_index_add does
+ *   score       S[j, i] = the float32 inner product an ivr_index holding the labels reports for (query = stored row j, stored row =
+ *               label i), to the bit
+ *   candidates  of row j: the labels whose S[j, i] is not NaN (+-inf scores are outside the definition); order: score descending,
+ *               equal scores the lower label
+ *   probability P[j, i] = exp(scale (S[j, i] - m_j)) / Z_j with m_j the best score of the row and Z_j the sum of the numerators over
+ *               ALL candidates, not only the listed ones.  exp is not reproducible to the bit elsewhere: P and Z lie within a stated
+ *               relative bound of the float64 value (ivr_amd/tagging.py, tag_prob_bound) and have the same bits on every run and stream
+ *   D, P, J     DEV float32 / float32 / int64 [ntotal][t]: score, probability and label number of the row's best t labels.  A slot is
+ *               used while P >= min_prob (P descends with the rank, so min_prob truncates); unused slots hold -FLT_MAX / 0 / -1
+ *   count, Z    DEV int32 / float32 [ntotal]: the used slots and Z_j (0 for a row without candidates)
+ *   rows        only rows [row0, min(row1, ntotal)) are computed and written, at their own lines of the outputs
+ * 1 <= t <= IVR_TAG_MAX_TOP.  IVR_ERR_INVALID: NULL handles, labels or outputs, C or t out of range, a scale that is not a positive
+ * finite number, a NaN min_prob, row0 < 0 or row0 > row1, ntotal >= 2^31.  An empty index or range succeeds and writes nothing.
+ * Cost: the stored rows of the range are read once, the label tiles once per block of up to 64 rows (from L2 / MALL).  Scratch on the
+ * index, grow-only: the tiled labels.  Two launches on the caller's stream, no host synchronisation once the scratch has grown.
+ *
+ * ivr_index_tag_segments reduces the rows' lists per segment (seg_off as for ivr_index_knn_graph; NULL: one segment):
+ *   votes[s][i] = the rows of segment s whose first label is i;  mass[s][i] = the sum over the rows of s and their used slots that
+ *   name i of rint(P 2^24) as an integer.  Integer sums: the same bits whatever the order.  The result is the top g <= IVR_TAG_MAX_TOP
+ *   labels of every segment by (mass or votes, per `rank`) descending, equal values the lower label, among the labels whose value is
+ *   not 0: L DEV int64 [nseg][g] (unused -1), mass DEV uint64 [nseg][g], votes DEV int32 [nseg][g] (unused 0), rows DEV int32 [nseg]
+ *   (the stored rows of each segment).  nseg x C may not exceed 2^25 table entries (IVR_ERR_INVALID beyond; 384 MiB of scratch at
+ *   the limit); the row lists go through a scratch of at most 2^24 slots, a larger index is walked in chunks of rows.  An empty index
+ *   succeeds and writes nothing. */
+#define IVR_TAG_MAX_LABELS 4096
+#define IVR_TAG_MAX_TOP 64
+#define IVR_TAG_RANK_MASS 0
+#define IVR_TAG_RANK_VOTES 1
+int ivr_tag_max_labels(void);
+int ivr_tag_max_top(void);
+int ivr_index_tag_rows(ivr_index *idx, const float *labels /*DEV [C][d]*/, int C, int normalize, float scale, int t, float min_prob,
+                       int64_t row0, int64_t row1, float *D /*DEV [ntotal][t]*/, float *P /*DEV [ntotal][t]*/, int64_t *J /*DEV [ntotal][t]*/,
+                       int32_t *count /*DEV [ntotal]*/, float *Z /*DEV [ntotal]*/, ivr_stream stream);
+int ivr_index_tag_segments(ivr_index *idx, const float *labels /*DEV [C][d]*/, int C, int normalize, float scale, int t, float min_prob,
+                           const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, int g, int rank, int64_t *L /*DEV [nseg][g]*/,
+                           uint64_t *mass /*DEV [nseg][g]*/, int32_t *votes /*DEV [nseg][g]*/, int32_t *rows /*DEV [nseg]*/, ivr_stream stream);
+
 /* ---- binary codes (faiss IndexBinaryFlat, and the sign-bit encoder of IndexLSH) --------------------------
  * Stands in for faiss.IndexLSH(dimension, 256), one of the index types of _create_index (core.py:1198-1230): a row is stored as
  * nbits sign bits (32 bytes at 256 bits, where the flat index stores 2-4.6 KB) and ranked by Hamming distance.

@@ -567,14 +567,15 @@ int ivr_launch_tile_rows(ivr_index *x, float *dst, const float *src, int64_t sta
     if (n <= 0) return IVR_OK;
     const int64_t ntiles = max_tiles ? max_tiles : ((start + n + 15) >> 4) - (start >> 4);
     const unsigned grid = (unsigned)ivr_ceil_div(ntiles, 4);
-    const bool rows = dst == x->data;
-    IvrProf prof("tile_rows", s, (double)n * (x->d + x->dp) * 4 + (x->scan16 ? (double)n * x->pieces * 64 * (rows ? 1 : 2) : 0.0), true);
+    const bool rows = dst == x->data, queries = dst == x->qtiled;
+    const bool scan16 = x->scan16 && (rows || queries);      // any other destination (the label tiles of tags.hip): float32 tiles alone
+    IvrProf prof("tile_rows", s, (double)n * (x->d + x->dp) * 4 + (scan16 ? (double)n * x->pieces * 64 * (rows ? 1 : 2) : 0.0), true);
     // query tiles: the padding rows of the last tile are zero-filled by the kernel itself (no memset in front of it)
     hipLaunchKernelGGL(tile_rows_kernel, dim3(grid), dim3(256), 0, s, src, dst, start, n, x->d, x->dp4, normalize, nonfinite, start_dev,
-                       x->scan16 ? (rows ? x->data16 : x->q16hi) : (uint4 *)nullptr, x->scan16 && !rows ? x->q16lo : (uint4 *)nullptr,
-                       x->scan16 && rows ? x->maxnorm : (unsigned int *)nullptr, rows ? (float *)nullptr : x->qnorm, rows ? 0 : 1,
-                       x->pieces, x->scan16 && rows ? x->maxdelta : (unsigned int *)nullptr,
-                       x->scan16 && !rows ? x->qdelta : (float *)nullptr);
+                       scan16 ? (rows ? x->data16 : x->q16hi) : (uint4 *)nullptr, scan16 && !rows ? x->q16lo : (uint4 *)nullptr,
+                       scan16 && rows ? x->maxnorm : (unsigned int *)nullptr, queries ? x->qnorm : (float *)nullptr, rows ? 0 : 1,
+                       x->pieces, scan16 && rows ? x->maxdelta : (unsigned int *)nullptr,
+                       scan16 && queries ? x->qdelta : (float *)nullptr);
     IVR_LAUNCH_CHECK();
     return IVR_OK;
 }

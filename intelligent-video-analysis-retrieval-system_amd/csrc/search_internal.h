@@ -16,7 +16,7 @@
 //                                 coded-index structs themselves are in search_coded.h)
 // Users: search_index.hip (the index object and its storage), search.hip (group-maximum scans and the top-k driver), search_range.hip,
 // search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_events.hip, search_groups.hip,
-// search_moments.hip, search_diverse.hip, search_fused.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip and knn.hip.
+// search_moments.hip, search_diverse.hip, search_fused.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip, knn.hip and tags.hip.
 #pragma once
 #include "ivr_common.h"
 
@@ -356,6 +356,10 @@ struct ivr_index {
                                      // behind them int64 [3]: the running total of the call, the total in front of the chunk, the chunk's moments
     DevBuf<uint64_t> mo_mom;         // DEV, 24 bytes per moment a chunk may hold: peak keys (uint64), lo (int64), hi (int32), cnt (int32), one array each
     DevBuf<int64_t> mo_rows;         // DEV [queries of a chunk][k]: the low word of every chosen rank key (-1: unused), then as many floats
+    // zero-shot tagging (ivr_index_tag_rows, ivr_index_tag_segments, tags.hip); grow-only, each on its own
+    DevBuf<float> tg_labels;         // DEV [C rounded up to 16][dp]: the labels in the storage-tile layout, zero rows behind the last
+    DevBuf<uint64_t> tg_table;       // DEV [nseg][C] uint64 mass, [nseg][C] int32 votes, [nseg] int32 rows: the segment tables of a call
+    DevBuf<uint64_t> tg_lists;       // DEV: J, D, P [rows of a chunk][t], then count and Z [rows of a chunk]: the row pass of the segment call
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity
@@ -417,7 +421,7 @@ int with_view(ivr_index *x, int64_t id_base, const ivr_id_filter *f, hipStream_t
 }
 
 // search_index.hip.  dst == x->data: index rows (bf16 scan copy + max norm alongside); dst == x->qtiled: queries (bf16 hi / lo split
-// alongside)
+// alongside); any other dst (tags.hip's label tiles): the float32 tiles alone, padding rows of the last tile zero-filled as for queries
 int ivr_launch_tile_rows(ivr_index *x, float *dst, const float *src, int64_t start, int64_t n, int normalize, int32_t *nonfinite,
                          hipStream_t s, const int64_t *start_dev = nullptr, int64_t max_tiles = 0);
 // search_rows.hip.  out[i] = stored row row_base + rows[i] (row-major float32); NaN rows for negative entries and for rows outside

@@ -1,5 +1,5 @@
 // The frame of the tiled self-joins over the flat index: frame clustering (cluster.hip) and the neighbour graph (knn.hip).  Not part of
-// the C ABI.
+// the C ABI.  tags.hip uses the staging and the scoring of a tile with a second matrix (the label tiles) as the streamed side.
 //
 // Score S[j, i] = <stored row j as the query, stored row i>, accumulated by stream_tile / mfma_chunk4 (search_internal.h), so it has
 // the bits ivr_index_search and ivr_index_rescore report for that pair.  The float32 storage tiles have the layout of the tiled query

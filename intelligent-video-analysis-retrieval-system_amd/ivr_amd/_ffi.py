@@ -23,6 +23,8 @@ IVR_SEQ_MAX_LEN = 64
 IVR_EVENT_MAX_LEN = 8
 IVR_EVENT_MAX_GAP = 4096
 IVR_KNN_MAX_K = 64
+IVR_TAG_MAX_LABELS, IVR_TAG_MAX_TOP = 4096, 64
+IVR_TAG_RANK = {"mass": 0, "votes": 1}                    # rank of ivr_index_tag_segments (_staging.check_tag_segments)
 IVR_GROUP_MAX_ROWS = 64
 IVR_PHASH_MAX_SIDE = 8192
 IVR_KEEPWIN_MAX_WINDOW = 64
@@ -144,6 +146,10 @@ _SIGS = {
     "ivr_knn_max_k": (_i, []),
     "ivr_knn_piece_rows": (_i, []),
     "ivr_index_knn_graph": (_i, [_p, _i, _p, _i, _f, _p, _p, _p, _p]),
+    "ivr_tag_max_labels": (_i, []),
+    "ivr_tag_max_top": (_i, []),
+    "ivr_index_tag_rows": (_i, [_p, _p, _i, _i, _f, _i, _f, _i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "ivr_index_tag_segments": (_i, [_p, _p, _i, _i, _f, _i, _f, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "ivr_bin_index_create": (_i, [_p, _i, _i64, C.POINTER(_p)]),
     "ivr_bin_index_destroy": (_i, [_p]),
     "ivr_bin_index_reset": (_i, [_p]),
@@ -221,7 +227,8 @@ _VALUE = frozenset(("ivr_api_version", "ivr_last_error", "ivr_preprocess_scratch
                     "ivr_graph_max_ef", "ivr_graph_max_cand", "ivr_graph_ntotal", "ivr_frame_quality_scratch_bytes",
                     "ivr_sq_index_ntotal", "ivr_ivfpq_ntotal", "ivr_ivfpq_probe_queries", "ivr_ivfsq_ntotal",
                     "ivr_pqfs_pass_queries", "ivr_pqfs_index_ntotal", "ivr_knn_max_k", "ivr_knn_piece_rows",
-                    "ivr_phash_scratch_bytes", "ivr_group_piece_rows", "ivr_moment_block_rows"))
+                    "ivr_phash_scratch_bytes", "ivr_group_piece_rows", "ivr_moment_block_rows", "ivr_tag_max_labels",
+                    "ivr_tag_max_top"))
 # the slot of the ivr_stream argument (the last one wherever there is one): call() fills it when the caller leaves it out
 _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_release_stream_scratch", "ivr_preprocess", "ivr_tower_encode_image", "ivr_tower_encode_text", "ivr_tower_debug_hidden",
@@ -240,7 +247,7 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
     "ivr_scene_keep_mask_window", "ivr_frame_quality", "ivr_resize_u8", "ivr_phash", "ivr_hash_keep_mask", "ivr_kept_window_mask",
     "ivr_index_diversify", "ivr_index_search_fused", "ivr_index_range_search_fused", "ivr_index_search_moments",
-    "ivr_index_range_search_moments")}
+    "ivr_index_range_search_moments", "ivr_index_tag_rows", "ivr_index_tag_segments")}
 
 _lib = None
 _lock = threading.Lock()

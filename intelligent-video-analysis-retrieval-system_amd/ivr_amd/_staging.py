@@ -150,6 +150,55 @@ def check_knn(k, threshold, kmax, what):
     return int(k), threshold
 
 
+def _is_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def check_tags(C, scale, top, min_prob, cmax, tmax, what):
+    """The parameters of a tagging call: C labels in [1, cmax], scale a positive finite number, top an integer in [1, tmax], min_prob a
+    number that is not NaN -> (float scale and float min_prob, both rounded to float32, int top)."""
+    if C < 1 or C > cmax:
+        raise ValueError(f"{what}: C={C} labels outside [1,{cmax}]")
+    if isinstance(top, bool) or not isinstance(top, (int, np.integer)):
+        raise ValueError(f"{what}: top must be an integer, got {type(top).__name__}")
+    if top < 1 or top > tmax:
+        raise ValueError(f"{what}: top={top} outside [1,{tmax}]")
+    if not _is_number(scale):
+        raise ValueError(f"{what}: scale must be a number, got {type(scale).__name__}")
+    scale = float(np.float32(scale))
+    if not (scale > 0.0 and scale != float("inf")):
+        raise ValueError(f"{what}: scale={scale} is not a positive finite number")
+    if not _is_number(min_prob):
+        raise ValueError(f"{what}: min_prob must be a number, got {type(min_prob).__name__}")
+    min_prob = float(np.float32(min_prob))
+    if min_prob != min_prob:
+        raise ValueError(f"{what}: min_prob={min_prob} is NaN")
+    return scale, int(top), min_prob
+
+
+def check_tag_segments(g, rank, gmax, what):
+    """top_labels an integer in [1, gmax], rank "mass" or "votes" -> (int g, the library's rank number)."""
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+        raise ValueError(f"{what}: top_labels must be an integer, got {type(g).__name__}")
+    if g < 1 or g > gmax:
+        raise ValueError(f"{what}: top_labels={g} outside [1,{gmax}]")
+    from ._ffi import IVR_TAG_RANK
+    if rank not in IVR_TAG_RANK:
+        raise ValueError(f"{what}: rank must be 'mass' or 'votes', got {rank!r}")
+    return int(g), IVR_TAG_RANK[rank]
+
+
+def check_row_range(row0, row1, n, what):
+    """A row range [row0, row1) of n rows, row1 None = n: integers with 0 <= row0 <= row1 -> (int row0, int row1 clipped to n)."""
+    row1 = n if row1 is None else row1
+    for name, r in (("row0", row0), ("row1", row1)):
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)):
+            raise ValueError(f"{what}: {name} must be an integer, got {type(r).__name__}")
+    if not 0 <= row0 <= row1:
+        raise ValueError(f"{what}: rows [{row0},{row1}) are no range")
+    return int(row0), int(min(row1, max(n, row0)))
+
+
 def alloc_DI(nq, k, device, dtype=torch.float32):
     """The (D, I) pair of a search: D `dtype` [nq,k], I int64 [nq,k]."""
     return torch.empty((nq, k), dtype=dtype, device=device), torch.empty((nq, k), dtype=torch.int64, device=device)

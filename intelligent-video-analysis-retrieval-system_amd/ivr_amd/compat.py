@@ -706,6 +706,56 @@ class FAISSRetriever:
                     results.append(SearchResult(metadata=md, similarity_score=s, rank=rank + 1, query_relevance=s))
             return results
 
+    def _tag_inputs(self, names, label_features):
+        names = list(names)
+        feats = np.asarray(label_features, dtype=np.float32)
+        if feats.ndim != 2 or feats.shape[0] != len(names) or feats.shape[1] != self.dimension:
+            raise ValueError(f"label_features must be [{len(names)},{self.dimension}], got {feats.shape}")
+        if not all(isinstance(n, str) and n.strip() for n in names):
+            raise ValueError("names must be non-empty strings")                    # add_semantic_tags drops such tags (core.py:3295)
+        return names, np.ascontiguousarray(feats)
+
+    def tag_frames(self, names, label_features, top: int = 5, min_prob: float = 0.1, scale: float = 100.0) -> Dict[str, List[str]]:
+        """Not in the reference, which leaves scene_tags to a remote vision call: zero-shot tags of every stored frame
+        (ivr_amd.tagging.tag_rows).  names[i] is the tag of label_features[i] (float32 [C,d], e.g. tagging.zero_shot_labels;
+        L2-normalised here).  A frame gets its `top` most probable labels with softmax probability >= min_prob, appended to
+        metadata.scene_tags as MetadataManager.add_semantic_tags does (core.py:3278-3298), duplicates removed.  One stated
+        departure: the reference's list(set(...)) loses the order; here the tags keep their order, most probable first behind
+        what the frame already carried.  Returns {unique key: the tags this call found for the frame, in rank order}."""
+        if not self.is_trained or not self.index:
+            raise RuntimeError("Index not trained. Call build_index first.")
+        from .tagging import tag_rows_device
+        with self._lock:
+            names, feats = self._tag_inputs(names, label_features)
+            _, _, J, count, _ = tag_rows_device(self.index, feats, top, scale, min_prob, normalize=True)
+            J, count = J.cpu().numpy(), count.cpu().numpy()
+            found = {}
+            for r in range(self.index.ntotal):
+                md = self.id_to_metadata.get(r)
+                if md is None:
+                    continue
+                tags = [names[i] for i in J[r, :count[r]].tolist()]
+                md.scene_tags = list(dict.fromkeys(list(md.scene_tags) + tags))     # duplicates out, order kept
+                found[md.get_unique_key()] = tags
+            return found
+
+    def tag_videos(self, names, label_features, top_labels: int = 5, rank: str = "mass", top: int = 5, min_prob: float = 0.1,
+                   scale: float = 100.0) -> Dict[str, List[Tuple[str, float]]]:
+        """Not in the reference: the tags of every VIDEO (ivr_amd.tagging.tag_segments): a video is a run of equal folder_name in the
+        metadata, as for search_grouped.  Returns {folder_name: [(tag, mean probability over the video's frames), ...]}, the
+        top_labels best by summed probability (rank="mass") or by the number of frames whose first tag it is (rank="votes")."""
+        if not self.is_trained or not self.index:
+            raise RuntimeError("Index not trained. Call build_index first.")
+        from .grouping import seg_off_from_labels
+        from .tagging import tag_segments
+        with self._lock:
+            names, feats = self._tag_inputs(names, label_features)
+            folders = [self.id_to_metadata[i].folder_name for i in range(self.index.ntotal)]
+            seg_off = seg_off_from_labels(folders)
+            L, _, _, _, mean = tag_segments(self.index, feats, seg_off, top_labels, rank, top, scale, min_prob, normalize=True)
+            return {folders[int(seg_off[s])]: [(names[i], float(p)) for i, p in zip(L[s].tolist(), mean[s].tolist()) if i >= 0]
+                    for s in range(len(seg_off) - 1) if seg_off[s] < seg_off[s + 1]}
+
     def save_index(self, index_path: str, validate_before_save: bool = True) -> None:
         """core.py:960: <index_path>/index.faiss (flat FAISS container, ivr_amd.faiss_io) + metadata.json."""
         if not self.is_trained:
