@@ -743,6 +743,56 @@ int ivr_index_tag_segments(ivr_index *idx, const float *labels /*DEV [C][d]*/, i
                            const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, int g, int rank, int64_t *L /*DEV [nseg][g]*/,
                            uint64_t *mass /*DEV [nseg][g]*/, int32_t *votes /*DEV [nseg][g]*/, int32_t *rows /*DEV [nseg]*/, ivr_stream stream);
 
+/* ---- video search: stored videos ranked against a SET of query vectors ------------------------------------
+ * Which stored videos look like this video or clip, whatever the order, frame rate or cut, and which contain all of these sub-queries
+ * somewhere?  Every other member of the seg_off family takes one vector per query.  Here both sides hold several: the measure is the
+ * two-sided reduction of the frame score matrix that vector stores ship for multi-vector documents as MaxSim / Chamfer similarity.
+ *   frame score   S[i, r] = the float32 inner product ivr_index_search reports for (member i, stored row r), to the bit, -0.0 counted
+ *                 as +0.0.  Precondition |S| <= 256; beyond it nothing faults and the result is unspecified
+ *   sets          set_off: DEV int64 [nsets + 1], ascending: set s is the members [set_off[s], set_off[s + 1]) of q, 1 <= m_s <=
+ *                 IVR_VIDEO_MAX_MEMBERS, 0 <= set_off[0], set_off[nsets] <= nq; NULL: all nq members are one set (nsets is not read).
+ *                 It is read back once before the first launch: the one host synchronisation of a call
+ *   videos        seg_off as for the grouped search: DEV int64 [nseg + 1], ascending, or NULL (one video); video j has the n_j rows of
+ *                 [seg_off[j], seg_off[j + 1]) that are stored rows
+ *   fix(t)        int64(rint(float32(t 2^24))): the fixed point of the tagging masses; the scaling is exact, so a term is rounded by at
+ *                 most 2^-25
+ *   Fsum[s, j]    the sum over the members i of s of fix(max over the rows r of j of S[i, r])
+ *   Bsum[s, j]    the sum over the rows r of j of fix(max over the members i of s of S[i, r])
+ *   V[s, j]       with F64 = double(Fsum) / (m_s 2^24) and B64 = double(Bsum) / (n_j 2^24): IVR_VIDEO_FORWARD float(F64) (MaxSim: "contains
+ *                 all of these"), IVR_VIDEO_BACKWARD float(B64), IVR_VIDEO_SYMMETRIC float((F64 + B64) 0.5) (Chamfer).  An empty video
+ *                 scores -FLT_MAX and is never ranked.  With m = 1, forward is the score of ivr_index_best_per_segment within 2^-25, not
+ *                 to the bit
+ *   order         videos rank by (V descending, video ascending) with the 64-bit key of every top-k of the library
+ * ivr_index_video_scores: V DEV float32 [nsets][nseg] (nseg = 1 without seg_off).  Replaces ivr_index_best_per_segment over every member
+ * plus ivr_index_tag_rows(t = 1) with the members as labels (whose IVR_TAG_MAX_LABELS caps the members of ALL sets together) plus a host
+ * reduction per video: two float32 passes over the index and a join.
+ * ivr_index_video_search: Vseg DEV int64 [nsets][k] and D DEV float32 [nsets][k], the k best videos of each set and their V; unused slots
+ * -1 / -FLT_MAX.  exclude: DEV int64 [nsets] or NULL, one video left out per set (any value that is no video leaves none out).  Replaces
+ * ivr_index_video_scores plus a top-k on the host.  1 <= k <= IVR_MAX_K.
+ * An empty index yields -FLT_MAX / unused slots only.  IVR_ERR_INVALID: NULL handles, members or outputs, nq < 1, an empty or too large
+ * set, a set_off that does not ascend or leaves [0, nq], nsets or nseg < 1 with their table, an unknown mode, k out of range,
+ * ntotal >= 2^31.
+ *
+ * Launches, all on `stream`: the members tiled and re-tiled so that every set starts a 16-member tile; the row -> video table; then per
+ * chunk of sets the score pass (a workgroup holds up to four member tiles of one set in LDS and streams 128 stored 16-row tiles past
+ * them on the float32 MFMA; it writes no score, but one 32-bit atomic maximum per (member, video run, wave) and one store, or for a
+ * set of more than one block one atomic maximum, per (row, block)), the two reductions (integer atomic adds only), the finish in
+ * float64 and the top-k selection.  Maxima and integer sums do not depend on the order of arrival: the same bits on every run and
+ * stream.  Scratch on the index, grow-only: 4 bytes per (member of a chunk, video) and per (set of a chunk, stored row), 24 bytes per
+ * (set of a chunk, video), two copies of the members.  A chunk holds as many whole sets as keep each table within
+ * IVR_SEQ_CHUNK_SLOTS slots, one at least.  Not graph-capturable (the read-back). */
+#define IVR_VIDEO_MAX_MEMBERS 4096
+#define IVR_VIDEO_FORWARD 0
+#define IVR_VIDEO_BACKWARD 1
+#define IVR_VIDEO_SYMMETRIC 2
+int ivr_index_video_scores(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, const int64_t *set_off /*DEV [nsets+1] or NULL*/, int nsets,
+                           const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, int mode, int normalize_q,
+                           float *V /*DEV [nsets][nseg]*/, ivr_stream stream);
+int ivr_index_video_search(ivr_index *idx, const float *q /*DEV [nq,d]*/, int nq, const int64_t *set_off /*DEV [nsets+1] or NULL*/, int nsets,
+                           const int64_t *seg_off /*DEV [nseg+1] or NULL*/, int nseg, int mode, int normalize_q, int k,
+                           const int64_t *exclude /*DEV [nsets] or NULL*/, int64_t *Vseg /*DEV [nsets][k]*/, float *D /*DEV [nsets][k]*/,
+                           ivr_stream stream);
+
 /* ---- binary codes (faiss IndexBinaryFlat, and the sign-bit encoder of IndexLSH) --------------------------
  * Stands in for faiss.IndexLSH(dimension, 256), one of the index types of _create_index (core.py:1198-1230): a row is stored as
  * nbits sign bits (32 bytes at 256 bits, where the flat index stores 2-4.6 KB) and ranked by Hamming distance.

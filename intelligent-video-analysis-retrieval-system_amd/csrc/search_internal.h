@@ -16,7 +16,7 @@
 //                                 coded-index structs themselves are in search_coded.h)
 // Users: search_index.hip (the index object and its storage), search.hip (group-maximum scans and the top-k driver), search_range.hip,
 // search_scanq.hip, search_ids.hip, search_rows.hip, search_refine.hip, search_seq.hip, search_events.hip, search_groups.hip,
-// search_moments.hip, search_diverse.hip, search_fused.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip, knn.hip and tags.hip.
+// search_moments.hip, search_diverse.hip, search_fused.hip, search_videos.hip, search_ivf.hip and the other list scans, and through self_join.h cluster.hip, knn.hip and tags.hip.
 #pragma once
 #include "ivr_common.h"
 
@@ -360,6 +360,14 @@ struct ivr_index {
     DevBuf<float> tg_labels;         // DEV [C rounded up to 16][dp]: the labels in the storage-tile layout, zero rows behind the last
     DevBuf<uint64_t> tg_table;       // DEV [nseg][C] uint64 mass, [nseg][C] int32 votes, [nseg] int32 rows: the segment tables of a call
     DevBuf<uint64_t> tg_lists;       // DEV: J, D, P [rows of a chunk][t], then count and Z [rows of a chunk]: the row pass of the segment call
+    // video search (ivr_index_video_scores, ivr_index_video_search, search_videos.hip), one chunk of query sets; grow-only, each on its
+    // own.  The row -> segment table goes to gr_seg
+    DevBuf<float> vi_pack;           // DEV [members rounded up to 16][dp]: the members of the call in the tiled query layout, packed
+    DevBuf<float> vi_q;              // DEV [16-member tiles of the call][16][dp]: the same, every set from a tile boundary on
+    DevBuf<int32_t> vi_tab;          // DEV [3][nsets + 1]: members, tiles and blocks in front of every set
+    DevBuf<uint32_t> vi_fmax;        // DEV [members of a chunk][nseg]: the greatest ordered score of each (member, video), 0 = no row
+    DevBuf<uint32_t> vi_bmax;        // DEV [sets of a chunk][ntotal rounded up to 16]: the greatest ordered score of each (set, row)
+    DevBuf<uint64_t> vi_sums;        // DEV [3][sets of a chunk][nseg]: Fsum, Bsum (int64), then the keys (ordered V, ~video)
 
     // The plan of a search: the sizes, bounds and path choices that the reserve functions and the drivers must agree on.
     // strides of the per-query rows of group / 16-row tile / 128-row block maxima, for the index's capacity

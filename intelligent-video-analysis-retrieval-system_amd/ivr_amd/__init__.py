@@ -1,6 +1,6 @@
 """ivr_amd: the HIP-backed pieces of the retrieval system.  The submodules are imported by name (ivr_amd.index, ivr_amd.tower, ...);
 the inverted-file indexes (flat rows, product-quantised and scalar-quantised codes), the binary / LSH indexes, the graph index, the re-ranking index, the product-quantisation (8- and 4-bit codes) and scalar-quantisation indexes
-and the clip search, the event search, the grouped search, the moment search, the diversified search, the fused search, the frame clustering, the neighbour graph, the zero-shot tagging and the perceptual hash with its look-back filters are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
+and the clip search, the event search, the grouped search, the moment search, the diversified search, the fused search, the frame clustering, the neighbour graph, the zero-shot tagging, the video search and the perceptual hash with its look-back filters are also reachable from the package itself, resolved on first use so that importing the package stays free of side effects."""
 _IVF = ("IVFFlatIndex", "IndexIVFFlat", "SearchParametersIVF", "METRIC_INNER_PRODUCT", "METRIC_L2")
 _BINARY = ("BinaryFlatIndex", "IndexBinaryFlat", "IndexLSH", "lsh_rotation")
 _GRAPH = ("GraphFlatIndex", "IndexHNSWFlat", "SearchParametersHNSW", "graph_prune_ref", "graph_link_ref", "graph_build_ref",
@@ -29,10 +29,12 @@ _CLUSTER = ("dbscan", "dbscan_device", "dbscan_ref", "cluster_members", "select_
 _NEIGHBORS = ("knn_graph", "knn_graph_device", "knn_graph_ref", "similarity_graphs", "build_similarity_relationships")
 _TAGGING = ("tag_rows", "tag_rows_device", "tag_segments", "tag_segments_device", "tag_rows_ref", "tag_segments_ref", "tag_prob_bound",
             "zero_shot_labels")
+_VIDEOS = ("video_scores", "video_scores_device", "video_search", "video_search_device", "related_videos", "video_scores_ref",
+           "video_search_ref", "video_sums_ref")
 _KEYFRAMES = ("phash", "phash_device", "phash_ref", "hash_keep_mask", "hash_keep_mask_device", "hash_keep_mask_ref", "kept_window_mask",
               "kept_window_mask_device", "kept_window_mask_ref", "select_keyframes", "select_keyframes_ref", "AdvancedKeyframeExtractor",
               "PerceptualHash")
-__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _PQFS + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL + _GROUPING + _MOMENTS + _DIVERSIFY + _FUSION + _CLUSTER + _NEIGHBORS + _TAGGING + _KEYFRAMES)
+__all__ = list(_IVF + _BINARY + _GRAPH + _REFINE + _PQ + _PQFS + _SQ + _IVFPQ + _IVFSQ + _TEMPORAL + _GROUPING + _MOMENTS + _DIVERSIFY + _FUSION + _CLUSTER + _NEIGHBORS + _TAGGING + _VIDEOS + _KEYFRAMES)
 
 
 def __getattr__(name):
@@ -87,6 +89,9 @@ def __getattr__(name):
     if name in _TAGGING:
         from . import tagging
         return getattr(tagging, name)
+    if name in _VIDEOS:
+        from . import videos
+        return getattr(videos, name)
     if name in _KEYFRAMES:
         from . import keyframes
         return getattr(keyframes, name)

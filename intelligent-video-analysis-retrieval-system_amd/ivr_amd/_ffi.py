@@ -33,6 +33,8 @@ IVR_FUSE_MAX_MEMBERS = 16
 IVR_FUSE_FOLD = {"max": 0, "min": 1, "sum": 2}            # fold / combine of ivr_index_search_fused
 IVR_FUSE_COMBINE = {"margin": 0, "veto": 1}
 IVR_MOMENT_RANK = {"peak": 0, "count": 1}                 # rank of ivr_index_search_moments
+IVR_VIDEO_MAX_MEMBERS = 4096
+IVR_VIDEO_MODE = {"forward": 0, "backward": 1, "symmetric": 2}        # mode of ivr_index_video_scores / ivr_index_video_search
 # flags of ivr_preprocess
 PP_MODE = {"identity": 0, "shortest_edge_crop": 1, "stretch": 2, "letterbox": 3}
 PP_BGR, PP_OUT_F32, PP_OUT_PATCH_MAJOR, PP_BILINEAR = 1 << 4, 1 << 5, 1 << 6, 1 << 7
@@ -150,6 +152,8 @@ _SIGS = {
     "ivr_tag_max_top": (_i, []),
     "ivr_index_tag_rows": (_i, [_p, _p, _i, _i, _f, _i, _f, _i64, _i64, _p, _p, _p, _p, _p, _p]),
     "ivr_index_tag_segments": (_i, [_p, _p, _i, _i, _f, _i, _f, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "ivr_index_video_scores": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _i, _p, _p]),
+    "ivr_index_video_search": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ivr_bin_index_create": (_i, [_p, _i, _i64, C.POINTER(_p)]),
     "ivr_bin_index_destroy": (_i, [_p]),
     "ivr_bin_index_reset": (_i, [_p]),
@@ -247,7 +251,8 @@ _STREAM = {n: len(_SIGS[n][1]) - 1 for n in (
     "ivr_topk_pack", "ivr_topk_merge_packed", "ivr_rowwise_cosine", "ivr_dedup_keep_mask", "ivr_scene_keep_mask",
     "ivr_scene_keep_mask_window", "ivr_frame_quality", "ivr_resize_u8", "ivr_phash", "ivr_hash_keep_mask", "ivr_kept_window_mask",
     "ivr_index_diversify", "ivr_index_search_fused", "ivr_index_range_search_fused", "ivr_index_search_moments",
-    "ivr_index_range_search_moments", "ivr_index_tag_rows", "ivr_index_tag_segments")}
+    "ivr_index_range_search_moments", "ivr_index_tag_rows", "ivr_index_tag_segments", "ivr_index_video_scores",
+    "ivr_index_video_search")}
 
 _lib = None
 _lock = threading.Lock()

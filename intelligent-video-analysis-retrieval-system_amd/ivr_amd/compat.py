@@ -601,6 +601,45 @@ class FAISSRetriever:
             groups = [self._frame_results(qn, idxs, validate_results) for idxs in indices]
             return [results for results in groups if results]
 
+    def _video_folders(self):
+        """(seg_off, the folder_name of every video) of the stored rows: a video is a run of equal folder_name, as for search_grouped."""
+        from .grouping import seg_off_from_labels
+        folders = [self.id_to_metadata[i].folder_name for i in range(self.index.ntotal)]
+        seg_off = seg_off_from_labels(folders)
+        return seg_off, [folders[int(seg_off[s])] if seg_off[s] < seg_off[s + 1] else None for s in range(len(seg_off) - 1)]
+
+    def search_by_video(self, embeddings, k: int = 10, mode: str = "symmetric") -> List[Tuple[str, float]]:
+        """Not in the reference (its search_by_image takes one frame): the k stored VIDEOS that look most like the frames in
+        `embeddings` [m, d], whatever their order, frame rate or cut (ivr_amd.videos.video_search: Chamfer similarity by default,
+        mode="forward" for "contains all of these").  Returns [(folder_name, score)], best first; the scores are the raw measure,
+        without the post-processing of search()."""
+        if not self.is_trained or not self.index:
+            raise RuntimeError("Index not trained. Call build_index first.")
+        if len(self.id_to_metadata) == 0:
+            return []
+        from .videos import video_search
+        with self._lock:
+            q = self._normalize_and_validate_features(embeddings)
+            if q.shape[1] != self.dimension:
+                raise ValueError(f"Query dimension ({q.shape[1]}) != index dimension ({self.dimension})")
+            seg_off, names = self._video_folders()
+            Vseg, D = video_search(self.index, q, k, seg_off=seg_off, mode=mode)
+            return [(names[j], float(v)) for j, v in zip(Vseg[0].tolist(), D[0].tolist()) if j >= 0]
+
+    def related_videos(self, k: int = 10, mode: str = "symmetric") -> Dict[str, List[Tuple[str, float]]]:
+        """Not in the reference: for every stored video its k most similar OTHER videos (ivr_amd.videos.related_videos; quadratic
+        in the stored rows).  Returns {folder_name: [(folder_name, score), ...]}, best first."""
+        if not self.is_trained or not self.index:
+            raise RuntimeError("Index not trained. Call build_index first.")
+        if len(self.id_to_metadata) == 0:
+            return {}
+        from .videos import related_videos
+        with self._lock:
+            seg_off, names = self._video_folders()
+            Vseg, D = related_videos(self.index, seg_off, k, mode)
+            return {names[s]: [(names[j], float(v)) for j, v in zip(Vseg[s].tolist(), D[s].tolist()) if j >= 0]
+                    for s in range(len(names)) if names[s] is not None}
+
     def search_moments(self, query_features, k: int = 10, threshold: float = 0.25, max_gap: int = 1, min_count: int = 1,
                        validate_results=True) -> List[SearchResult]:
         """Not in the reference: the k best MOMENTS of the first query row (ivr_amd.moments.moment_search, rank="peak"): runs of
